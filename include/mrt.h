@@ -155,7 +155,9 @@ typedef struct mrt_opts {
 } mrt_opts;
 
 #define MRT_FLAG_COUNT_SEGMENTS 1u   /* keep the per-launch path-segment counter (mrt_stats.segments): one wave reduction and
-                                        one atomic per wavefront, a read-back when mrt_get_stats is called */
+                                        one atomic per wavefront, a read-back when mrt_get_stats is called.  Implies
+                                        MRT_FLAG_NO_LOOKAHEAD: a look-ahead launch traces samples of later calls, so no call could
+                                        report its own segments */
 #define MRT_FLAG_NO_EVENT_TIMING 2u  /* no HIP events around the kernels (mrt_stats.kernel_ms / reduce_ms stay 0): what a caller that
                                         runs one sample per call (src/cli.rs:162-170) and never asks for stats wants */
 #define MRT_FLAG_NO_LOOKAHEAD 8u     /* one-sample mrt_execute calls always run their own one-sample launch.  Default: a context that

@@ -466,7 +466,8 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     if (const char *f = getenv("MRT_PARTIAL_LIMIT_BYTES")) c->knob_partial_budget = (size_t)strtoull(f, nullptr, 10);                  // tests
     c->knob_partial_fail = getenv("MRT_PARTIAL_FAIL_ALLOC") != nullptr;                                                                // tests
     c->debug_fallbacks = env_on("MRT_DEBUG_FALLBACKS");
-    c->la_enabled = !c->defer && (opts->flags & MRT_FLAG_NO_LOOKAHEAD) == 0;
+    // (MRT_FLAG_COUNT_SEGMENTS: every call runs its own launch, so that mrt_stats.segments counts that call's paths)
+    c->la_enabled = !c->defer && !c->count_segments && (opts->flags & MRT_FLAG_NO_LOOKAHEAD) == 0;
     if (const char *f = getenv("MRT_LOOKAHEAD")) { const int v = atoi(f); if (v <= 1) c->la_enabled = false; else c->la_max = v > 64 ? 64u : (u32)v; }
     {   // both plane sets together stay below 4 GiB (32 samples of a 1080p frame: 2 x 0.8 GB; a 4K frame gets 20 per launch)
         const size_t plane_bytes = (size_t)c->padded_rows * nw * 3 * sizeof(float);
@@ -797,7 +798,9 @@ static int la_launch(mrt_ctx *c, int i, u32 base, u32 n)
 }
 
 // one eager one-sample call served from the look-ahead planes; returns MRT_ERR_LIMIT when the planes cannot be had (the caller
-// then runs the plain launch)
+// then runs the plain launch from here on) and kLaPlain when the two sets would reach past sample index 0xffffffff (the caller
+// runs the plain launch for this call only)
+constexpr int kLaPlain = 1;
 static int run_lookahead(mrt_ctx *c)
 {
     int rc = set_device(c);
@@ -810,8 +813,9 @@ static int run_lookahead(mrt_ctx *c)
         la_drop(c);
         c->la_streak = 2;
         const u32 n0 = 2u < c->la_max ? 2u : c->la_max;
-        if ((rc = la_launch(c, 0, k, n0))) return rc;
         const u32 n1 = 2u * n0 < c->la_max ? 2u * n0 : c->la_max;
+        if ((unsigned long long)k + n0 + n1 > 0xffffffffull) return kLaPlain;      // (a set's base + n must not wrap)
+        if ((rc = la_launch(c, 0, k, n0))) return rc;
         if ((rc = la_launch(c, 1, k + n0, n1))) { (void)hipStreamSynchronize(c->la_stream); c->la_n[0] = c->la_n[1] = 0; return rc; }
         s = 0;
     }
@@ -833,10 +837,10 @@ static int run_lookahead(mrt_ctx *c)
     if (k + 1u == c->la_base[s] + c->la_n[s]) {
         // the set is spent (its last plane has been folded): the next launch goes into it, behind the other set's, twice as long
         const int o = 1 - s;
-        const u32 nb = c->la_base[o] + c->la_n[o];
+        const unsigned long long nb = (unsigned long long)c->la_base[o] + c->la_n[o];
         const u32 nn = 2u * c->la_n[o] < c->la_max ? 2u * c->la_n[o] : c->la_max;
         c->la_n[s] = 0;
-        if (c->la_n[o] && (unsigned long long)nb + nn <= 0xffffffffull) (void)la_launch(c, s, nb, nn);      // (a failure here only means a later call starts over)
+        if (c->la_n[o] && nb + nn <= 0xffffffffull) (void)la_launch(c, s, (u32)nb, nn);      // (a failure here only means a later call starts over)
     }
     return MRT_OK;
 }
@@ -848,8 +852,8 @@ static int run_samples(mrt_ctx *c, uint32_t n_samples)
     if (c->la_enabled && n_samples == 1u && c->local_rows) {
         if (c->la_streak >= 2u) {
             rc = run_lookahead(c);
-            if (rc != MRT_ERR_LIMIT) return rc;
-            c->la_enabled = false;                       // no memory for the planes: the plain per-call launch from here on
+            if (rc == MRT_ERR_LIMIT) c->la_enabled = false;      // no memory for the planes: the plain per-call launch from here on
+            else if (rc != kLaPlain) return rc;                  // (kLaPlain: this call only, at the top of the sample range)
         } else {
             ++c->la_streak;
         }

@@ -693,8 +693,16 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         }
     }
     P.n_lin = (u32)lin_list.size(); P.n_bvh_nodes = (u32)(bvh_nodes.size() / BVH_WORDS);
+    // all_ident: the F_IDENT kernels send every ray through instance 0's matrices, so every instance must be untransformed AND hold
+    // the same matrix bits.  Identities differ in the signs of their zeros (the loader's default dir (-0, -0, -1, -0) against an
+    // explicit [0, 0, -1, 0]), and rot_y * (look * v) of a vector with zero / infinite components can then differ in the sign of a
+    // zero; such scenes take the per-instance kernels.
     out.all_ident = n_inst_total > 0;
-    for (u32 i = 0; i < n_inst_total; ++i) out.all_ident = out.all_ident && (inst_tab[(size_t)i * INST_WORDS + INST_TAG] & TAG_IDENT) != 0u;
+    const u32 xf0 = n_inst_total ? inst_tab[INST_TAG] >> TAG_XF_SHIFT : 0u;
+    for (u32 i = 0; i < n_inst_total && out.all_ident; ++i) {
+        const u32 tag = inst_tab[(size_t)i * INST_WORDS + INST_TAG];
+        out.all_ident = (tag & TAG_IDENT) != 0u && memcmp(&xf_tab[tag >> TAG_XF_SHIFT], &xf_tab[xf0], XF_IDENT * sizeof(float)) == 0;
+    }
     {
         // the culling margin of the instance BVH (mrt_trace.h), one per ray from the root box: 1e-4 of the origin distance (boxes,
         // triangles, mesh root boxes: rounding proportional to the distance) + 4e-6 / r_min of its SQUARE when spheres are bounded

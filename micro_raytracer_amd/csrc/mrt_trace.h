@@ -65,7 +65,7 @@ constexpr u32 kLeafQueue = MRT_LEAF_QUEUE;
 #ifndef MRT_PROBE
 #define MRT_PROBE(phase)
 #endif
-// Work counters, likewise only defined by tests/emu/probe.cpp.
+// Work counters, likewise only defined by the x86 builds of tests/emu (probe.cpp keeps them all, emu.cpp only CT_WALK_OVERFLOW).
 #ifndef MRT_COUNT
 #define MRT_COUNT(counter)
 #endif
@@ -1346,10 +1346,11 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
     st.put(ST_WORD, u2f(job.word));
     st.put(ST_CHUNK, u2f(job.k));                                   // local chunk index of this lane
     u32 s = (g0 + job.k) * kChunk;                                  // global sample index
-    if (s < s_base || planes1) s = s_base;
     {
-        u32 e = (g0 + job.k + 1u) * kChunk;
-        if (e > s_stop) e = s_stop;
+        // chunk end min(s + kChunk, s_stop) from the chunk's start, without forming s + kChunk: the last chunk below 2^32
+        // would wrap it to 0 (s_stop <= 0xffffffff, mrt_execute's limit)
+        u32 e = s_stop - s > kChunk ? s + kChunk : s_stop;
+        if (s < s_base || planes1) s = s_base;
         if (planes1) e = s_base + 1u;
         st.put(ST_SEND, u2f(e));
     }
@@ -1526,8 +1527,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
                     j += P.k_split;
                     alive = j < n_chunks;
                     s = (g0 + j) * kChunk;
-                    e = s + kChunk;
-                    if (e > s_stop) e = s_stop;
+                    e = s_stop - s > kChunk ? s + kChunk : s_stop;   // (no wrap past 2^32, as above)
                 }
                 st.put(ST_CHUNK, u2f(j));
                 st.put(ST_SEND, u2f(e));

@@ -126,4 +126,23 @@ def cases():
         {"type": "plane", "n": [0, 0, 1], "pos": [0, 0, -0.5], "mat": {"albedo": "#4080ff"}}]
     d["scene"]["light"] = [{"type": "point", "pos": [1.0, -1.5, 1.5], "pwr": 0.6}]
     out["meshes_tbvh_nan_origins"] = d
+
+    # ---- untransformed instances whose identities differ only in the sign of a zero: the loader's default dir (-0, -0, -1, -0) next to
+    # explicit [0, 0, -1, 0] / [-0.0, 0, -1, 0] / [0, 0, -1, -0.0].  Their matrices hold zeros of different signs, and rot_y * (look * v)
+    # of a vector with zero / infinite components can differ in the sign of a zero between them.  An axis-aligned pinhole camera on a
+    # lattice point and axis planes make such vectors everywhere.  "mixed": the scene must not take the F_IDENT kernels, which would
+    # send every ray through instance 0's matrices; "uniform": one sign everywhere, the F_IDENT kernels (mrt_pack.cpp all_ident).
+    for name, dirs in (("mixed", [None, [0, 0, -1, 0], [-0.0, 0, -1, 0], [0, 0, -1, -0.0]]), ("uniform", [None] * 4)):
+        def inst(p, k):
+            return [p, dirs[k % 4] if dirs[k % 4] is not None else [-0.0, -0.0, -1, -0.0]]
+        d = _base(res=(24, 16), sample=3, bounce=4, aprt=0.0)
+        d["frame"]["cam"].update(pos=[0.0, -2.0, 0.0], dir=[0, 0, 1, 0])
+        rend = [{"type": "plane", "n": [0, 0, 1], "pos": [0, 0, -1.0], "mat": {"rough": 0.5}},
+                {"type": "plane", "n": [1, 0, 0], "pos": [1.5, 0, 0], "mat": {"metal": 1, "albedo": "#c0e0ff"}},
+                {"type": "box", "sizes": [0.5, 0.5, 0.5], "mat": {"glass": 0.6, "opacity": 0.4},
+                 "inst": [inst([0.0, 0.5, 0.0], 1), inst([-1.0, 1.0, 0.0], 2), inst([0.5, 1.5, 0.5], 3)]},
+                {"type": "sphere", "r": 0.25, "mat": {"emit": 0.5}, "inst": [inst([0.0, 1.0, 0.5], 0), inst([-0.5, 0.0, -0.5], 3)]}]
+        d["scene"]["renderer"] = rend
+        d["scene"]["light"] = [{"type": "point", "pos": [0.0, 0.0, 1.0], "pwr": 0.6}, {"type": "dir", "dir": [0, 0, -1], "pwr": 0.3}]
+        out[f"ident_zero_signs_{name}"] = d
     return out

@@ -6,10 +6,15 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 #include <thread>
 #include <vector>
-#include <atomic>
+
+// walks of the 4-wide triangle-BVH that ran out of walk area and answered through the reference's walk (emu_walk_overflows):
+// the only work counter this build keeps (tests/emu/probe.cpp keeps them all)
+static std::atomic<unsigned long long> g_walk_overflows(0);
+#define MRT_COUNT(counter) do { if ((counter) == CT_WALK_OVERFLOW) g_walk_overflows.fetch_add(1, std::memory_order_relaxed); } while (0)
 
 #include "../../micro_raytracer_amd/csrc/mrt_pack.h"
 #include "../../micro_raytracer_amd/csrc/mrt_post.h"
@@ -28,9 +33,36 @@ static uint32_t walk_cap()
     return c < 4 ? 4u : (c > (int)kWalkCapMax ? kWalkCapMax : (uint32_t)c);
 }
 
+// The F_IDENT form the 256-thread kernels take for this scene (pt_instantiation, mrt_kernels.hip): every instance untransformed
+// and no triangle / map code -- the plain feature set of the scene, or with the instance BVH only its light bit -- or -1
+static int ident_form(const Packed &pk)
+{
+    if (!pk.all_ident) return -1;
+    const u32 need = pk.features & F_ALL;
+    if (pk.features & F_BVH) return (need & (F_BOX | F_TRI | F_MAPS)) ? -1 : (int)((need & F_LIGHTS) | F_BVH | F_IDENT);
+    return (need & (F_TRI | F_MAPS)) ? -1 : (int)(need | F_IDENT);
+}
+
+template <class Stash>
+static void render_ident(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &job, u32 &sg, u32 feat)
+{
+    switch (feat) {
+    case F_IDENT: render_pixel<F_IDENT>(S, st, x, y, job, sg); break;
+    case F_IDENT | F_BOX: render_pixel<F_IDENT | F_BOX>(S, st, x, y, job, sg); break;
+    case F_IDENT | F_LIGHTS: render_pixel<F_IDENT | F_LIGHTS>(S, st, x, y, job, sg); break;
+    case F_IDENT | F_BOX | F_LIGHTS: render_pixel<F_IDENT | F_BOX | F_LIGHTS>(S, st, x, y, job, sg); break;
+    case F_IDENT | F_BVH: render_pixel<F_IDENT | F_BVH>(S, st, x, y, job, sg); break;
+    case F_IDENT | F_LIGHTS | F_BVH: render_pixel<F_IDENT | F_LIGHTS | F_BVH>(S, st, x, y, job, sg); break;
+    default: break;
+    }
+}
+
 extern "C" {
 
 const char *emu_error(void) { return g_err.c_str(); }
+
+// walk-area overflows counted since the last call (CT_WALK_OVERFLOW of mrt_trace.h), and start counting again from 0
+unsigned long long emu_walk_overflows(void) { return g_walk_overflows.exchange(0); }
 
 // pack only: returns code, fills sizes (blob words, nw, nh)
 int emu_pack(const mrt_render_desc *d, uint32_t *blob_words, uint32_t *nw, uint32_t *nh, uint32_t *info /*[8]*/)
@@ -57,6 +89,34 @@ int emu_layout(const mrt_render_desc *d, uint32_t *out /*[32]*/)
                           pk.n_tbvh_nodes, pk.n_nodes, pk.n_tris, pk.n_leaf_ids, pk.n_bvh_nodes, pk.features, P.lds_words_hot};
     for (size_t i = 0; i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
     return 0;
+}
+
+// The F_IDENT kernels send every ray through instance 0's transform X0 (mrt_trace.h trace / isect_instance).  For a scene the
+// packer marks all_ident, rot_y * (look * v) must then be the same bits through every instance's own transform, for every v
+// with components in {+-0, +-0.5, +-inf, NaN} (the vectors that take the mat-vecs; NaN results match any NaN).  Returns the
+// number of (instance, v) pairs that differ, *all_ident = the packer's verdict.
+int emu_ident_xf(const mrt_render_desc *d, uint32_t *all_ident)
+{
+    Packed pk;
+    const int rc = pack_scene(d, pk, g_err);
+    if (rc) return rc;
+    if (all_ident) *all_ident = pk.all_ident ? 1u : 0u;
+    const float *F = reinterpret_cast<const float *>(pk.blob.data());
+    const Params &P = pk.P;
+    const float c[7] = {0.0f, -0.0f, 0.5f, -0.5f, __builtin_inff(), -__builtin_inff(), __builtin_nanf("")};
+    const float *X0 = F + P.off_xf + (ldu(F + P.off_inst, INST_TAG) >> TAG_XF_SHIFT);
+    int bad = 0;
+    for (u32 i = 0; i < P.n_inst; ++i) {
+        const float *X = F + P.off_xf + (ldu(F + P.off_inst, i * INST_WORDS + INST_TAG) >> TAG_XF_SHIFT);
+        for (int a = 0; a < 7; ++a) for (int b = 0; b < 7; ++b) for (int e = 0; e < 7; ++e) {
+            const V3 v = v3(c[a], c[b], c[e]);
+            const V3 p = xf_full(X, v), q = xf_full(X0, v);
+            const float pv[3] = {p.x, p.y, p.z}, qv[3] = {q.x, q.y, q.z};
+            for (int k = 0; k < 3; ++k)
+                if (f2u(pv[k]) != f2u(qv[k]) && !(pv[k] != pv[k] && qv[k] != qv[k])) { ++bad; break; }
+        }
+    }
+    return bad;
 }
 
 int emu_features(const mrt_render_desc *d)
@@ -87,6 +147,7 @@ int emu_render_deep(const mrt_render_desc *d, uint64_t seed, uint32_t sample_bas
     P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32);
     P.n_samples = n_samples; P.sample_base = sample_base; P.k_split = 1; P.accum = accum;
     if (row1 > pk.nh) row1 = pk.nh;
+    const int ident = deep_nodes || warm_only ? -1 : ident_form(pk);
     Scn S;
     S.F = reinterpret_cast<const float *>(pk.blob.data());
     S.U = S.F; S.G = S.F;
@@ -106,6 +167,7 @@ int emu_render_deep(const mrt_render_desc *d, uint64_t seed, uint32_t sample_bas
                     RegStash st; LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
                     if (warm_only) { if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH | F_COLD>(S, st, x, y, job, sg); else render_pixel<F_ALL | F_COLD>(S, st, x, y, job, sg); }
                     else if (deep_nodes) { if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH | F_COLD | F_DEEP>(S, st, x, y, job, sg); else render_pixel<F_ALL | F_COLD | F_DEEP>(S, st, x, y, job, sg); }
+                    else if (ident >= 0) render_ident(S, st, x, y, job, sg, (u32)ident);
                     else if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
                 }
                 local += sg;

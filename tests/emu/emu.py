@@ -24,6 +24,7 @@ def lib():
         L.emu_render.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                  C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.emu_img.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+        L.emu_walk_overflows.restype = C.c_ulonglong
         L.emu_math.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
         L.emu_octree.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -114,3 +115,19 @@ def octree(tris):
     L.emu_octree(_fp(tris), tris.shape[0], _fp(boxes), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
                  ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, C.byref(n_ids))
     return boxes, counts, ids[:n_ids.value]
+
+
+def walk_overflows():
+    """4-wide walks that overflowed their walk area (and answered through the reference's walk) since the last call."""
+    return lib().emu_walk_overflows()
+
+
+def ident_xf(holder):
+    """(all_ident, mismatches): the packer's F_IDENT verdict and the (instance, vector) pairs whose transform differs in any bit
+    from instance 0's on vectors with components in {+-0, +-0.5, +-inf, NaN} (emu.cpp emu_ident_xf)."""
+    L = lib()
+    flag = C.c_uint32()
+    rc = L.emu_ident_xf(C.cast(holder.ptr(), C.c_void_p), C.byref(flag))
+    if rc < 0:
+        raise ValueError((rc, L.emu_error().decode()))
+    return bool(flag.value), rc

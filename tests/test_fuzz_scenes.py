@@ -79,7 +79,9 @@ def ident_scene(seed):
             continue                                      # (plain kernels only: planes, spheres, boxes)
         o.pop("dir", None)
         if "inst" in o:
-            o["inst"] = [[[float(round(c * 2) / 2) for c in i[0]], [0, 0, -1, 0]] for i in o["inst"]]
+            # (the loader's default dir, which the objects without `inst` get: one identity, zeros of one sign, so that the scene
+            # takes the F_IDENT kernels -- mrt_pack.cpp all_ident; tests/edge_cases.py has the mixed signs)
+            o["inst"] = [[[float(round(c * 2) / 2) for c in i[0]], [-0.0, -0.0, -1, -0.0]] for i in o["inst"]]
         elif "pos" in o:
             o["pos"] = [float(round(c * 2) / 2) for c in o["pos"]]
         o.get("mat", {}).pop("tex", None)
@@ -90,6 +92,53 @@ def ident_scene(seed):
     if rng.random() < 0.5:                                # camera on the lattice, looking straight down +y, pinhole
         cam = d["frame"]["cam"]
         cam["pos"] = [0.0, -2.0, 0.0]; cam["dir"] = [0, 0, 1, 0]; cam["aprt"] = 0.0
+    return d
+
+
+def _fuzz_mesh(rng, n):
+    """n triangles (300-1500) of one of the kinds tests/mesh_probe.py draws, at the sizes that fill the triangle BVH: a lobed
+    icosphere, a plain one, a soup of large triangles, small triangles with huge, duplicate and degenerate ones, vertices on
+    a quarter-unit grid (on octree cell boundaries)."""
+    from micro_raytracer_amd import scenes
+    kind = int(rng.integers(0, 5))
+    if kind == 0:
+        t = scenes.bumpy_mesh(n, seed=int(rng.integers(0, 1000)))
+    elif kind == 1:
+        t = scenes.icosphere(3, float(rng.uniform(0.3, 0.6)), tuple(rng.uniform(0.6, 1.4, 3)))[:n]
+    elif kind == 2:
+        t = rng.uniform(-0.6, 0.6, (n, 3, 3))
+    elif kind == 3:
+        t = rng.uniform(-0.6, 0.6, (n, 1, 3)) + rng.uniform(-0.05, 0.05, (n, 3, 3))
+        t[::17] = rng.uniform(-0.8, 0.8, t[::17].shape)
+        t[3::29] = t[2::29][: len(t[3::29])]
+        t[5::31, 1] = t[5::31, 0]
+    else:
+        t = rng.integers(-3, 4, (n, 3, 3)) / 4.0
+    return [[[float(c) for c in v] for v in tri] for tri in np.asarray(t, np.float32)]
+
+
+def mesh_fuzz_scene(seed):
+    """random_scene's materials, lights and cameras around 1-3 meshes of 300-1500 triangles (the triangle-BVH walks: deep
+    levels, full walk areas), some of them in rotated and translated instances, some glass or translucent; small frames."""
+    d = random_scene(seed)
+    rng = np.random.default_rng(seed + 31337)
+    rend = [o for o in d["scene"]["renderer"] if o["type"] in ("plane", "sphere", "box")][:2]
+    for _ in range(int(rng.integers(1, 4))):
+        m = {"albedo": [float(x) for x in rng.uniform(0.2, 1.0, 3)], "rough": float(rng.choice([0, 0.3, 1])), "metal": float(rng.choice([0, 0.7])),
+             "glass": float(rng.choice([0, 0.3, 0.9])), "opacity": float(rng.choice([1, 1, 0.5, 0.1])), "emit": float(rng.choice([0, 0, 0.5]))}
+        o = {"type": "mesh", "mesh": _fuzz_mesh(rng, int(rng.integers(300, 1501))), "mat": m}
+        if rng.random() < 0.5:
+            o["inst"] = [[[float(x) for x in rng.uniform(-1, 1, 3)],
+                          [float(x) for x in np.r_[rng.uniform(-0.9, 0.9), rng.normal(size=3)]] if rng.random() < 0.7 else [0, 0, -1, 0]]
+                         for _ in range(int(rng.integers(1, 4)))]
+        else:
+            o["pos"] = [float(x) for x in rng.uniform(-0.8, 0.8, 3)]
+            o["dir"] = [float(x) for x in np.r_[rng.uniform(-0.9, 0.9), rng.normal(size=3)]] if rng.random() < 0.5 else [0, 0, -1, 0]
+        rend.append(o)
+    d["scene"]["renderer"] = rend
+    d["frame"]["res"] = [int(rng.integers(6, 17)), int(rng.integers(5, 12))]
+    d["frame"]["ssaa"] = 1
+    d["rt"]["sample"] = int(rng.integers(1, 3))
     return d
 
 
