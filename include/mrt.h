@@ -270,6 +270,41 @@ uint32_t mrt_abi_version(void);
 /* Number of HIP devices visible (0 if none); never initialises more than the runtime. */
 int mrt_device_count(void);
 
+/* ---- adaptive sampling: a per-tile noise threshold (not in the reference) ---------------------
+ * Rounds of `step` samples; round r traces the global sample indices [r*step, (r+1)*step) of every pixel of the tiles still
+ * running (a tile = 8x8 pixels of the supersampled frame, x/8, y/8; edge tiles hold only their in-frame pixels).  Every tile
+ * runs until min_samples; from then on the tiles are evaluated after every second round (n = min_samples, min_samples + 2*step,
+ * ...) and a tile whose error (csrc/mrt_adapt.h) is <= threshold stops there for good; none goes past max_samples.  Each
+ * pixel is the uniform render's estimator at its tile's count: the accumulator bytes of a tile that stopped at n equal those
+ * of an n-sample mrt_execute on the same seed.
+ * Rules: step a positive multiple of 16; min_samples and max_samples positive multiples of 2*step, min <= max; threshold >= 0
+ * (inf: every tile stops at min_samples); otherwise MRT_ERR_ARG. */
+typedef struct mrt_adapt {
+    uint32_t min_samples, max_samples, step;
+    float threshold;
+    uint32_t reserved[4];
+} mrt_adapt;
+
+typedef struct mrt_adapt_info {
+    uint64_t samples;                          /* path samples traced by the call */
+    uint32_t rounds, launches, tiles, tiles_converged, min_count, max_count;
+    double   kernel_ms;                        /* HIP-event time of the path-tracing launches, summed (0 under MRT_FLAG_NO_EVENT_TIMING) */
+} mrt_adapt_info;
+
+/* One adaptive render on a context that holds no samples (fresh, or after mrt_reset; none booked under MRT_FLAG_DEFER), run
+ * eagerly.  Sharded and multi-device contexts: MRT_ERR_STATE.  Afterwards mrt_img / mrt_img_ss tone-map each pixel with its
+ * tile's 1/count, mrt_accum returns the sums with *count = the smallest per-pixel count, mrt_get_stats describes this call,
+ * and mrt_execute returns MRT_ERR_STATE until mrt_reset, mrt_set_accum or mrt_set_accum_device returns the context to uniform
+ * sampling.  info and seconds (wall time) may be NULL. */
+int mrt_execute_adaptive(mrt_ctx *ctx, const mrt_adapt *a, mrt_adapt_info *info, double *seconds);
+
+/* Samples accumulated per pixel, counts[nh][nw] (a uniform context: its count everywhere). */
+int mrt_sample_counts(mrt_ctx *ctx, uint32_t *counts);
+
+/* The half buffer H of the last adaptive call, rgb[nh][nw][3]: per pixel the sum of its even-numbered rounds' samples
+ * (count/2 of them).  MRT_ERR_STATE on a context that has run no adaptive call since its last reset. */
+int mrt_adapt_half(mrt_ctx *ctx, float *rgb);
+
 /* Test hook, host only (no device needed): what mrt_create would stage in LDS for this scene and the workgroup shape of its
  * launches -- the policy of csrc/mrt_api.cpp as data, so that it can be checked where no GPU exists. */
 typedef struct mrt_plan {

@@ -86,6 +86,16 @@ class Plan(C.Structure):
                 ("small_plain_grid", C.c_uint32), ("walk_cap", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class Adapt(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("step", C.c_uint32), ("threshold", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class AdaptInfo(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("rounds", C.c_uint32), ("launches", C.c_uint32), ("tiles", C.c_uint32),
+                ("tiles_converged", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
 STAGING = ("all", "warm", "deep", "none")
 MAP_SLOTS = ("tex", "rmap", "mmap", "gmap", "omap", "emap")
 

@@ -15,6 +15,7 @@ SYMBOLS = (
     "mrt_set_accum", "mrt_img", "mrt_img_ss", "mrt_reset", "mrt_get_stats", "mrt_last_error", "mrt_last_status",
     "mrt_abi_version", "mrt_device_count", "mrt_selftest_math", "mrt_padded_rows", "mrt_bind_accum",
     "mrt_set_accum_device", "mrt_save_image", "mrt_selftest_sweep", "mrt_plan_launch",
+    "mrt_execute_adaptive", "mrt_sample_counts", "mrt_adapt_half",
 )
 
 
@@ -51,6 +52,9 @@ def lib():
     L.mrt_destroy.restype = None
     L.mrt_destroy.argtypes = [vp]
     L.mrt_execute.argtypes = [vp, u32, C.POINTER(C.c_double)]
+    L.mrt_execute_adaptive.argtypes = [vp, C.POINTER(_abi.Adapt), C.POINTER(_abi.AdaptInfo), C.POINTER(C.c_double)]
+    L.mrt_sample_counts.argtypes = [vp, u32p]
+    L.mrt_adapt_half.argtypes = [vp, f32p]
     L.mrt_dims.argtypes = [vp, u32p, u32p, u32p]
     L.mrt_accum.argtypes = [vp, f32p, u32p]
     L.mrt_accum_local.argtypes = [vp, f32p, u32p]

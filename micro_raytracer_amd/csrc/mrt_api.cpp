@@ -189,6 +189,11 @@ struct mrt_ctx {
     std::vector<ncclComm_t> comms;
     float *d_gather = nullptr;           // [n_devices][padded_rows][nw][3] on device 0
     u32 *d_rowmap = nullptr;             // [n_devices][padded_rows] frame row of each gathered row (0xffffffff: padding)
+    // adaptive sampling (mrt_execute_adaptive), allocated by the first adaptive call
+    bool adaptive = false;               // the accumulator holds an adaptive render: per-tile counts, count = the smallest
+    float *d_half = nullptr;             // H: [padded_rows][nw][3], per pixel the sum of its even-numbered rounds
+    u32 *d_adapt = nullptr;              // [n_tiles] x 5 + 1: two tile lists, keep flags, per-tile count, per-tile converged flag, list length
+    std::vector<u32> tile_count;         // per-tile counts of the last adaptive call (host copy)
 };
 
 namespace {
@@ -210,7 +215,7 @@ void free_ctx(mrt_ctx *c)
     if (c->la_stream) { (void)hipStreamSynchronize(c->la_stream); (void)hipStreamDestroy(c->la_stream); }
     for (int i = 0; i < 2; ++i) { if (c->la_ev0[i]) (void)hipEventDestroy(c->la_ev0[i]); if (c->la_ev1[i]) (void)hipEventDestroy(c->la_ev1[i]); }
     void *ptrs[] = {c->d_blob, c->d_accum_own, c->d_partial, c->d_segments, c->d_full, c->d_ss, c->d_out, c->d_tmp, c->d_vl, c->d_vc, c->d_hl, c->d_hc, c->d_vw, c->d_hw,
-                    c->d_la[0], c->d_la[1], c->d_la_counter};
+                    c->d_la[0], c->d_la[1], c->d_la_counter, c->d_half, c->d_adapt};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -586,28 +591,20 @@ static int resolve_stats(mrt_ctx *c)
     return MRT_OK;
 }
 
-// asynchronous half of mrt_execute on one device: everything up to the closing event
-static int exec_launch(mrt_ctx *c, uint32_t n_samples)
+// Lanes per pixel (k_split) and sample chunks per launch (cap) of a batch of n_chunks chunks over wave_tiles 8x8 tiles;
+// (re)allocates the chunk planes the split needs.  planes: the batch must go through the chunk planes (k_split >= 2 even for
+// a single chunk: the adaptive even rounds, whose chunk sums are added to the half buffer too) -- MRT_ERR_LIMIT without them.
+static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks, bool planes, u32 &k_split, u32 &cap)
 {
-    int rc = set_device(c);
-    if (rc) return rc;
-    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.launches = 0; c->stats.samples = 0; c->stats.segments = 0;
-    c->stats_pending = false; c->ev_used = 0;
-    if (!(n_samples && c->local_rows)) return MRT_OK;
-    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
-    // sample split: spread a small frame over more wavefronts, one lane per (pixel, every k-th sample chunk)
-    const u32 first_chunk = c->count / kChunk;
-    const u32 end_chunk = (c->count + n_samples - 1u) / kChunk + 1u;
-    const u32 n_chunks = end_chunk - first_chunk;
-    const unsigned long long wave_tiles = (unsigned long long)((c->pk.nw + 7) / 8) * ((c->local_rows + 7) / 8);
-    u32 k_split = 1;
+    k_split = 1;
     // (a frame of 100 000 wave tiles or more -- 4K -- has its 25 rounds without splitting: CornellBox2 at 3840x2160 loses 1.6 %
     // to a second lane per pixel, 985 -> 1001 ms)
     const unsigned long long split_target = wave_tiles >= 100000ull ? 0ull : kSplitTargetWaves;
     while (k_split * 2u <= n_chunks && k_split < 16u && wave_tiles * k_split < split_target) k_split *= 2u;
     if (c->knob_k_split) { k_split = c->knob_k_split; while (k_split > n_chunks) k_split /= 2u; }
+    if (planes && k_split < 2u) k_split = 2u;
     const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
-    u32 cap = kMaxChunksPerLaunch;                       // chunks per launch
+    cap = kMaxChunksPerLaunch;                           // chunks per launch
     if (c->knob_max_chunks) cap = c->knob_max_chunks;
     size_t budget = kPartialBudgetBytes;
     if (c->knob_partial_budget) budget = c->knob_partial_budget;
@@ -623,6 +620,27 @@ static int exec_launch(mrt_ctx *c, uint32_t n_samples)
             else c->partial_floats = need;
         }
     }
+    if (planes && k_split < 2u) return fail(MRT_ERR_LIMIT, "mrt_execute_adaptive: no memory for the chunk planes of a round");
+    return MRT_OK;
+}
+
+// asynchronous half of mrt_execute on one device: everything up to the closing event
+static int exec_launch(mrt_ctx *c, uint32_t n_samples)
+{
+    int rc = set_device(c);
+    if (rc) return rc;
+    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.launches = 0; c->stats.samples = 0; c->stats.segments = 0;
+    c->stats_pending = false; c->ev_used = 0;
+    if (!(n_samples && c->local_rows)) return MRT_OK;
+    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
+    // sample split: spread a small frame over more wavefronts, one lane per (pixel, every k-th sample chunk)
+    const u32 first_chunk = c->count / kChunk;
+    const u32 end_chunk = (c->count + n_samples - 1u) / kChunk + 1u;
+    const u32 n_chunks = end_chunk - first_chunk;
+    const unsigned long long wave_tiles = (unsigned long long)((c->pk.nw + 7) / 8) * ((c->local_rows + 7) / 8);
+    u32 k_split = 1, cap = kMaxChunksPerLaunch;
+    if ((rc = split_policy(c, wave_tiles, n_chunks, false, k_split, cap))) return rc;
+    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
     c->P.partial = c->d_partial;
     c->P.partial_stride = plane;
     c->stats.k_split = k_split;
@@ -878,6 +896,7 @@ constexpr u32 kDeferLimit = 1024u;        // booked samples that trigger a launc
 int mrt_execute(mrt_ctx *c, uint32_t n_samples, double *seconds)
 {
     if (!c) return fail(MRT_ERR_ARG, "mrt_execute: null context");
+    if (c->adaptive) return fail(MRT_ERR_STATE, "mrt_execute: the context holds an adaptive render (per-tile sample counts): mrt_reset first");
     if ((unsigned long long)c->count + c->pending + n_samples > 0xffffffffull) return fail(MRT_ERR_LIMIT, "mrt_execute: sample count overflows u32");
     const auto t0 = std::chrono::steady_clock::now();
     int rc = MRT_OK;
@@ -891,6 +910,175 @@ int mrt_execute(mrt_ctx *c, uint32_t n_samples, double *seconds)
     if (rc) return rc;
     c->stats.deferred = deferred ? 1u : 0u;       // whether THIS call was booked (MRT_FLAG_DEFER honoured) or ran at once
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ok();
+    return MRT_OK;
+}
+
+// ---- adaptive sampling ---------------------------------------------------------------------------------------------------------
+// One round of an adaptive render: samples [base, base + n) of the n_listed tiles of `list`, launched like exec_launch's batches
+// (sample split sized from the listed tiles, chunk-aligned launches), asynchronous.  Even rounds go through the chunk planes
+// and reduce_chunks_listed adds their chunk sums, in chunk order, to the accumulator and to the half buffer alike.
+static int adapt_round(mrt_ctx *c, u32 base, u32 n, bool even, const u32 *list, u32 n_listed)
+{
+    const u32 n_chunks = (base + n - 1u) / kChunk - base / kChunk + 1u;
+    u32 k_split = 1, cap = kMaxChunksPerLaunch;
+    int rc = split_policy(c, n_listed, n_chunks, even, k_split, cap);
+    if (rc) return rc;
+    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
+    c->P.partial = c->d_partial;
+    c->P.partial_stride = plane;
+    const TileList tl{list, n_listed};
+    c->P.persist_grid = c->persist_grid;
+    const u32 bt = c->block_threads;
+    const u32 s_end = base + n;
+    while (base < s_end) {
+        u32 stop = s_end;
+        if (k_split > 1u) {
+            const unsigned long long lim = ((unsigned long long)(base / kChunk) + cap) * kChunk;
+            if (lim < stop) stop = (u32)lim;
+        }
+        const u32 nc = (stop - 1u) / kChunk - base / kChunk + 1u;
+        u32 ks = k_split;
+        while (ks > nc) ks /= 2u;
+        if (even && ks < 2u) ks = 2u;                    // (a lane of chunk phase >= nc has nothing to do)
+        c->P.n_samples = stop - base;
+        c->P.sample_base = base;
+        c->P.k_split = ks;
+        if (ks > c->stats.k_split) c->stats.k_split = ks;
+        while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->evs.push_back(e); }
+        hipEvent_t *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
+        if (bt > 64u && c->P.persist_grid) HIP_TRY(hipMemsetAsync(c->P.tile_counter, 0, sizeof(u32), c->stream));
+        if (c->event_timing) HIP_TRY(hipEventRecord(ev[0], c->stream));
+        HIP_TRY(launch_pt(c->P, bt, c->scene_in_lds, c->pk.features, c->stream, &tl));
+        if (c->event_timing) HIP_TRY(hipEventRecord(ev[1], c->stream));
+        if (ks > 1u)
+            HIP_TRY(launch_reduce_chunks_listed(c->d_accum, even ? c->d_half : nullptr, c->d_partial, list, n_listed, c->pk.nw, c->pk.nh, plane, nc, c->stream));
+        if (c->event_timing) { HIP_TRY(hipEventRecord(ev[2], c->stream)); c->ev_used += 3u; }
+        c->stats.launches += 1u;
+        base = stop;
+    }
+    return MRT_OK;
+}
+
+static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
+{
+    const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u, n_ty = (nh + 7u) / 8u, n_tiles = n_tx * n_ty;
+    const size_t acc_floats = (size_t)c->padded_rows * nw * 3;
+    if (!c->d_half) HIP_TRY(hipMalloc((void **)&c->d_half, acc_floats * sizeof(float)));
+    if (!c->d_adapt) HIP_TRY(hipMalloc((void **)&c->d_adapt, (5u * (size_t)n_tiles + 1u) * sizeof(u32)));
+    u32 *lists[2] = {c->d_adapt, c->d_adapt + n_tiles};
+    u32 *keep = c->d_adapt + 2u * (size_t)n_tiles, *tcount = c->d_adapt + 3u * (size_t)n_tiles, *tconv = c->d_adapt + 4u * (size_t)n_tiles;
+    u32 *d_n = c->d_adapt + 5u * (size_t)n_tiles;
+    std::vector<u32> all(n_tiles);
+    for (u32 t = 0; t < n_tiles; ++t) all[t] = t;
+    HIP_TRY(hipMemcpy(lists[0], all.data(), n_tiles * sizeof(u32), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(c->d_accum, 0, acc_floats * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_half, 0, acc_floats * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(tcount, 0, 2u * (size_t)n_tiles * sizeof(u32), c->stream));
+    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
+    u32 n_active = n_tiles, n = 0, rounds = 0, cur = 0;
+    while (n_active) {
+        for (int r = 0; r < 2; ++r, ++rounds, n += a->step) {
+            const int rc = adapt_round(c, n, a->step, (rounds & 1u) == 0u, lists[cur], n_active);
+            if (rc) return rc;
+        }
+        if (n < a->min_samples) continue;
+        // the stop rule at count n for every tile still running; the next list, and its length (the one read-back of a step)
+        HIP_TRY(launch_adapt_eval(c->d_accum, c->d_half, lists[cur], n_active, nw, nh, n, a->threshold, n >= a->max_samples, keep, tcount, tconv,
+                                  lists[cur ^ 1u], d_n, c->stream));
+        HIP_TRY(hipMemcpyAsync(&n_active, d_n, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        cur ^= 1u;
+    }
+    std::vector<u32> conv(n_tiles);
+    c->tile_count.assign(n_tiles, 0u);
+    HIP_TRY(hipMemcpy(c->tile_count.data(), tcount, n_tiles * sizeof(u32), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(conv.data(), tconv, n_tiles * sizeof(u32), hipMemcpyDeviceToHost));
+    uint64_t samples = 0;
+    u32 lo = 0xffffffffu, hi = 0, n_conv = 0;
+    for (u32 t = 0; t < n_tiles; ++t) {
+        const u32 ty = t / n_tx, tx = t - ty * n_tx;
+        const u32 px = ((nw - tx * 8u) < 8u ? nw - tx * 8u : 8u) * ((nh - ty * 8u) < 8u ? nh - ty * 8u : 8u);
+        const u32 k = c->tile_count[t];
+        samples += (uint64_t)k * px;
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+        n_conv += conv[t] ? 1u : 0u;
+    }
+    c->count = lo;
+    c->adaptive = true;
+    c->stats.samples = samples;
+    c->stats_pending = true;
+    if (info) {
+        int rc = resolve_stats(c);
+        if (rc) return rc;
+        info->samples = samples;
+        info->rounds = rounds;
+        info->launches = c->stats.launches;
+        info->tiles = n_tiles;
+        info->tiles_converged = n_conv;
+        info->min_count = lo;
+        info->max_count = hi;
+        info->kernel_ms = c->stats.kernel_ms;
+    }
+    return MRT_OK;
+}
+
+int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, double *seconds)
+{
+    if (!c || !a) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: null argument");
+    const unsigned long long two = 2ull * a->step;
+    if (a->step == 0u || a->step % kChunk) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: step %u is not a positive multiple of %u", a->step, kChunk);
+    if (a->min_samples == 0u || a->min_samples % two || a->max_samples == 0u || a->max_samples % two)
+        return fail(MRT_ERR_ARG, "mrt_execute_adaptive: min_samples %u and max_samples %u must be positive multiples of 2 * step = %llu", a->min_samples, a->max_samples, two);
+    if (a->min_samples > a->max_samples) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: min_samples %u > max_samples %u", a->min_samples, a->max_samples);
+    if (!(a->threshold >= 0.0f)) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: threshold %g is not >= 0", (double)a->threshold);
+    if (!c->subs.empty() || c->shard_count > 1u) return fail(MRT_ERR_STATE, "mrt_execute_adaptive: sharded and multi-device contexts are not supported");
+    if (c->adaptive || c->count || c->pending || c->d_full)
+        return fail(MRT_ERR_STATE, "mrt_execute_adaptive: the context holds samples (an adaptive render starts from none): mrt_reset first");
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = set_device(c);
+    if (rc) return rc;
+    la_drop(c);
+    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.launches = 0; c->stats.samples = 0; c->stats.segments = 0;
+    c->stats.k_split = 1; c->stats.deferred = 0;
+    c->stats_pending = false; c->ev_used = 0;
+    if ((rc = adapt_run(c, a, info))) {
+        // nothing half done stays behind: the context is an empty uniform one again
+        const std::string keep = g_err;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipMemset(c->d_accum, 0, (size_t)c->padded_rows * c->pk.nw * 3 * sizeof(float));
+        (void)hipGetLastError();
+        c->adaptive = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
+        g_err = keep; g_status = rc;
+        return rc;
+    }
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ok();
+    return MRT_OK;
+}
+
+int mrt_sample_counts(mrt_ctx *c, uint32_t *counts)
+{
+    if (!c || !counts) return fail(MRT_ERR_ARG, "mrt_sample_counts: null argument");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = settle(c))) return rc;
+    const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u;
+    const u32 uniform = c->d_full ? c->full_count : c->count;
+    for (u32 y = 0; y < nh; ++y)
+        for (u32 x = 0; x < nw; ++x) counts[(size_t)y * nw + x] = c->adaptive ? c->tile_count[(y / 8u) * n_tx + x / 8u] : uniform;
+    ok();
+    return MRT_OK;
+}
+
+int mrt_adapt_half(mrt_ctx *c, float *rgb)
+{
+    if (!c || !rgb) return fail(MRT_ERR_ARG, "mrt_adapt_half: null argument");
+    if (!c->adaptive) return fail(MRT_ERR_STATE, "mrt_adapt_half: no adaptive render on this context since its last reset");
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(rgb, c->d_half, (size_t)c->pk.nw * c->pk.nh * 3 * sizeof(float), hipMemcpyDeviceToHost));
     ok();
     return MRT_OK;
 }
@@ -992,6 +1180,7 @@ int mrt_set_accum_device(mrt_ctx *c, const void *dev_rgb, uint32_t count)
     if (rc) return rc;
     if ((rc = settle(c))) return rc;
     la_drop(c);                                   // the sample count changes under what was traced ahead
+    c->adaptive = false;
     const size_t bytes = (size_t)c->pk.nw * c->pk.nh * 3 * sizeof(float);
     if (!c->subs.empty()) return fail(MRT_ERR_STATE, "mrt_set_accum_device: use mrt_set_accum on a multi-device context");
     if (c->shard_count == 1) {
@@ -1013,6 +1202,7 @@ int mrt_set_accum(mrt_ctx *c, const float *rgb, uint32_t count)
     if (rc) return rc;
     if ((rc = settle(c))) return rc;
     la_drop(c);
+    c->adaptive = false;
     const size_t row_bytes = (size_t)c->pk.nw * 3 * sizeof(float);
     if (!c->subs.empty()) {
         HIP_TRY(hipMemcpy(c->d_full, rgb, row_bytes * c->pk.nh, hipMemcpyHostToDevice));
@@ -1043,6 +1233,7 @@ int mrt_reset(mrt_ctx *c)
     int rc = set_device(c);
     if (rc) return rc;
     la_drop(c);
+    c->adaptive = false;
     if (!c->subs.empty()) {
         for (mrt_ctx *s : c->subs) if ((rc = mrt_reset(s))) return rc;
         HIP_TRY(hipSetDevice(c->device));
@@ -1113,6 +1304,11 @@ static int img_tonemap(mrt_ctx *c)
     const float rc = 1.0f / (float)count;
     const float wexp = (1.0f - c->pk.exp) * (1.0f - c->pk.exp);
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    if (c->adaptive) {                        // each pixel with its tile's 1/count (tile counts of the last adaptive call)
+        const u32 n_tiles = ((c->pk.nw + 7u) / 8u) * ((c->pk.nh + 7u) / 8u);
+        HIP_TRY(launch_tonemap_tiles(src, c->d_ss, c->d_adapt + 3u * (size_t)n_tiles, c->pk.nw, c->pk.nh, c->pk.gamma, wexp, c->stream));
+        return MRT_OK;
+    }
     HIP_TRY(launch_tonemap(src, c->d_ss, c->pk.nw * c->pk.nh, rc, c->pk.gamma, wexp, c->stream));
     return MRT_OK;
 }

@@ -9,8 +9,16 @@ namespace mrt {
 hipError_t configure_pt(size_t max_lds_bytes);
 u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features);     // FEAT template argument of the kernel launch_pt picks
 size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 features);
-hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream);
+hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream, const TileList *list = nullptr);
+// mrt_adapt.hip: the tile-list instantiations (launch_pt with a list), their LDS attributes (configure_pt)
+hipError_t launch_pt_list(const Params &P, const TileList &TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst, hipStream_t stream);
+hipError_t configure_pt_list(size_t max_lds_bytes);
 hipError_t launch_reduce_chunks(float *accum, const float *partial, size_t n_words, size_t stride, u32 n_chunks, hipStream_t stream);
+hipError_t launch_reduce_chunks_listed(float *accum, float *half, const float *partial, const u32 *list, u32 n_listed, u32 nw, u32 nh,
+                                       size_t stride, u32 n_chunks, hipStream_t stream);
+hipError_t launch_adapt_eval(const float *accum, const float *half, const u32 *list, u32 n_listed, u32 nw, u32 nh, u32 n, float threshold, bool last,
+                             u32 *keep, u32 *tile_count, u32 *tile_conv, u32 *list_out, u32 *n_out, hipStream_t stream);
+hipError_t launch_tonemap_tiles(const float *accum, unsigned char *out, const u32 *tile_count, u32 nw, u32 nh, float gamma, float wexp, hipStream_t stream);
 hipError_t launch_scatter_rows(float *frame, const float *gathered, const u32 *rowmap, u32 n_rows, u32 row_words, hipStream_t stream);
 hipError_t launch_tonemap(const float *accum, unsigned char *out, u32 n_px, float rc, float gamma, float wexp, hipStream_t stream);
 hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,

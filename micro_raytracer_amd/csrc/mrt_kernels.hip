@@ -3,6 +3,7 @@
 //   pt_megakernel    Sampler::execute (reference src/sampler.rs:28-78) and everything of src/rt.rs
 //                    it reaches: one lane per supersampled pixel, all samples of the launch in
 //                    registers, scene staged in LDS, one accumulator read-modify-write per launch.
+//   (pt_megakernel_list, the same over a list of 8x8 tiles, and the other kernels of adaptive sampling: mrt_adapt.hip)
 //   tonemap_u8       Sampler::img's per-pixel map (src/sampler.rs:84-96)
 //   lanczos3_v/_h    image::imageops::resize(.., Lanczos3) (src/sampler.rs:98): vertical pass to f32,
 //                    horizontal pass to u8, taps precomputed on the host.
@@ -12,163 +13,15 @@
 #include <hip/hip_runtime.h>
 
 #include "mrt_kernels.h"
+#include "mrt_megakernel.h"
 #include "mrt_post.h"
 #include "mrt_trace.h"
 
 namespace mrt {
 
-// Workgroup = tiles_x x tiles_y wavefronts, each wavefront an 8x8 pixel tile (64 lanes): neighbouring
-// pixels share most of their path prefix, which keeps the per-lane predicates of the uniform traversal
-// loop coherent.  Rows are the shard-local rows of this context (block-cyclic over shards).
-// Register budget per instantiation (second __launch_bounds__ argument = minimum waves per SIMD).  The kernel is
-// VALU-issue bound, so the light variants (planes / spheres / boxes, no maps, no lights, no triangles) are squeezed to
-// 6 waves per SIMD (80 VGPRs, a few spills: measured +14 % on the Cornell box); the heavier variants lose more to
-// spills than they gain from occupancy and keep the compiler's choice.  MRT_WAVES_PER_EU overrides (experiments).
-// The per-path LDS stash (mrt_trace.h) is used by every launch shape that has room for it next to the scene: the
-// 64- and 256-thread workgroups with the scene in LDS.  It moves 7-25 VGPRs of rarely touched state out of the loop.
-constexpr bool lds_stash_for(bool scene_in_lds, int block_threads, u32 feat)
-{
-#ifdef MRT_NO_STASH
-    return false;
-#else
-    (void)scene_in_lds;      // scenes read through L2 keep the stash too: the LDS is otherwise empty
-    return block_threads != 512 && !(feat & F_NOSTASH);
-#endif
-}
-#ifndef MRT_BVH_WAVES
-#define MRT_BVH_WAVES 6
-#endif
-constexpr int waves_for(u32 feat_, int block_threads)
-{
-#ifdef MRT_WAVES_PER_EU
-    return MRT_WAVES_PER_EU;
-#else
-    const u32 feat = plain_feat(feat_);      // (F_IDENT changes nothing here)
-    // Planes and spheres only (the Cornell box), 256-thread workgroups: 8 waves per SIMD (64 VGPRs).  With single-wave
-    // workgroups every wavefront brings its own 5.5 KB of LDS (scene copy + stash) and the CU tops out at 29 of them, so a
-    // bound of 8 only bought spills there (-3 %); four waves around one copy need 13 KB and all 32 fit: 7.42 -> 7.93
-    // Gsamples/s on the headline frame (7.71 with the 7-wave build of the same shape).  With boxes (CornellBox2) 8 loses to 7.
-    if (feat == 0u && block_threads == 256) return 8;
-    // The instance-BVH kernels without mesh code, warm staging (F_COLD: texels in global memory, so the LDS no longer caps the
-    // resident wavefronts at one 1024-thread workgroup): bound to 6 waves per SIMD (80 VGPRs, a few spills).  These walks
-    // wait on dependent LDS reads, not on issue slots: the Minecraft-shaped scene gains 12 % with 5 waves, 16 % with 6, 17 %
-    // with 7-8 over the 4 its 114 VGPRs allow.  The mesh kernels stay at 4: their LDS footprint caps them at 16 waves per CU.
-    if ((feat & F_COLD) && (feat & F_BVH) && !(feat & F_TRI)) return MRT_BVH_WAVES;
-    // Scenes with lights but without meshes, triangles or an instance BVH (example/Default.json, dof.json: 106-122 VGPRs as the
-    // compiler would have it, 4 waves): bound to 5 waves per SIMD (96 VGPRs).  1080p renders: default scene 110 -> 118
-    // Gsamples/s, dof scene 17.7 -> 20.3 (6 waves: 111 / 19.2).  The mesh kernels lose with every register taken from them
-    // (kitchen-sink scene: 3284 / 3095 / 2765 Msamples/s at 4 / 5 / 6 waves).
-    if ((feat & F_LIGHTS) && !(feat & (F_TRI | F_BVH | F_COLD | F_NOSTASH)) && block_threads <= 256) return 5;      // (larger workgroups: LDS-capped at 16 waves per CU anyway)
-    return (feat & ~F_BOX) == 0 ? 7 : ((feat & (F_LIGHTS | F_TRI | F_BVH)) == 0 ? 6 : 4);      // the BVH walks need their registers more than two extra waves
-#endif
-}
-
-template <bool SCENE_IN_LDS, int BLOCK_THREADS, u32 FEAT>
-__global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS)) pt_megakernel(const Params P, const u32 *__restrict__ blob_g)
-{
-    extern __shared__ uint4 lds_blob[];
-    const float *F;
-    // words of the scene this workgroup stages: all of it, or (F_COLD) the hot prefix -- records, transforms, materials, node
-    // arrays; triangles, membership tables and texels are then read from global memory
-    const u32 staged_words = !SCENE_IN_LDS ? 0u : staged_words_for(P, FEAT);
-    if (SCENE_IN_LDS) {
-        const uint4 *g = reinterpret_cast<const uint4 *>(P.blob);
-        const u32 n4 = staged_words >> 2;
-        for (u32 i = threadIdx.x; i < n4; i += blockDim.x) lds_blob[i] = g[i];
-        __syncthreads();
-        F = reinterpret_cast<const float *>(lds_blob);
-    } else {
-        F = reinterpret_cast<const float *>(P.blob);
-    }
-
-    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    Scn S;
-    S.F = F;
-#ifdef MRT_UNIFORM_SMEM
-    S.U = reinterpret_cast<const float *>(blob_g);
-#else
-    S.U = F;
-#endif
-    S.G = reinterpret_cast<const float *>(blob_g);
-    S.P = &P;
-    // behind the staged scene (16-byte aligned): [lane stash: ST_SLOTS x blockDim floats] [walk areas: P.walk_cap x blockDim words]
-    const u32 stash_base4 = (staged_words + 3u) >> 2;
-    constexpr bool kStash = lds_stash_for(SCENE_IN_LDS, BLOCK_THREADS, FEAT);
-    S.wk = nullptr; S.wk_stride = BLOCK_THREADS;
-    if constexpr (has_walk_area(FEAT))
-        S.wk = (void *)(reinterpret_cast<float *>(lds_blob + stash_base4) + (kStash ? stash_slots_for(FEAT, BLOCK_THREADS) * BLOCK_THREADS : 0u) + threadIdx.x);
-    u32 segments = 0;
-#ifdef MRT_PHASE_TIMING
-    unsigned long long wave_ticks[4] = {0ull, 0ull, 0ull, 0ull};
-#endif
-    // one 8x8 tile of shard-local rows for this wavefront, lane k of the sample split
-    auto do_tile = [&](u32 tx, u32 ty, u32 k) {
-        const u32 x = tx * 8u + (lane & 7u);
-        const u32 ry = ty * 8u + (lane >> 3);
-        // shard-local row -> frame row: row block b of this shard is frame row block b * shard_count + shard_index
-        const u32 blk = ry / P.shard_rows;
-        const u32 y = (blk * P.shard_count + P.shard_index) * P.shard_rows + (ry - blk * P.shard_rows);
-        const bool active = x < P.nw && ry < P.local_rows && y < P.nh;
-        if (!active) return;
-        u32 seg = 0;
-        LaneJob job;
-        job.k = k;
-        job.word = (ry * P.nw + x) * 3u;        // < 2^32: mrt_create limits a shard to 2^30 pixels
-        if constexpr (lds_stash_for(SCENE_IN_LDS, BLOCK_THREADS, FEAT)) {
-            // per-lane column behind the scene blob (16-byte aligned): ST_SLOTS x blockDim floats
-#ifdef MRT_PHASE_TIMING
-            unsigned long long tk[4] = {0ull, 0ull, 0ull, 0ull};
-#else
-            unsigned long long *tk = nullptr;
-#endif
-            LdsStash<BLOCK_THREADS> st;
-            st.base = (lds_vfloat *)(reinterpret_cast<float *>(lds_blob + stash_base4) + threadIdx.x);
-            render_pixel<FEAT>(S, st, x, y, job, seg, tk);
-#ifdef MRT_PHASE_TIMING
-            for (int k = 0; k < 4; ++k) wave_ticks[k] += tk[k];
-#endif
-        } else {
-            RegStash st;
-            render_pixel<FEAT>(S, st, x, y, job, seg);
-        }
-        segments += seg;
-    };
-    // Persistent workgroup (more than one wavefront, P.persist_grid set): its wavefronts draw tiles from a counter until the
-    // launch is out of tiles, so a CU never waits for the slowest wavefront of a workgroup (whose LDS copy of the scene
-    // would otherwise keep the next workgroup out).  Otherwise blockIdx addresses the one tile of each wavefront.
-    const bool persist = BLOCK_THREADS > 64 && P.persist_grid != 0u;
-    const u32 n_tx = (P.nw + 7u) >> 3, n_ty = (P.local_rows + 7u) >> 3;
-    const u32 per_k = n_tx * n_ty, total = per_k * P.k_split;
-    for (;;) {
-        u32 tx = blockIdx.x * P.tiles_x + wave % P.tiles_x, ty = blockIdx.y * P.tiles_y + wave / P.tiles_x, k = blockIdx.z;
-        if (persist) {
-            u32 t = 0;
-            if (lane == 0) t = atomicAdd(P.tile_counter, 1u);
-            t = __builtin_amdgcn_readfirstlane(t);
-            if (t >= total) break;
-            k = t / per_k;
-            const u32 r = t - k * per_k;
-            ty = r / n_tx;
-            tx = r - ty * n_tx;
-        }
-        do_tile(tx, ty, k);
-        if (!persist) break;
-    }
-#ifdef MRT_PHASE_TIMING
-    // one lane per wavefront (the longest-running one speaks for the wave: every lane carries the wave's clock differences)
-    for (int k = 0; k < 4; ++k) {
-        unsigned long long v = wave_ticks[k];
-        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
-        if (lane == 0 && v) atomicAdd(P.segments + 2 + k, v);
-    }
-#endif
-    if (P.count_segments) {
-        // wave-level sum (every lane of the wavefront is here), one atomic per wavefront
-        u32 v = segments;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0 && v) atomicAdd(P.segments, (unsigned long long)v);
-    }
-}
+#define MRT_PT_LIST 0
+#include "mrt_pt_kernel.h"
+#undef MRT_PT_LIST
 
 // acc[p] += chunk sums in chunk order (the canonical order of mrt_trace.h), one thread per accumulator word
 __global__ void __launch_bounds__(256) reduce_chunks(float *__restrict__ accum, const float *__restrict__ partial, size_t n_words,
@@ -301,11 +154,7 @@ __global__ void __launch_bounds__(256) math_sweep(int op, unsigned long long fir
     }
 }
 
-// ---- launchers (declared in mrt_kernels.h) ----
-// One instantiation per feature set for the two common launch shapes with the scene in LDS: 256 threads (2x2 wave
-// tiles) and 64 threads (one 8x8 tile per workgroup, used when the frame has too few tiles to balance 256 CUs with
-// 4-wave workgroups).  The 512-thread shape (one LDS copy per CU, scenes of 78-160 KB) and the scene-in-L2 fallback
-// and the 1024-thread shape (one LDS copy + stash per CU, 16 waves) carry every feature.
+// ---- launchers (declared in mrt_kernels.h); the instantiations: mrt_megakernel.h ----
 template <int THREADS, u32 FEAT>
 static void launch_lds(dim3 grid, size_t lds, hipStream_t stream, const Params &P)
 {
@@ -353,37 +202,34 @@ u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features)
 
 #define MRT_CASE(T, F) case (F): launch_lds<T, (F)>(grid, lds, stream, P); return hipGetLastError();
 #define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((pt_megakernel<false, 256, (F)>), grid, dim3(256), lds, stream, P, P.blob); return hipGetLastError();
-#define MRT_PLAIN16(T) MRT_CASE(T, 0) MRT_CASE(T, 1) MRT_CASE(T, 2) MRT_CASE(T, 3) MRT_CASE(T, 4) MRT_CASE(T, 5) MRT_CASE(T, 6) MRT_CASE(T, 7) \
-    MRT_CASE(T, 8) MRT_CASE(T, 9) MRT_CASE(T, 10) MRT_CASE(T, 11) MRT_CASE(T, 12) MRT_CASE(T, 13) MRT_CASE(T, 14) MRT_CASE(T, 15)
-#define MRT_BVH4(T, X) MRT_CASE(T, F_BVH | (X)) MRT_CASE(T, F_LIGHTS | F_BVH | (X)) MRT_CASE(T, (F_ALL & ~F_TRI) | F_BVH | (X)) MRT_CASE(T, F_ALL | F_BVH | (X))
-#define MRT_BIG2(T, X) MRT_CASE(T, (F_ALL & ~F_TRI) | (X)) MRT_CASE(T, F_ALL | (X))
-#define MRT_IDENT4(T) MRT_CASE(T, F_IDENT) MRT_CASE(T, F_IDENT | F_BOX) MRT_CASE(T, F_IDENT | F_LIGHTS) MRT_CASE(T, F_IDENT | F_BOX | F_LIGHTS)
-#define MRT_IDENT_BVH2(T) MRT_CASE(T, F_IDENT | F_BVH) MRT_CASE(T, F_IDENT | F_LIGHTS | F_BVH)
-#define MRT_DEEP2(T) MRT_CASE(T, F_ALL | F_COLD | F_DEEP) MRT_CASE(T, F_ALL | F_BVH | F_COLD | F_DEEP)
-
-hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream)
+hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream, const TileList *TL)
 {
     if (block_threads != P.tiles_x * P.tiles_y * 64u) return hipErrorInvalidConfiguration;
     const u32 tile_w = P.tiles_x * 8u, tile_h = P.tiles_y * 8u;
     dim3 grid((P.nw + tile_w - 1) / tile_w, (P.local_rows + tile_h - 1) / tile_h, P.k_split);
+    if (TL) {                                // tile-list launch: one wavefront per listed tile, list entries packed along x
+        if (!TL->n) return hipSuccess;
+        const u32 per_wg = P.tiles_x * P.tiles_y;
+        grid = dim3((TL->n + per_wg - 1) / per_wg, 1, P.k_split);
+    }
     if (block_threads > 64u && P.persist_grid) {
         const unsigned long long n_wg = (unsigned long long)grid.x * grid.y * grid.z;
         grid = dim3((unsigned)(n_wg < P.persist_grid ? n_wg : P.persist_grid), 1, 1);
     }
     const size_t lds = pt_lds_bytes(P, block_threads, scene_in_lds, features);
     const u32 inst = pt_instantiation(block_threads, scene_in_lds, features);
+    if (TL) return launch_pt_list(P, *TL, grid, lds, block_threads, scene_in_lds, inst, stream);
     if (!scene_in_lds) {
         if (block_threads != 256u) return hipErrorInvalidConfiguration;
-        switch (inst) { MRT_CASE_L2(F_ALL & ~F_TRI) MRT_CASE_L2(F_ALL) MRT_CASE_L2((F_ALL & ~F_TRI) | F_BVH) MRT_CASE_L2(F_ALL | F_BVH) default: break; }
+        switch (inst) { MRT_SHAPES_L2 default: break; }
     } else if (block_threads == 64u) {
-        switch (inst) { MRT_PLAIN16(64) MRT_BVH4(64, 0u) default: break; }
+        switch (inst) { MRT_SHAPES_64 default: break; }
     } else if (block_threads == 256u) {
-        switch (inst) { MRT_PLAIN16(256) MRT_IDENT4(256) MRT_BVH4(256, 0u) MRT_IDENT_BVH2(256) MRT_BIG2(256, F_COLD) MRT_BVH4(256, F_COLD) MRT_DEEP2(256) default: break; }
+        switch (inst) { MRT_SHAPES_256 default: break; }
     } else if (block_threads == 512u) {
-        switch (inst) { MRT_BIG2(512, 0u) MRT_BVH4(512, 0u) MRT_IDENT_BVH2(512) MRT_BIG2(512, F_COLD) MRT_BVH4(512, F_COLD) MRT_DEEP2(512) default: break; }
+        switch (inst) { MRT_SHAPES_512 default: break; }
     } else if (block_threads == 1024u) {
-        switch (inst) { MRT_BIG2(1024, 0u) MRT_BVH4(1024, 0u) MRT_IDENT_BVH2(1024) MRT_BIG2(1024, F_NOSTASH) MRT_BVH4(1024, F_NOSTASH)
-                        MRT_BIG2(1024, F_COLD) MRT_BVH4(1024, F_COLD) MRT_DEEP2(1024) default: break; }
+        switch (inst) { MRT_SHAPES_1024 default: break; }
     }
     return hipErrorInvalidConfiguration;
 }
@@ -401,12 +247,9 @@ hipError_t configure_pt(size_t max_lds_bytes)
     const int b = (int)max_lds_bytes;
     hipError_t e;
 #define MRT_CASE(T, F) if ((e = set_lds_attr<T, (F)>(b)) != hipSuccess) return e;
-    MRT_PLAIN16(64) MRT_BVH4(64, 0u)
-    MRT_PLAIN16(256) MRT_IDENT4(256) MRT_BVH4(256, 0u) MRT_IDENT_BVH2(256) MRT_BIG2(256, F_COLD) MRT_BVH4(256, F_COLD) MRT_DEEP2(256)
-    MRT_BIG2(512, 0u) MRT_BVH4(512, 0u) MRT_IDENT_BVH2(512) MRT_BIG2(512, F_COLD) MRT_BVH4(512, F_COLD) MRT_DEEP2(512)
-    MRT_BIG2(1024, 0u) MRT_BVH4(1024, 0u) MRT_IDENT_BVH2(1024) MRT_BIG2(1024, F_NOSTASH) MRT_BVH4(1024, F_NOSTASH) MRT_BIG2(1024, F_COLD) MRT_BVH4(1024, F_COLD) MRT_DEEP2(1024)
+    MRT_SHAPES_64 MRT_SHAPES_256 MRT_SHAPES_512 MRT_SHAPES_1024
 #undef MRT_CASE
-    return hipSuccess;
+    return configure_pt_list(max_lds_bytes);
 }
 
 hipError_t launch_reduce_chunks(float *accum, const float *partial, size_t n_words, size_t stride, u32 n_chunks, hipStream_t stream)

@@ -1,0 +1,138 @@
+// mrt_pt_kernel.h — the path-tracing kernel, included twice (no include guard): by mrt_kernels.hip with MRT_PT_LIST 0 as
+// pt_megakernel, the ordinary launches, and by mrt_adapt.hip with MRT_PT_LIST 1 as pt_megakernel_list, the tile-list
+// launches of adaptive sampling (argument TL).  Two translation units and the preprocessor, not a shared function: the
+// ordinary kernel is then exactly the text it was, and the compiler's decisions for it (registers, spills) do not move.
+// Needs mrt_megakernel.h (lds_stash_for, waves_for) and mrt_trace.h; expands inside namespace mrt.
+#ifndef MRT_PT_LIST
+#error "define MRT_PT_LIST (0: pt_megakernel, 1: pt_megakernel_list) before including mrt_pt_kernel.h"
+#endif
+
+template <bool SCENE_IN_LDS, int BLOCK_THREADS, u32 FEAT>
+#if MRT_PT_LIST
+__global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS)) pt_megakernel_list(const Params P, const u32 *__restrict__ blob_g, const TileList TL)
+#else
+__global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS)) pt_megakernel(const Params P, const u32 *__restrict__ blob_g)
+#endif
+{
+    extern __shared__ uint4 lds_blob[];
+    const float *F;
+    // words of the scene this workgroup stages: all of it, or (F_COLD) the hot prefix -- records, transforms, materials, node
+    // arrays; triangles, membership tables and texels are then read from global memory
+    const u32 staged_words = !SCENE_IN_LDS ? 0u : staged_words_for(P, FEAT);
+    if (SCENE_IN_LDS) {
+        const uint4 *g = reinterpret_cast<const uint4 *>(P.blob);
+        const u32 n4 = staged_words >> 2;
+        for (u32 i = threadIdx.x; i < n4; i += blockDim.x) lds_blob[i] = g[i];
+        __syncthreads();
+        F = reinterpret_cast<const float *>(lds_blob);
+    } else {
+        F = reinterpret_cast<const float *>(P.blob);
+    }
+
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    Scn S;
+    S.F = F;
+#ifdef MRT_UNIFORM_SMEM
+    S.U = reinterpret_cast<const float *>(blob_g);
+#else
+    S.U = F;
+#endif
+    S.G = reinterpret_cast<const float *>(blob_g);
+    S.P = &P;
+    // behind the staged scene (16-byte aligned): [lane stash: ST_SLOTS x blockDim floats] [walk areas: P.walk_cap x blockDim words]
+    const u32 stash_base4 = (staged_words + 3u) >> 2;
+    constexpr bool kStash = lds_stash_for(SCENE_IN_LDS, BLOCK_THREADS, FEAT);
+    S.wk = nullptr; S.wk_stride = BLOCK_THREADS;
+    if constexpr (has_walk_area(FEAT))
+        S.wk = (void *)(reinterpret_cast<float *>(lds_blob + stash_base4) + (kStash ? stash_slots_for(FEAT, BLOCK_THREADS) * BLOCK_THREADS : 0u) + threadIdx.x);
+    u32 segments = 0;
+#ifdef MRT_PHASE_TIMING
+    unsigned long long wave_ticks[4] = {0ull, 0ull, 0ull, 0ull};
+#endif
+    // one 8x8 tile of shard-local rows for this wavefront, lane k of the sample split
+    auto do_tile = [&](u32 tx, u32 ty, u32 k) {
+        const u32 x = tx * 8u + (lane & 7u);
+        const u32 ry = ty * 8u + (lane >> 3);
+        // shard-local row -> frame row: row block b of this shard is frame row block b * shard_count + shard_index
+        const u32 blk = ry / P.shard_rows;
+        const u32 y = (blk * P.shard_count + P.shard_index) * P.shard_rows + (ry - blk * P.shard_rows);
+        const bool active = x < P.nw && ry < P.local_rows && y < P.nh;
+        if (!active) return;
+        u32 seg = 0;
+        LaneJob job;
+        job.k = k;
+        job.word = (ry * P.nw + x) * 3u;        // < 2^32: mrt_create limits a shard to 2^30 pixels
+        if constexpr (lds_stash_for(SCENE_IN_LDS, BLOCK_THREADS, FEAT)) {
+            // per-lane column behind the scene blob (16-byte aligned): ST_SLOTS x blockDim floats
+#ifdef MRT_PHASE_TIMING
+            unsigned long long tk[4] = {0ull, 0ull, 0ull, 0ull};
+#else
+            unsigned long long *tk = nullptr;
+#endif
+            LdsStash<BLOCK_THREADS> st;
+            st.base = (lds_vfloat *)(reinterpret_cast<float *>(lds_blob + stash_base4) + threadIdx.x);
+            render_pixel<FEAT>(S, st, x, y, job, seg, tk);
+#ifdef MRT_PHASE_TIMING
+            for (int k = 0; k < 4; ++k) wave_ticks[k] += tk[k];
+#endif
+        } else {
+            RegStash st;
+            render_pixel<FEAT>(S, st, x, y, job, seg);
+        }
+        segments += seg;
+    };
+    // Persistent workgroup (more than one wavefront, P.persist_grid set): its wavefronts draw tiles from a counter until the
+    // launch is out of tiles, so a CU never waits for the slowest wavefront of a workgroup (whose LDS copy of the scene
+    // would otherwise keep the next workgroup out).  Otherwise blockIdx addresses the one tile of each wavefront.
+    // A tile-list launch (pt_megakernel_list) maps its tile index i -- counter-drawn or blockIdx-addressed -- to TL.tiles[i].
+    const bool persist = BLOCK_THREADS > 64 && P.persist_grid != 0u;
+    const u32 n_tx = (P.nw + 7u) >> 3, n_ty = (P.local_rows + 7u) >> 3;
+#if MRT_PT_LIST
+    const u32 per_k = TL.n, total = per_k * P.k_split;
+#else
+    const u32 per_k = n_tx * n_ty, total = per_k * P.k_split;
+#endif
+    for (;;) {
+        u32 tx = blockIdx.x * P.tiles_x + wave % P.tiles_x, ty = blockIdx.y * P.tiles_y + wave / P.tiles_x, k = blockIdx.z;
+        if (persist) {
+            u32 t = 0;
+            if (lane == 0) t = atomicAdd(P.tile_counter, 1u);
+            t = __builtin_amdgcn_readfirstlane(t);
+            if (t >= total) break;
+            k = t / per_k;
+#if MRT_PT_LIST
+            const u32 r = TL.tiles[t - k * per_k];
+#else
+            const u32 r = t - k * per_k;
+#endif
+            ty = r / n_tx;
+            tx = r - ty * n_tx;
+        }
+#if MRT_PT_LIST
+        else {
+            // plain grid of a list launch: grid.x = ceil(n_listed / waves per workgroup), wavefront -> list entry
+            const u32 i = blockIdx.x * (P.tiles_x * P.tiles_y) + wave;
+            if (i >= per_k) break;
+            const u32 r = TL.tiles[i];
+            ty = r / n_tx;
+            tx = r - ty * n_tx;
+        }
+#endif
+        do_tile(tx, ty, k);
+        if (!persist) break;
+    }
+#ifdef MRT_PHASE_TIMING
+    // one lane per wavefront (the longest-running one speaks for the wave: every lane carries the wave's clock differences)
+    for (int k = 0; k < 4; ++k) {
+        unsigned long long v = wave_ticks[k];
+        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
+        if (lane == 0 && v) atomicAdd(P.segments + 2 + k, v);
+    }
+#endif
+    if (P.count_segments) {
+        // wave-level sum (every lane of the wavefront is here), one atomic per wavefront
+        u32 v = segments;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if (lane == 0 && v) atomicAdd(P.segments, (unsigned long long)v);
+    }
+}

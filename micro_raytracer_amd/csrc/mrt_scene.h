@@ -170,4 +170,11 @@ struct Params {
     u32 persist_grid;        // workgroups of a persistent launch (0: one workgroup per tile block, blockIdx addresses the tiles)
 };
 
+// Tile-list launches (adaptive sampling, mrt_execute_adaptive): only the n 8x8 wave tiles tiles[i] = ty * n_tx + tx are traced.
+// A kernel argument of its own (pt_megakernel_list), not a Params field: the ordinary launches keep their argument block.
+struct TileList {
+    const u32 *tiles;
+    u32 n;
+};
+
 }  // namespace mrt

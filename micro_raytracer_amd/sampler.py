@@ -165,6 +165,38 @@ class Sampler:
         _lib.check(_lib.lib().mrt_execute(self._ctx, n_samples, C.byref(secs)))
         return secs.value
 
+    def execute_adaptive(self, render: Render, threshold: float, min_samples: int = 32, max_samples=None, step: int = 16) -> dict:
+        """Tile-adaptive sampling (mrt_execute_adaptive): rounds of `step` samples; from `min_samples` on, every 8x8 tile whose
+        noise estimate is <= `threshold` after an even number of rounds stops, none goes past `max_samples` (default
+        render.rt.sample).  Needs a context without samples (a fresh Sampler, or reset()).  Returns mrt_adapt_info as a dict
+        plus the wall time ("seconds")."""
+        self._ensure(render)
+        a = _abi.Adapt()
+        a.min_samples = int(min_samples)
+        a.max_samples = int(render.rt.sample if max_samples is None else max_samples)
+        a.step = int(step)
+        a.threshold = float(threshold)
+        info = _abi.AdaptInfo()
+        secs = C.c_double()
+        _lib.check(_lib.lib().mrt_execute_adaptive(self._ctx, C.byref(a), C.byref(info), C.byref(secs)))
+        out = {k: getattr(info, k) for k, _ in info._fields_}
+        out["seconds"] = secs.value
+        return out
+
+    def sample_counts(self) -> np.ndarray:
+        """Samples accumulated per supersampled pixel, uint32 [nh][nw]."""
+        self._need()
+        out = np.empty((self.nh, self.nw), np.uint32)
+        _lib.check(_lib.lib().mrt_sample_counts(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def adapt_half(self) -> np.ndarray:
+        """The half buffer of the last adaptive call: per pixel the f32 sum of its even-numbered rounds, [nh][nw][3]."""
+        self._need()
+        out = np.empty((self.nh, self.nw, 3), np.float32)
+        _lib.check(_lib.lib().mrt_adapt_half(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
     def img(self, frame=None) -> np.ndarray:
         self._need()
         out = np.empty((self.res[1], self.res[0], 3), np.uint8)
