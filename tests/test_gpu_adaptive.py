@@ -33,9 +33,9 @@ def _scene(name):
     return _CACHE[name]
 
 
-def _adaptive(render, thr, max_samples=MAX, step=STEP, min_samples=MIN, flags=0):
+def _adaptive(render, thr, max_samples=MAX, step=STEP, min_samples=MIN, flags=0, seed=SEED):
     from micro_raytracer_amd import Sampler
-    s = Sampler(seed=SEED, device=0, flags=flags)
+    s = Sampler(seed=seed, device=0, flags=flags)
     info = s.execute_adaptive(render, thr, min_samples=min_samples, max_samples=max_samples, step=step)
     A, cnt = s.accum()
     out = dict(info=info, A=A, cnt=cnt, counts=s.sample_counts(), H=s.adapt_half(), s=s)
@@ -46,9 +46,9 @@ def _tile_counts(counts):
     return counts[::8, ::8]
 
 
-def _uniform(render, n):
+def _uniform(render, n, seed=SEED):
     from micro_raytracer_amd import Sampler
-    s = Sampler(seed=SEED, device=0)
+    s = Sampler(seed=seed, device=0)
     s.execute(render, n_samples=n)
     return s
 
@@ -240,3 +240,126 @@ def test_cli_adaptive_png_equals_sampler_img(tmp_path, capsys):
     _lib.save_image(str(ref), s.img())
     s.close()
     assert out.read_bytes() == ref.read_bytes()
+
+
+# ---- more than one adapt_compact block: the tile list is compacted by one 1024-thread workgroup in blocks of 1024 entries,
+# and each block's survivors are written after the survivors of the blocks before it
+BIG_MIN, BIG_MAX, BIG_STEP = 32, 96, 16
+
+
+def _big_scenes():
+    from micro_raytracer_amd import scenes
+    # 48 x 42 = 2016 tiles each.  The Cornell box of cornell_box() is not used: its tile errors at MIN take a few hundred
+    # discrete values (single paths reaching the one emitter), and hundreds of tiles tie around the 1024th.
+    return {"cornell2_384x336": scenes.cornell_box2(res=(384, 336), ssaa=1, sample=BIG_MAX, bounce=8),
+            "mesh_ssaa2_192x168": scenes.mesh_scene(res=(192, 168), ssaa=2, sample=BIG_MAX, bounce=6)}
+
+
+@pytest.mark.parametrize("name", ["cornell2_384x336", "mesh_ssaa2_192x168"])
+def test_adaptive_beyond_one_compaction_block(name, oracle_mod):
+    render, _ = make_holder(_big_scenes()[name])
+    n_tiles = ((render.frame.nw + 7) // 8) * ((render.frame.nh + 7) // 8)
+    for seed in range(SEED, SEED + 8):
+        # the tile errors at MIN; a seed whose errors tie where a threshold must separate them is passed over.  "Nearly all
+        # active": the first gap above the smallest errors (black tiles all have error 0)
+        kw = dict(min_samples=BIG_MIN, max_samples=BIG_MAX, step=BIG_STEP, seed=seed)
+        r = _adaptive(render, float("inf"), **kw)
+        e0, nan0, _ = np_tile_errors(r["A"], r["H"], BIG_MIN, 0.0)
+        r["s"].close()
+        assert e0.size == n_tiles > 1024 and not nan0.any()
+        es = np.sort(e0.reshape(-1))
+        j0 = int(np.flatnonzero(es[1:] > es[:-1])[0])
+        targets = (1023, 1024, 1025, n_tiles - 1 - j0)
+        if all(es[n_tiles - 1 - k] < es[n_tiles - k] for k in targets):
+            break
+    else:
+        raise AssertionError("every seed tried has tied tile errors at a target")
+    uniform = {n: _uniform(render, n, seed=seed) for n in range(BIG_MIN, BIG_MAX + 1, 2 * BIG_STEP)}
+    U = {n: (u.accum()[0], u.img_ss()) for n, u in uniform.items()}
+    for u in uniform.values():
+        u.close()
+    fw, fh = render.frame.res
+    for active in targets:
+        j = n_tiles - 1 - active                           # threshold = the (j+1)-th smallest error: j + 1 tiles stop at MIN
+        assert es[j] < es[j + 1], (active, es[j:j + 2])
+        thr = float(es[j])
+        a = _adaptive(render, thr, **kw)
+        counts, info, A, H = a["counts"], a["info"], a["A"], a["H"]
+        tc = _tile_counts(counts)
+        conv0 = e0 <= np.float32(thr)
+        assert int((~conv0).sum()) == active
+        assert np.array_equal(tc > BIG_MIN, ~conv0), active       # exactly the tiles numpy leaves running go on
+        stops = np.unique(tc)
+        assert all(n % (2 * BIG_STEP) == 0 and BIG_MIN <= n <= BIG_MAX for n in stops.tolist()), stops
+        ss = a["s"].img_ss()
+        for n in stops.tolist():
+            m = counts == n
+            assert np.array_equal(A[m], U[n][0][m]) and np.array_equal(ss[m], U[n][1][m]), (active, n)
+        for n in stops.tolist():                                 # a tile stopped below MAX is converged at its count
+            if n < BIG_MAX:
+                assert np_tile_errors(A, H, n, thr)[2][tc == n].all(), (active, n)
+        c = _adaptive(render, thr, min_samples=BIG_MIN, max_samples=2 * BIG_MIN, step=BIG_STEP, seed=seed)   # ... and one beyond 64 is not at 64
+        assert not np_tile_errors(c["A"], c["H"], 2 * BIG_MIN, thr)[2][tc > 2 * BIG_MIN].any(), active
+        c["s"].close()
+        # the info block, replayed on the host from the counts
+        at_max = tc == BIG_MAX
+        conv_max = np_tile_errors(A, H, BIG_MAX, thr)[2]
+        assert info["tiles"] == n_tiles
+        assert info["tiles_converged"] == int((~at_max).sum() + (conv_max & at_max).sum()), active
+        assert info["samples"] == int(counts.astype(np.int64).sum())
+        assert info["rounds"] == int(tc.max()) // BIG_STEP
+        assert info["min_count"] == tc.min() and info["max_count"] == tc.max()
+        if (fw, fh) != (counts.shape[1], counts.shape[0]):
+            assert np.array_equal(a["s"].img(), oracle_mod.lanczos3_resize(ss, fw, fh))
+        print(f"{name} seed {seed}: {active} of {n_tiles} tiles active after the first evaluation, stops {stops.tolist()}, "
+              f"{info['rounds']} rounds, {info['tiles_converged']} converged")
+        a["s"].close()
+
+
+# ---- a failed adaptive call leaves an empty uniform context behind (mrt_execute_adaptive's rollback)
+@pytest.mark.parametrize("bound", [False, True], ids=["own", "bound"])
+@pytest.mark.parametrize("knob", ["MRT_PARTIAL_LIMIT_BYTES", "MRT_PARTIAL_FAIL_ALLOC"])
+def test_adaptive_failure_rolls_back_to_an_empty_uniform_context(knob, bound, monkeypatch):
+    from micro_raytracer_amd import MrtError, Sampler, _abi
+    from test_image_path import DeviceBuffer
+    render, _ = _scene("partial100x60")
+    probe = Sampler(seed=SEED, device=0).create(render)
+    plane = probe.padded_rows() * probe.nw * 3 * 4                # bytes of one chunk plane
+    probe.close()
+    with monkeypatch.context() as mp:
+        mp.setenv(knob, str(plane - 4) if knob == "MRT_PARTIAL_LIMIT_BYTES" else "1")
+        s = Sampler(seed=SEED, device=0).create(render)
+    t = None
+    if bound:
+        t = DeviceBuffer(plane, fill=3.0)
+        s.bind_accum(t.ptr.value, t.nbytes)
+    with pytest.raises(MrtError) as e:
+        s.execute_adaptive(render, 0.05, min_samples=32, max_samples=64)
+    assert e.value.code == _abi.MRT_ERR_LIMIT and "chunk planes" in e.value.msg
+    with pytest.raises(MrtError) as e:
+        s.img()
+    assert e.value.code == _abi.MRT_ERR_STATE
+    with pytest.raises(MrtError) as e:
+        s.adapt_half()
+    assert e.value.code == _abi.MRT_ERR_STATE
+    A, cnt = s.accum()
+    assert cnt == 0 and not A.any() and (s.sample_counts() == 0).all()
+    if bound:
+        t.synchronize()
+        assert not t.read().any()
+    s.execute(render, n_samples=20)
+    f = _uniform(render, 20)
+    A, cnt = s.accum()
+    F, fcnt = f.accum()
+    assert cnt == fcnt == 20 and np.array_equal(A.view(np.uint32), F.view(np.uint32))
+    assert np.array_equal(s.img(), f.img())
+    if bound:
+        t.synchronize()
+        assert np.array_equal(t.read(np.uint32).reshape(-1, s.nw, 3)[:s.nh], F.view(np.uint32))
+    with pytest.raises(MrtError) as e:
+        s.adapt_half()
+    assert e.value.code == _abi.MRT_ERR_STATE
+    f.close()
+    s.close()
+    if bound:
+        t.free()
