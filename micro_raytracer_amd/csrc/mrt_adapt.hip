@@ -111,48 +111,12 @@ __global__ void __launch_bounds__(256) tonemap_tiles_u8(const float *__restrict_
 }
 
 // ---- launchers (declared in mrt_kernels.h) ----
-template <int THREADS, u32 FEAT>
-static void launch_list_lds(dim3 grid, size_t lds, hipStream_t stream, const Params &P, const TileList &TL)
-{
-    hipLaunchKernelGGL((pt_megakernel_list<true, THREADS, FEAT>), grid, dim3(THREADS), lds, stream, P, P.blob, TL);
-}
-
-#define MRT_CASE(T, F) case (F): launch_list_lds<T, (F)>(grid, lds, stream, P, TL); return hipGetLastError();
-#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((pt_megakernel_list<false, 256, (F)>), grid, dim3(256), lds, stream, P, P.blob, TL); return hipGetLastError();
 hipError_t launch_pt_list(const Params &P, const TileList &TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst, hipStream_t stream)
 {
-    if (!scene_in_lds) {
-        if (block_threads != 256u) return hipErrorInvalidConfiguration;
-        switch (inst) { MRT_SHAPES_L2 default: break; }
-    } else if (block_threads == 64u) {
-        switch (inst) { MRT_SHAPES_64 default: break; }
-    } else if (block_threads == 256u) {
-        switch (inst) { MRT_SHAPES_256 default: break; }
-    } else if (block_threads == 512u) {
-        switch (inst) { MRT_SHAPES_512 default: break; }
-    } else if (block_threads == 1024u) {
-        switch (inst) { MRT_SHAPES_1024 default: break; }
-    }
-    return hipErrorInvalidConfiguration;
-}
-#undef MRT_CASE
-#undef MRT_CASE_L2
-
-template <int THREADS, u32 FEAT>
-static hipError_t set_list_lds_attr(int bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&pt_megakernel_list<true, THREADS, FEAT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return launch_pt_inst(P, &TL, grid, lds, block_threads, scene_in_lds, inst, stream);
 }
 
-hipError_t configure_pt_list(size_t max_lds_bytes)
-{
-    const int b = (int)max_lds_bytes;
-    hipError_t e;
-#define MRT_CASE(T, F) if ((e = set_list_lds_attr<T, (F)>(b)) != hipSuccess) return e;
-    MRT_SHAPES_64 MRT_SHAPES_256 MRT_SHAPES_512 MRT_SHAPES_1024
-#undef MRT_CASE
-    return hipSuccess;
-}
+hipError_t configure_pt_list(size_t max_lds_bytes) { return configure_pt_inst(max_lds_bytes); }
 
 hipError_t launch_reduce_chunks_listed(float *accum, float *half, const float *partial, const u32 *list, u32 n_listed, u32 nw, u32 nh,
                                        size_t stride, u32 n_chunks, hipStream_t stream)

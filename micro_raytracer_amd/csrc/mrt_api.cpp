@@ -198,6 +198,9 @@ struct mrt_ctx {
 
 namespace {
 
+// floats of one [padded_rows][nw][3] plane: the accumulator, H, a chunk plane, a look-ahead plane
+size_t plane_floats(const mrt_ctx *c) { return (size_t)c->padded_rows * c->pk.nw * 3; }
+
 int set_device(const mrt_ctx *c)
 {
     HIP_TRY(hipSetDevice(c->device));
@@ -405,7 +408,7 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     c->whole_frame = shard_count == 1;
 
     // rows of this shard: row block b (shard_rows rows) belongs to shard b % shard_count
-    const u32 nh = c->pk.nh, nw = c->pk.nw;
+    const u32 nh = c->pk.nh;
     for (u32 y = 0; y < nh; ++y) if ((y / c->shard_rows) % shard_count == c->shard_index) c->row_of.push_back(y);
     c->local_rows = (u32)c->row_of.size();
 
@@ -423,7 +426,7 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
         c->padded_rows = ((n_blocks + shard_count - 1) / shard_count) * c->shard_rows;
         if (shard_count == 1) c->padded_rows = nh;
     }
-    const size_t acc_bytes = (size_t)c->padded_rows * nw * 3 * sizeof(float);
+    const size_t acc_bytes = plane_floats(c) * sizeof(float);
     if ((e = hipMalloc((void **)&c->d_accum_own, acc_bytes)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(accumulator)", e);
     c->d_accum = c->d_accum_own;
     if ((e = hipMemset(c->d_accum, 0, acc_bytes)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
@@ -475,7 +478,7 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     c->la_enabled = !c->defer && !c->count_segments && (opts->flags & MRT_FLAG_NO_LOOKAHEAD) == 0;
     if (const char *f = getenv("MRT_LOOKAHEAD")) { const int v = atoi(f); if (v <= 1) c->la_enabled = false; else c->la_max = v > 64 ? 64u : (u32)v; }
     {   // both plane sets together stay below 4 GiB (32 samples of a 1080p frame: 2 x 0.8 GB; a 4K frame gets 20 per launch)
-        const size_t plane_bytes = (size_t)c->padded_rows * nw * 3 * sizeof(float);
+        const size_t plane_bytes = plane_floats(c) * sizeof(float);
         const size_t fit = plane_bytes ? ((size_t)2u << 30) / plane_bytes : 0;
         if (fit < 2) c->la_enabled = false; else if (fit < c->la_max) c->la_max = (u32)fit;
     }
@@ -513,7 +516,7 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
     if ((e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", hipGetErrorString(e));
     if ((e = hipEventCreate(&g->ev0)) != hipSuccess || (e = hipEventCreate(&g->ev1)) != hipSuccess) return bail("hipEventCreate", hipGetErrorString(e));
     const u32 pr = g->subs[0]->padded_rows, nw = g->pk.nw, nh = g->pk.nh;
-    const size_t plane = (size_t)pr * nw * 3;
+    const size_t plane = plane_floats(g->subs[0]);
     if ((e = hipMalloc((void **)&g->d_full, (size_t)nh * nw * 3 * sizeof(float))) != hipSuccess) return bail("hipMalloc(frame)", hipGetErrorString(e));
     if ((e = hipMemset(g->d_full, 0, (size_t)nh * nw * 3 * sizeof(float))) != hipSuccess) return bail("hipMemset", hipGetErrorString(e));
     if ((e = hipMalloc((void **)&g->d_gather, plane * n * sizeof(float))) != hipSuccess) return bail("hipMalloc(gather)", hipGetErrorString(e));
@@ -603,7 +606,7 @@ static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks,
     while (k_split * 2u <= n_chunks && k_split < 16u && wave_tiles * k_split < split_target) k_split *= 2u;
     if (c->knob_k_split) { k_split = c->knob_k_split; while (k_split > n_chunks) k_split /= 2u; }
     if (planes && k_split < 2u) k_split = 2u;
-    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
+    const size_t plane = plane_floats(c);
     cap = kMaxChunksPerLaunch;                           // chunks per launch
     if (c->knob_max_chunks) cap = c->knob_max_chunks;
     size_t budget = kPartialBudgetBytes;
@@ -624,28 +627,33 @@ static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks,
     return MRT_OK;
 }
 
-// asynchronous half of mrt_execute on one device: everything up to the closing event
-static int exec_launch(mrt_ctx *c, uint32_t n_samples)
+// One trace launch of P on `stream`: the tile counter P draws from is reset first when the launch is persistent (before ev0, so
+// the kernel time leaves the reset out), then ev0, launch_pt, ev1 (null events are not recorded).  tl: a tile-list launch.
+static int launch_trace(mrt_ctx *c, const Params &P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const TileList *tl)
 {
-    int rc = set_device(c);
-    if (rc) return rc;
-    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.launches = 0; c->stats.samples = 0; c->stats.segments = 0;
-    c->stats_pending = false; c->ev_used = 0;
-    if (!(n_samples && c->local_rows)) return MRT_OK;
-    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
+    if (c->block_threads > 64u && P.persist_grid) HIP_TRY(hipMemsetAsync(P.tile_counter, 0, sizeof(u32), stream));
+    if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
+    HIP_TRY(launch_pt(P, c->block_threads, c->scene_in_lds, c->pk.features, stream, tl));
+    if (ev1) HIP_TRY(hipEventRecord(ev1, stream));
+    return MRT_OK;
+}
+
+// Samples [base, base + n) of the whole frame (tl null) or of the listed tiles, asynchronous on c->stream: the sample split
+// (split_policy, sized from the tiles traced), cut into chunk-aligned launches, each followed by the fold of its chunk sums into
+// the accumulator -- and into `half` too when it is not null (listed tiles only).  planes: every launch goes through the chunk
+// planes.  k_split receives split_policy's lanes per pixel; ks_max is raised to the largest split of any launch.
+static int launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *half, bool planes, u32 &k_split, u32 &ks_max)
+{
+    const u32 n_chunks = (base + n - 1u) / kChunk - base / kChunk + 1u;
     // sample split: spread a small frame over more wavefronts, one lane per (pixel, every k-th sample chunk)
-    const u32 first_chunk = c->count / kChunk;
-    const u32 end_chunk = (c->count + n_samples - 1u) / kChunk + 1u;
-    const u32 n_chunks = end_chunk - first_chunk;
-    const unsigned long long wave_tiles = (unsigned long long)((c->pk.nw + 7) / 8) * ((c->local_rows + 7) / 8);
-    u32 k_split = 1, cap = kMaxChunksPerLaunch;
-    if ((rc = split_policy(c, wave_tiles, n_chunks, false, k_split, cap))) return rc;
-    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
+    const unsigned long long wave_tiles = tl ? tl->n : (unsigned long long)((c->pk.nw + 7) / 8) * ((c->local_rows + 7) / 8);
+    u32 cap = kMaxChunksPerLaunch;
+    int rc = split_policy(c, wave_tiles, n_chunks, planes, k_split, cap);
+    if (rc) return rc;
+    const size_t plane = plane_floats(c);
     c->P.partial = c->d_partial;
     c->P.partial_stride = plane;
-    c->stats.k_split = k_split;
-    const u32 s_end = c->count + n_samples;
-    u32 base = c->count;
+    const u32 s_end = base + n;
     while (base < s_end) {
         // this launch: samples [base, stop), stop on a chunk boundary (or the end); k_split == 1 needs no buffer: one launch
         u32 stop = s_end;
@@ -656,26 +664,46 @@ static int exec_launch(mrt_ctx *c, uint32_t n_samples)
         const u32 nc = (stop - 1u) / kChunk - base / kChunk + 1u;
         u32 ks = k_split;
         while (ks > nc) ks /= 2u;
+        if (planes && ks < 2u) ks = 2u;                  // (a lane of chunk phase >= nc has nothing to do)
         c->P.n_samples = stop - base;
         c->P.sample_base = base;
         c->P.k_split = ks;
+        if (ks > ks_max) ks_max = ks;
         while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->evs.push_back(e); }
         hipEvent_t *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
-        const u32 bt = c->block_threads;
         c->P.persist_grid = (c->small_plain_grid && stop - base < kChunk) ? 0u : c->persist_grid;
-        const bool persist = bt > 64u && c->P.persist_grid != 0u;
-        if (persist) HIP_TRY(hipMemsetAsync(c->P.tile_counter, 0, sizeof(u32), c->stream));
-        if (c->event_timing) HIP_TRY(hipEventRecord(ev[0], c->stream));
-        HIP_TRY(launch_pt(c->P, bt, c->scene_in_lds, c->pk.features, c->stream));
-        c->stats.block_threads = bt;
-        c->stats.lds_bytes = (u32)pt_lds_bytes(c->P, bt, c->scene_in_lds, c->pk.features);
-        c->stats.kernel_features = pt_instantiation(bt, c->scene_in_lds, c->pk.features);
-        if (c->event_timing) HIP_TRY(hipEventRecord(ev[1], c->stream));
-        if (ks > 1u) HIP_TRY(launch_reduce_chunks(c->d_accum, c->d_partial, (size_t)c->local_rows * c->pk.nw * 3, plane, nc, c->stream));
-        if (c->event_timing) { HIP_TRY(hipEventRecord(ev[2], c->stream)); c->ev_used += 3u; }
+        if ((rc = launch_trace(c, c->P, c->stream, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, tl))) return rc;
+        if (ks > 1u) {
+            if (tl) HIP_TRY(launch_reduce_chunks_listed(c->d_accum, half, c->d_partial, tl->tiles, tl->n, c->pk.nw, c->pk.nh, plane, nc, c->stream));
+            else HIP_TRY(launch_reduce_chunks(c->d_accum, c->d_partial, (size_t)c->local_rows * c->pk.nw * 3, plane, nc, c->stream));
+        }
+        if (ev) { HIP_TRY(hipEventRecord(ev[2], c->stream)); c->ev_used += 3u; }
         c->stats.launches += 1u;
         base = stop;
     }
+    return MRT_OK;
+}
+
+// the statistics of one execute start over (an adaptive call's, and a look-ahead call's, as well)
+static void reset_exec_stats(mrt_ctx *c)
+{
+    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.launches = 0; c->stats.samples = 0; c->stats.segments = 0;
+    c->stats_pending = false; c->ev_used = 0;
+}
+
+// asynchronous half of mrt_execute on one device: everything up to the closing event
+static int exec_launch(mrt_ctx *c, uint32_t n_samples)
+{
+    int rc = set_device(c);
+    if (rc) return rc;
+    reset_exec_stats(c);
+    if (!(n_samples && c->local_rows)) return MRT_OK;
+    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
+    u32 ks_max = 0;                                  // (the uniform path reports the policy's k_split)
+    if ((rc = launch_batch(c, c->count, n_samples, nullptr, nullptr, false, c->stats.k_split, ks_max))) return rc;
+    c->stats.block_threads = c->block_threads;
+    c->stats.lds_bytes = (u32)pt_lds_bytes(c->P, c->block_threads, c->scene_in_lds, c->pk.features);
+    c->stats.kernel_features = pt_instantiation(c->block_threads, c->scene_in_lds, c->pk.features);
     return MRT_OK;
 }
 
@@ -707,7 +735,7 @@ static int exec_group(mrt_ctx *g, uint32_t n_samples)
     // kernels (before its part of the gather) and one after it; the slowest stream's interval plus scatter_rows is the
     // exchange.  A rank whose kernels finish early waits inside the collective for the slowest one, so the figure is an
     // upper bound of the transfer itself; kernel_ms (the slowest rank's kernels) is reported next to it.
-    const size_t plane = (size_t)g->subs[0]->padded_rows * g->pk.nw * 3;
+    const size_t plane = plane_floats(g->subs[0]);
     hipError_t he = hipSuccess;
     for (u32 r = 0; r < n && he == hipSuccess; ++r) {
         mrt_ctx *s = g->subs[r];
@@ -788,7 +816,7 @@ static void la_drop(mrt_ctx *c)
 // launch the trace of samples [base, base + n) into plane set i (asynchronous, on la_stream)
 static int la_launch(mrt_ctx *c, int i, u32 base, u32 n)
 {
-    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
+    const size_t plane = plane_floats(c);
     if (!c->la_stream) {
         HIP_TRY(hipStreamCreateWithFlags(&c->la_stream, hipStreamNonBlocking));
         for (int k = 0; k < 2; ++k) { HIP_TRY(hipEventCreate(&c->la_ev0[k])); HIP_TRY(hipEventCreate(&c->la_ev1[k])); }
@@ -807,10 +835,8 @@ static int la_launch(mrt_ctx *c, int i, u32 base, u32 n)
     // the launch has ended); larger ones leave slots free and keep their persistent workgroups, with a tile counter of their own
     P.persist_grid = c->small_plain_grid ? 0u : c->persist_grid;
     P.tile_counter = c->d_la_counter;
-    if (c->block_threads > 64u && P.persist_grid) HIP_TRY(hipMemsetAsync(c->d_la_counter, 0, sizeof(u32), c->la_stream));
-    HIP_TRY(hipEventRecord(c->la_ev0[i], c->la_stream));
-    HIP_TRY(launch_pt(P, c->block_threads, c->scene_in_lds, c->pk.features, c->la_stream));
-    HIP_TRY(hipEventRecord(c->la_ev1[i], c->la_stream));
+    const int rc = launch_trace(c, P, c->la_stream, c->la_ev0[i], c->la_ev1[i], nullptr);
+    if (rc) return rc;
     c->la_base[i] = base; c->la_n[i] = n;
     return MRT_OK;
 }
@@ -837,14 +863,13 @@ static int run_lookahead(mrt_ctx *c)
         if ((rc = la_launch(c, 1, k + n0, n1))) { (void)hipStreamSynchronize(c->la_stream); c->la_n[0] = c->la_n[1] = 0; return rc; }
         s = 0;
     }
-    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
+    const size_t plane = plane_floats(c);
     const size_t words = (size_t)c->local_rows * c->pk.nw * 3;
     HIP_TRY(hipStreamWaitEvent(c->stream, c->la_ev1[s], 0));
     HIP_TRY(launch_reduce_chunks(c->d_accum, c->d_la[s] + (size_t)(k - c->la_base[s]) * plane, words, plane, 1u, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                // the fold has run, so the set's launch has ended too
     c->count += 1u;
-    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.segments = 0;
-    c->stats_pending = false; c->ev_used = 0;
+    reset_exec_stats(c);
     c->stats.launches = 1u; c->stats.k_split = 1u;
     c->stats.samples = (uint64_t)c->local_rows * c->pk.nw;
     c->stats.block_threads = c->block_threads;
@@ -915,55 +940,10 @@ int mrt_execute(mrt_ctx *c, uint32_t n_samples, double *seconds)
 }
 
 // ---- adaptive sampling ---------------------------------------------------------------------------------------------------------
-// One round of an adaptive render: samples [base, base + n) of the n_listed tiles of `list`, launched like exec_launch's batches
-// (sample split sized from the listed tiles, chunk-aligned launches), asynchronous.  Even rounds go through the chunk planes
-// and reduce_chunks_listed adds their chunk sums, in chunk order, to the accumulator and to the half buffer alike.
-static int adapt_round(mrt_ctx *c, u32 base, u32 n, bool even, const u32 *list, u32 n_listed)
-{
-    const u32 n_chunks = (base + n - 1u) / kChunk - base / kChunk + 1u;
-    u32 k_split = 1, cap = kMaxChunksPerLaunch;
-    int rc = split_policy(c, n_listed, n_chunks, even, k_split, cap);
-    if (rc) return rc;
-    const size_t plane = (size_t)c->padded_rows * c->pk.nw * 3;
-    c->P.partial = c->d_partial;
-    c->P.partial_stride = plane;
-    const TileList tl{list, n_listed};
-    c->P.persist_grid = c->persist_grid;
-    const u32 bt = c->block_threads;
-    const u32 s_end = base + n;
-    while (base < s_end) {
-        u32 stop = s_end;
-        if (k_split > 1u) {
-            const unsigned long long lim = ((unsigned long long)(base / kChunk) + cap) * kChunk;
-            if (lim < stop) stop = (u32)lim;
-        }
-        const u32 nc = (stop - 1u) / kChunk - base / kChunk + 1u;
-        u32 ks = k_split;
-        while (ks > nc) ks /= 2u;
-        if (even && ks < 2u) ks = 2u;                    // (a lane of chunk phase >= nc has nothing to do)
-        c->P.n_samples = stop - base;
-        c->P.sample_base = base;
-        c->P.k_split = ks;
-        if (ks > c->stats.k_split) c->stats.k_split = ks;
-        while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->evs.push_back(e); }
-        hipEvent_t *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
-        if (bt > 64u && c->P.persist_grid) HIP_TRY(hipMemsetAsync(c->P.tile_counter, 0, sizeof(u32), c->stream));
-        if (c->event_timing) HIP_TRY(hipEventRecord(ev[0], c->stream));
-        HIP_TRY(launch_pt(c->P, bt, c->scene_in_lds, c->pk.features, c->stream, &tl));
-        if (c->event_timing) HIP_TRY(hipEventRecord(ev[1], c->stream));
-        if (ks > 1u)
-            HIP_TRY(launch_reduce_chunks_listed(c->d_accum, even ? c->d_half : nullptr, c->d_partial, list, n_listed, c->pk.nw, c->pk.nh, plane, nc, c->stream));
-        if (c->event_timing) { HIP_TRY(hipEventRecord(ev[2], c->stream)); c->ev_used += 3u; }
-        c->stats.launches += 1u;
-        base = stop;
-    }
-    return MRT_OK;
-}
-
 static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
 {
     const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u, n_ty = (nh + 7u) / 8u, n_tiles = n_tx * n_ty;
-    const size_t acc_floats = (size_t)c->padded_rows * nw * 3;
+    const size_t acc_floats = plane_floats(c);
     if (!c->d_half) HIP_TRY(hipMalloc((void **)&c->d_half, acc_floats * sizeof(float)));
     if (!c->d_adapt) HIP_TRY(hipMalloc((void **)&c->d_adapt, (5u * (size_t)n_tiles + 1u) * sizeof(u32)));
     u32 *lists[2] = {c->d_adapt, c->d_adapt + n_tiles};
@@ -979,7 +959,12 @@ static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
     u32 n_active = n_tiles, n = 0, rounds = 0, cur = 0;
     while (n_active) {
         for (int r = 0; r < 2; ++r, ++rounds, n += a->step) {
-            const int rc = adapt_round(c, n, a->step, (rounds & 1u) == 0u, lists[cur], n_active);
+            // one round over the tiles still running; even rounds go through the chunk planes, whose sums are added, in chunk
+            // order, to the accumulator and to the half buffer alike.  The adaptive path reports the largest split as k_split.
+            const bool even = (rounds & 1u) == 0u;
+            const TileList tl{lists[cur], n_active};
+            u32 k_split = 1;
+            const int rc = launch_batch(c, n, a->step, &tl, even ? c->d_half : nullptr, even, k_split, c->stats.k_split);
             if (rc) return rc;
         }
         if (n < a->min_samples) continue;
@@ -1040,14 +1025,13 @@ int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, d
     int rc = set_device(c);
     if (rc) return rc;
     la_drop(c);
-    c->stats.kernel_ms = 0; c->stats.reduce_ms = 0; c->stats.gather_ms = 0; c->stats.launches = 0; c->stats.samples = 0; c->stats.segments = 0;
+    reset_exec_stats(c);
     c->stats.k_split = 1; c->stats.deferred = 0;
-    c->stats_pending = false; c->ev_used = 0;
     if ((rc = adapt_run(c, a, info))) {
         // nothing half done stays behind: the context is an empty uniform one again
         const std::string keep = g_err;
         (void)hipStreamSynchronize(c->stream);
-        (void)hipMemset(c->d_accum, 0, (size_t)c->padded_rows * c->pk.nw * 3 * sizeof(float));
+        (void)hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float));
         (void)hipGetLastError();
         c->adaptive = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
         g_err = keep; g_status = rc;
@@ -1140,7 +1124,7 @@ int mrt_accum_device_ptr(mrt_ctx *c, void **dev_ptr, size_t *bytes)
     { int rc = set_device(c); if (rc) return rc; if ((rc = settle(c))) return rc; }
     c->handed_out = true;                     // from now on the caller may read the accumulator behind the library's back (sticky)
     if (dev_ptr) *dev_ptr = c->subs.empty() ? c->d_accum : c->d_full;
-    if (bytes) *bytes = (size_t)c->padded_rows * c->pk.nw * 3 * sizeof(float);
+    if (bytes) *bytes = plane_floats(c) * sizeof(float);
     ok();
     return MRT_OK;
 }
@@ -1160,7 +1144,7 @@ int mrt_bind_accum(mrt_ctx *c, void *dev_ptr, size_t bytes)
     int rc = set_device(c);
     if (rc) return rc;
     if ((rc = settle(c))) return rc;
-    const size_t need = (size_t)c->padded_rows * c->pk.nw * 3 * sizeof(float);
+    const size_t need = plane_floats(c) * sizeof(float);
     float *dst = dev_ptr ? (float *)dev_ptr : c->d_accum_own;
     if (dev_ptr && bytes < need) return fail(MRT_ERR_ARG, "mrt_bind_accum: buffer of %zu bytes, need %zu", bytes, need);     // nothing changed
     if (dst != c->d_accum) {
@@ -1242,7 +1226,7 @@ int mrt_reset(mrt_ctx *c)
         ok();
         return MRT_OK;
     }
-    HIP_TRY(hipMemset(c->d_accum, 0, (size_t)c->padded_rows * c->pk.nw * 3 * sizeof(float)));
+    HIP_TRY(hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float)));
     if (c->d_full) { (void)hipFree(c->d_full); c->d_full = nullptr; }
     c->count = 0; c->full_count = 0;
     ok();
@@ -1313,6 +1297,17 @@ static int img_tonemap(mrt_ctx *c)
     return MRT_OK;
 }
 
+// the end of mrt_img / mrt_img_ss: close the timing of the image kernels, wait for them and copy `bytes` of `src` out
+static int img_read_back(mrt_ctx *c, uint8_t *rgb8, const unsigned char *src, size_t bytes)
+{
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); c->stats.img_ms = ms; }
+    HIP_TRY(hipMemcpy(rgb8, src, bytes, hipMemcpyDeviceToHost));
+    ok();
+    return MRT_OK;
+}
+
 int mrt_img_ss(mrt_ctx *c, uint8_t *rgb8)
 {
     if (!c || !rgb8) return fail(MRT_ERR_ARG, "mrt_img_ss: null argument");
@@ -1321,12 +1316,7 @@ int mrt_img_ss(mrt_ctx *c, uint8_t *rgb8)
     if ((rc = settle(c))) return rc;
     if ((rc = img_prepare(c))) return rc;
     if ((rc = img_tonemap(c))) return rc;
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); c->stats.img_ms = ms; }
-    HIP_TRY(hipMemcpy(rgb8, c->d_ss, (size_t)c->pk.nw * c->pk.nh * 3, hipMemcpyDeviceToHost));
-    ok();
-    return MRT_OK;
+    return img_read_back(c, rgb8, c->d_ss, (size_t)c->pk.nw * c->pk.nh * 3);
 }
 
 int mrt_img(mrt_ctx *c, uint8_t *rgb8)
@@ -1338,22 +1328,10 @@ int mrt_img(mrt_ctx *c, uint8_t *rgb8)
     if ((rc = img_prepare(c))) return rc;
     if ((rc = img_tonemap(c))) return rc;
     const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
-    if (rw == nw && rh == nh) {    // image 0.24 resize copies when the dimensions match
-        HIP_TRY(hipEventRecord(c->ev1, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); c->stats.img_ms = ms; }
-        HIP_TRY(hipMemcpy(rgb8, c->d_ss, (size_t)nw * nh * 3, hipMemcpyDeviceToHost));
-        ok();
-        return MRT_OK;
-    }
+    if (rw == nw && rh == nh) return img_read_back(c, rgb8, c->d_ss, (size_t)nw * nh * 3);      // image 0.24 resize copies when the dimensions match
     HIP_TRY(launch_lanczos_v(c->d_ss, c->d_tmp, nw, rh, c->d_vl, c->d_vc, c->d_vw, c->vcap, c->stream));
     HIP_TRY(launch_lanczos_h(c->d_tmp, c->d_out, nw, rw, rh, c->d_hl, c->d_hc, c->d_hw, c->hcap, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); c->stats.img_ms = ms; }
-    HIP_TRY(hipMemcpy(rgb8, c->d_out, (size_t)rw * rh * 3, hipMemcpyDeviceToHost));
-    ok();
-    return MRT_OK;
+    return img_read_back(c, rgb8, c->d_out, (size_t)rw * rh * 3);
 }
 
 int mrt_get_stats(mrt_ctx *c, mrt_stats *out)

@@ -155,12 +155,6 @@ __global__ void __launch_bounds__(256) math_sweep(int op, unsigned long long fir
 }
 
 // ---- launchers (declared in mrt_kernels.h); the instantiations: mrt_megakernel.h ----
-template <int THREADS, u32 FEAT>
-static void launch_lds(dim3 grid, size_t lds, hipStream_t stream, const Params &P)
-{
-    hipLaunchKernelGGL((pt_megakernel<true, THREADS, FEAT>), grid, dim3(THREADS), lds, stream, P, P.blob);
-}
-
 size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 features)
 {
     const u32 inst = pt_instantiation(block_threads, scene_in_lds, features);      // what the kernel itself sees as FEAT
@@ -200,8 +194,6 @@ u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features)
     return big | nostash;
 }
 
-#define MRT_CASE(T, F) case (F): launch_lds<T, (F)>(grid, lds, stream, P); return hipGetLastError();
-#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((pt_megakernel<false, 256, (F)>), grid, dim3(256), lds, stream, P, P.blob); return hipGetLastError();
 hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream, const TileList *TL)
 {
     if (block_threads != P.tiles_x * P.tiles_y * 64u) return hipErrorInvalidConfiguration;
@@ -219,37 +211,13 @@ hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 
     const size_t lds = pt_lds_bytes(P, block_threads, scene_in_lds, features);
     const u32 inst = pt_instantiation(block_threads, scene_in_lds, features);
     if (TL) return launch_pt_list(P, *TL, grid, lds, block_threads, scene_in_lds, inst, stream);
-    if (!scene_in_lds) {
-        if (block_threads != 256u) return hipErrorInvalidConfiguration;
-        switch (inst) { MRT_SHAPES_L2 default: break; }
-    } else if (block_threads == 64u) {
-        switch (inst) { MRT_SHAPES_64 default: break; }
-    } else if (block_threads == 256u) {
-        switch (inst) { MRT_SHAPES_256 default: break; }
-    } else if (block_threads == 512u) {
-        switch (inst) { MRT_SHAPES_512 default: break; }
-    } else if (block_threads == 1024u) {
-        switch (inst) { MRT_SHAPES_1024 default: break; }
-    }
-    return hipErrorInvalidConfiguration;
-}
-#undef MRT_CASE
-#undef MRT_CASE_L2
-
-template <int THREADS, u32 FEAT>
-static hipError_t set_lds_attr(int bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&pt_megakernel<true, THREADS, FEAT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return launch_pt_inst(P, nullptr, grid, lds, block_threads, scene_in_lds, inst, stream);
 }
 
 hipError_t configure_pt(size_t max_lds_bytes)
 {
-    const int b = (int)max_lds_bytes;
-    hipError_t e;
-#define MRT_CASE(T, F) if ((e = set_lds_attr<T, (F)>(b)) != hipSuccess) return e;
-    MRT_SHAPES_64 MRT_SHAPES_256 MRT_SHAPES_512 MRT_SHAPES_1024
-#undef MRT_CASE
-    return configure_pt_list(max_lds_bytes);
+    const hipError_t e = configure_pt_inst(max_lds_bytes);
+    return e != hipSuccess ? e : configure_pt_list(max_lds_bytes);
 }
 
 hipError_t launch_reduce_chunks(float *accum, const float *partial, size_t n_words, size_t stride, u32 n_chunks, hipStream_t stream)

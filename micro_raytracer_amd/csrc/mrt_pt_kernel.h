@@ -2,7 +2,9 @@
 // pt_megakernel, the ordinary launches, and by mrt_adapt.hip with MRT_PT_LIST 1 as pt_megakernel_list, the tile-list
 // launches of adaptive sampling (argument TL).  Two translation units and the preprocessor, not a shared function: the
 // ordinary kernel is then exactly the text it was, and the compiler's decisions for it (registers, spills) do not move.
-// Needs mrt_megakernel.h (lds_stash_for, waves_for) and mrt_trace.h; expands inside namespace mrt.
+// The host side of each kernel -- the launch of one instantiation and the LDS attribute of all of them -- comes from the end
+// of this file as well.  Needs mrt_megakernel.h (lds_stash_for, waves_for, the instantiation lists) and mrt_trace.h; expands
+// inside namespace mrt.
 #ifndef MRT_PT_LIST
 #error "define MRT_PT_LIST (0: pt_megakernel, 1: pt_megakernel_list) before including mrt_pt_kernel.h"
 #endif
@@ -136,3 +138,49 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
         if (lane == 0 && v) atomicAdd(P.segments, (unsigned long long)v);
     }
 }
+
+// ---- host side of this kernel (static in each translation unit; the exported launchers are in mrt_kernels.hip / mrt_adapt.hip)
+#if MRT_PT_LIST
+#define MRT_PT_KERNEL pt_megakernel_list
+#define MRT_PT_ARGS P, P.blob, *TL
+#else
+#define MRT_PT_KERNEL pt_megakernel
+#define MRT_PT_ARGS P, P.blob
+#endif
+// Launch instantiation `inst` (pt_instantiation) of a launch shape, grid and LDS bytes as launch_pt computed them; TL: the tile
+// list of pt_megakernel_list (unused by pt_megakernel).  A shape without that instantiation is an invalid configuration.
+static hipError_t launch_pt_inst(const Params &P, const TileList *TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst,
+                                 hipStream_t stream)
+{
+#define MRT_CASE(T, F) case (F): hipLaunchKernelGGL((MRT_PT_KERNEL<true, T, (F)>), grid, dim3(T), lds, stream, MRT_PT_ARGS); return hipGetLastError();
+#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((MRT_PT_KERNEL<false, 256, (F)>), grid, dim3(256), lds, stream, MRT_PT_ARGS); return hipGetLastError();
+    if (!scene_in_lds) {
+        if (block_threads != 256u) return hipErrorInvalidConfiguration;
+        switch (inst) { MRT_SHAPES_L2 default: break; }
+    } else if (block_threads == 64u) {
+        switch (inst) { MRT_SHAPES_64 default: break; }
+    } else if (block_threads == 256u) {
+        switch (inst) { MRT_SHAPES_256 default: break; }
+    } else if (block_threads == 512u) {
+        switch (inst) { MRT_SHAPES_512 default: break; }
+    } else if (block_threads == 1024u) {
+        switch (inst) { MRT_SHAPES_1024 default: break; }
+    }
+#undef MRT_CASE
+#undef MRT_CASE_L2
+    return hipErrorInvalidConfiguration;
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for every scene-in-LDS instantiation of this kernel
+static hipError_t configure_pt_inst(size_t max_lds_bytes)
+{
+    const int b = (int)max_lds_bytes;
+    hipError_t e;
+#define MRT_CASE(T, F) \
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(&MRT_PT_KERNEL<true, T, (F)>), hipFuncAttributeMaxDynamicSharedMemorySize, b)) != hipSuccess) return e;
+    MRT_SHAPES_64 MRT_SHAPES_256 MRT_SHAPES_512 MRT_SHAPES_1024
+#undef MRT_CASE
+    return hipSuccess;
+}
+#undef MRT_PT_KERNEL
+#undef MRT_PT_ARGS

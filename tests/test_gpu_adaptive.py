@@ -155,6 +155,24 @@ SHAPES = [{"MRT_BLOCK_THREADS": "64"}, {"MRT_BLOCK_THREADS": "256"}, {"MRT_BLOCK
           {"MRT_SCENE_IN_L2": "1"}, {"MRT_K_SPLIT": "1"}, {"MRT_K_SPLIT": "4"}, {"MRT_MAX_CHUNKS": "1"}, "defer"]
 
 
+@pytest.mark.parametrize("step,k_split", [(16, 2), (48, 2), (96, 4)])
+def test_adaptive_rounds_are_cut_into_bounded_launches(step, k_split, monkeypatch):
+    """Each round is cut at chunk boundaries into launches of at most MRT_MAX_CHUNKS chunks; MRT_K_SPLIT lanes per pixel are
+    halved to the round's chunk count (even rounds keep 2: their chunk sums go to H as well), and the reported k_split is
+    the largest of any launch.  A threshold of inf with min = max pins the round count."""
+    render, _ = _scene("partial100x60")
+    monkeypatch.setenv("MRT_K_SPLIT", "4")
+    monkeypatch.setenv("MRT_MAX_CHUNKS", "4")
+    n = 4 * step
+    r = _adaptive(render, float("inf"), max_samples=n, step=step, min_samples=n)
+    info, st = r["info"], r["s"].stats()
+    per_round = -(-(step // 16) // 4)
+    assert (r["counts"] == n).all() and info["rounds"] == n // step == 4
+    assert info["launches"] == st["launches"] == info["rounds"] * per_round, (info, st)
+    assert st["k_split"] == k_split, st
+    r["s"].close()
+
+
 @pytest.mark.parametrize("name,step", [("partial100x60", 16), ("partial100x60", 32), ("mesh", 16)])
 def test_adaptive_independent_of_launch_shape(name, step, monkeypatch):
     from micro_raytracer_amd import _abi
