@@ -305,6 +305,42 @@ int mrt_sample_counts(mrt_ctx *ctx, uint32_t *counts);
  * (count/2 of them).  MRT_ERR_STATE on a context that has run no adaptive call since its last reset. */
 int mrt_adapt_half(mrt_ctx *ctx, float *rgb);
 
+/* ---- first-hit AOVs and the a-trous denoiser ---------------------------------------------------------------
+ * AOVs: one camera ray per supersampled pixel through the lens centre, its closest hit.  Computed once per context on first
+ * use and kept on the device (mrt_reset keeps them: they depend on scene and camera only).  Any output may be NULL:
+ *   depth[nh][nw]        distance along the unit ray (+inf: miss)
+ *   normal[nh][nw][3]    world-space normal as the path tracer uses it (0: miss)
+ *   albedo[nh][nw][3]    material albedo x texture at the hit (0: miss)
+ *   renderer[nh][nw]     index into mrt_scene.renderer (-1: miss)
+ *   instance[nh][nw]     index into that renderer's inst list (-1: miss)
+ * Sharded and multi-device contexts return the whole frame too.  Not an observation: booked samples stay booked. */
+int mrt_aov(mrt_ctx *ctx, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance);
+
+/* Edge-avoiding a-trous filter (Dammertz et al. 2010) on the mean radiance, guided by the AOVs.  passes 0..8 (0: the means
+ * unchanged); sigmas > 0 or +inf (+inf switches that term off); NaN or <= 0: MRT_ERR_ARG.  NULL options = the defaults. */
+#define MRT_DENOISE_PASSES 5u
+#define MRT_DENOISE_SIGMA_COLOR 0.5f
+#define MRT_DENOISE_SIGMA_NORMAL 0.25f
+#define MRT_DENOISE_SIGMA_PLANE 0.05f
+typedef struct mrt_denoise_opts {
+    uint32_t passes;
+    float sigma_color, sigma_normal, sigma_plane;
+    uint32_t reserved[4];
+} mrt_denoise_opts;
+typedef struct mrt_denoise_info {
+    double aov_ms, filter_ms;      /* HIP-event times of this call's AOV pass (0: the AOVs were cached) and of the filter */
+    uint32_t passes, aov_cached;
+    uint32_t reserved[2];
+} mrt_denoise_info;
+
+/* The filtered means rgb[nh][nw][3].  An observation like mrt_img: booked samples are traced first; needs the whole frame
+ * (unsharded, or after mrt_set_accum*) and at least one sample, else MRT_ERR_STATE; after mrt_execute_adaptive each pixel's
+ * mean uses its tile's count.  info may be NULL. */
+int mrt_denoise(mrt_ctx *ctx, const mrt_denoise_opts *o, float *rgb, mrt_denoise_info *info);
+
+/* mrt_img of the filtered means: rgb8[res_h][res_w][3] (passes = 0: the bytes of mrt_img). */
+int mrt_img_denoised(mrt_ctx *ctx, const mrt_denoise_opts *o, uint8_t *rgb8, mrt_denoise_info *info);
+
 /* Test hook, host only (no device needed): what mrt_create would stage in LDS for this scene and the workgroup shape of its
  * launches -- the policy of csrc/mrt_api.cpp as data, so that it can be checked where no GPU exists. */
 typedef struct mrt_plan {

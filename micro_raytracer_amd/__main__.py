@@ -2,16 +2,44 @@
 
     python -m micro_raytracer_amd scene.json -o out.png [--sample N] [--bounce N] [--seed S] [--update]
                                   [--adaptive THRESHOLD [--min-sample N] [--step N]]
+                                  [--denoise [--denoise-passes N]] [--aov PREFIX]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
 --adaptive renders with a per-tile noise threshold instead (Sampler.execute_adaptive), --sample being the cap.
+--denoise saves the image of the AOV-guided a-trous filter (Sampler.img_denoised) instead of the raw means; --aov writes the
+first-hit normal, albedo and depth as PREFIX.normal.png, PREFIX.albedo.png and PREFIX.depth.png.
 """
 import argparse
 import sys
 import time
 
-from . import _lib, load_render
+import numpy as np
+
+from . import _abi, _lib, load_render
 from .sampler import Sampler
+
+
+def image(s, a):
+    return s.img_denoised(passes=a.denoise_passes) if a.denoise else s.img()
+
+
+def aov_images(aov):
+    """The first-hit AOVs as 8-bit images: normal * 0.5 + 0.5, albedo, depth normalised over its finite values."""
+    def u8(x):
+        return (np.clip(np.nan_to_num(x, nan=0.0), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    d = aov["depth"].astype(np.float64)
+    fin = np.isfinite(d)
+    dn = np.zeros_like(d)
+    if fin.any():
+        lo, hi = d[fin].min(), d[fin].max()
+        dn[fin] = (d[fin] - lo) / (hi - lo) if hi > lo else 0.0
+    return {"normal": u8(aov["normal"] * 0.5 + 0.5), "albedo": u8(aov["albedo"]),
+            "depth": np.ascontiguousarray(np.repeat(u8(dn)[..., None], 3, axis=2))}
+
+
+def save_aov(s, prefix):
+    for name, img in aov_images(s.aov()).items():
+        _lib.save_image(f"{prefix}.{name}.png", np.ascontiguousarray(img))
 
 
 def main(argv=None):
@@ -26,7 +54,13 @@ def main(argv=None):
                     help="tile-adaptive sampling: 8x8 tiles stop once their noise estimate is <= THRESHOLD (--sample is the cap)")
     ap.add_argument("--min-sample", type=int, default=32, help="--adaptive: samples every tile takes (default 32)")
     ap.add_argument("--step", type=int, default=16, help="--adaptive: samples per round, a multiple of 16 (default 16)")
+    ap.add_argument("--denoise", action="store_true", help="save the denoised image (AOV-guided a-trous filter)")
+    ap.add_argument("--denoise-passes", type=int, default=_abi.DENOISE_PASSES,
+                    help=f"--denoise: filter passes, 0..8 (default {_abi.DENOISE_PASSES})")
+    ap.add_argument("--aov", metavar="PREFIX", help="also write PREFIX.normal.png, PREFIX.albedo.png and PREFIX.depth.png")
     a = ap.parse_args(argv)
+    if not 0 <= a.denoise_passes <= 8:
+        ap.error(f"--denoise-passes {a.denoise_passes} is not in 0..8")
     if a.adaptive is not None:
         if a.update:
             ap.error("--update cannot be combined with --adaptive")
@@ -49,10 +83,12 @@ def main(argv=None):
     elif a.update:
         for _ in range(render.rt.sample):
             s.execute(render)
-            _lib.save_image(a.output, s.img())
+            _lib.save_image(a.output, image(s, a))
     else:
         s.execute(render, n_samples=render.rt.sample)
-    _lib.save_image(a.output, s.img())
+    _lib.save_image(a.output, image(s, a))
+    if a.aov:
+        save_aov(s, a.aov)
     st = s.stats()
     print(f"done: {s.nw}x{s.nh} x {render.rt.sample} spp in {time.perf_counter() - t0:.3f} s -> {a.output} "
           f"({st['block_threads']}-thread workgroups, {st['lds_bytes']} B LDS)", file=sys.stderr)

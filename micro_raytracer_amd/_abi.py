@@ -96,6 +96,30 @@ class AdaptInfo(C.Structure):
                 ("tiles_converged", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
+class DenoiseOpts(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class DenoiseInfo(C.Structure):
+    _fields_ = [("aov_ms", C.c_double), ("filter_ms", C.c_double), ("passes", C.c_uint32), ("aov_cached", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+# defaults of mrt_denoise_opts (include/mrt.h MRT_DENOISE_*)
+DENOISE_PASSES, DENOISE_SIGMA_COLOR, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_PLANE = 5, 0.5, 0.25, 0.05
+
+
+def denoise_opts(passes=DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None) -> DenoiseOpts:
+    """mrt_denoise_opts; a sigma of None takes its default, float("inf") switches that term off."""
+    o = DenoiseOpts()
+    o.passes = int(passes)
+    o.sigma_color = DENOISE_SIGMA_COLOR if sigma_color is None else float(sigma_color)
+    o.sigma_normal = DENOISE_SIGMA_NORMAL if sigma_normal is None else float(sigma_normal)
+    o.sigma_plane = DENOISE_SIGMA_PLANE if sigma_plane is None else float(sigma_plane)
+    return o
+
+
 STAGING = ("all", "warm", "deep", "none")
 MAP_SLOTS = ("tex", "rmap", "mmap", "gmap", "omap", "emap")
 

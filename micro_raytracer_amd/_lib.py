@@ -16,6 +16,7 @@ SYMBOLS = (
     "mrt_abi_version", "mrt_device_count", "mrt_selftest_math", "mrt_padded_rows", "mrt_bind_accum",
     "mrt_set_accum_device", "mrt_save_image", "mrt_selftest_sweep", "mrt_plan_launch",
     "mrt_execute_adaptive", "mrt_sample_counts", "mrt_adapt_half",
+    "mrt_aov", "mrt_denoise", "mrt_img_denoised",
 )
 
 
@@ -55,6 +56,9 @@ def lib():
     L.mrt_execute_adaptive.argtypes = [vp, C.POINTER(_abi.Adapt), C.POINTER(_abi.AdaptInfo), C.POINTER(C.c_double)]
     L.mrt_sample_counts.argtypes = [vp, u32p]
     L.mrt_adapt_half.argtypes = [vp, f32p]
+    L.mrt_aov.argtypes = [vp, f32p, f32p, f32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.mrt_denoise.argtypes = [vp, C.POINTER(_abi.DenoiseOpts), f32p, C.POINTER(_abi.DenoiseInfo)]
+    L.mrt_img_denoised.argtypes = [vp, C.POINTER(_abi.DenoiseOpts), u8p, C.POINTER(_abi.DenoiseInfo)]
     L.mrt_dims.argtypes = [vp, u32p, u32p, u32p]
     L.mrt_accum.argtypes = [vp, f32p, u32p]
     L.mrt_accum_local.argtypes = [vp, f32p, u32p]

@@ -10,11 +10,13 @@
 #include <string.h>
 
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/mrt.h"
+#include "mrt_denoise.h"
 #include "mrt_kernels.h"
 #include "mrt_pack.h"
 #include "mrt_trace.h"
@@ -194,6 +196,18 @@ struct mrt_ctx {
     float *d_half = nullptr;             // H: [padded_rows][nw][3], per pixel the sum of its even-numbered rounds
     u32 *d_adapt = nullptr;              // [n_tiles] x 5 + 1: two tile lists, keep flags, per-tile count, per-tile converged flag, list length
     std::vector<u32> tile_count;         // per-tile counts of the last adaptive call (host copy)
+    // first-hit AOVs and the denoiser (mrt_aov, mrt_denoise: DESIGN.md §13), on `device`, allocated by the first call; the AOVs
+    // depend on scene and camera only and survive mrt_reset
+    std::unique_ptr<Packed> aov_pk;      // deep-staged contexts: the scene as packed without them (binary triangle BVHs) for the AOV kernel
+    u32 *d_aov_blob = nullptr;           // the scene the AOV kernel reads when d_blob is not it (deep staging, multi-device contexts)
+    unsigned long long *d_aov_seg = nullptr;   // its diagnostic counters (mrt_trace.h count_fallback)
+    float *d_guide = nullptr;            // [2][nh][nw] float4: (normal, depth), (world point, hit flag)
+    float *d_albedo = nullptr;           // [nh][nw][3]
+    i32 *d_ids = nullptr;                // [nh][nw][2]: renderer, flat instance index
+    bool aov_ready = false;
+    std::vector<u32> inst_first;         // flat index of each renderer's first instance (ids -> mrt_scene order)
+    float *d_dn = nullptr;               // two e planes ([nh][nw] float4) and the filtered means [nh][nw][3]
+    hipEvent_t dn_ev[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -218,13 +232,15 @@ void free_ctx(mrt_ctx *c)
     if (c->la_stream) { (void)hipStreamSynchronize(c->la_stream); (void)hipStreamDestroy(c->la_stream); }
     for (int i = 0; i < 2; ++i) { if (c->la_ev0[i]) (void)hipEventDestroy(c->la_ev0[i]); if (c->la_ev1[i]) (void)hipEventDestroy(c->la_ev1[i]); }
     void *ptrs[] = {c->d_blob, c->d_accum_own, c->d_partial, c->d_segments, c->d_full, c->d_ss, c->d_out, c->d_tmp, c->d_vl, c->d_vc, c->d_hl, c->d_hc, c->d_vw, c->d_hw,
-                    c->d_la[0], c->d_la[1], c->d_la_counter, c->d_half, c->d_adapt};
+                    c->d_la[0], c->d_la[1], c->d_la_counter, c->d_half, c->d_adapt, c->d_aov_blob, c->d_aov_seg, c->d_guide, c->d_albedo, c->d_ids,
+                    c->d_dn};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_g0) (void)hipEventDestroy(c->ev_g0);
     if (c->ev_g1) (void)hipEventDestroy(c->ev_g1);
     for (hipEvent_t e : c->evs) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -392,6 +408,10 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); delete c; return nullptr; }
     Plan plan;
     plan_launch(desc, c->pk, plan);          // may re-pack the scene (deep staging: 4-wide triangle BVHs), before anything is uploaded
+    if (c->pk.tbvh_wide) {                   // the AOV kernel (scene through L2, no F_DEEP build) walks the binary triangle BVHs
+        c->aov_pk.reset(new Packed());
+        if (pack_scene(desc, *c->aov_pk, err) != MRT_OK) { fail(MRT_ERR_SCENE, "mrt_create: %s", err.c_str()); delete c; return nullptr; }
+    }
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -1329,6 +1349,163 @@ int mrt_img(mrt_ctx *c, uint8_t *rgb8)
     if ((rc = img_tonemap(c))) return rc;
     const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
     if (rw == nw && rh == nh) return img_read_back(c, rgb8, c->d_ss, (size_t)nw * nh * 3);      // image 0.24 resize copies when the dimensions match
+    HIP_TRY(launch_lanczos_v(c->d_ss, c->d_tmp, nw, rh, c->d_vl, c->d_vc, c->d_vw, c->vcap, c->stream));
+    HIP_TRY(launch_lanczos_h(c->d_tmp, c->d_out, nw, rw, rh, c->d_hl, c->d_hc, c->d_hw, c->hcap, c->stream));
+    return img_read_back(c, rgb8, c->d_out, (size_t)rw * rh * 3);
+}
+
+// ---- first-hit AOVs and the a-trous denoiser -------------------------------------------------------------------
+// The AOV buffers of this context, computed on first use: *ms = HIP-event time of the pass (0 when they were there already)
+static int aov_compute(mrt_ctx *c, bool &cached, double &ms)
+{
+    cached = c->aov_ready;
+    ms = 0.0;
+    if (c->aov_ready) return MRT_OK;
+    const Packed &ap = c->aov_pk ? *c->aov_pk : c->pk;
+    const size_t np = (size_t)ap.nw * ap.nh;
+    if (!c->d_guide) HIP_TRY(hipMalloc((void **)&c->d_guide, np * 8u * sizeof(float)));
+    if (!c->d_albedo) HIP_TRY(hipMalloc((void **)&c->d_albedo, np * 3u * sizeof(float)));
+    if (!c->d_ids) HIP_TRY(hipMalloc((void **)&c->d_ids, np * 2u * sizeof(i32)));
+    if (!c->d_aov_seg) {
+        HIP_TRY(hipMalloc((void **)&c->d_aov_seg, 8u * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(c->d_aov_seg, 0, 8u * sizeof(unsigned long long)));
+    }
+    const u32 *blob = c->d_blob;
+    if (c->aov_pk || !blob) {                 // deep staging, or a multi-device context (its scene lives on the sub-contexts)
+        if (!c->d_aov_blob) {
+            const size_t bytes = ap.blob.size() * 4u;
+            HIP_TRY(hipMalloc((void **)&c->d_aov_blob, bytes ? bytes : 16u));
+            HIP_TRY(hipMemcpy(c->d_aov_blob, ap.blob.data(), bytes, hipMemcpyHostToDevice));
+        }
+        blob = c->d_aov_blob;
+    }
+    for (hipEvent_t &e : c->dn_ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    Params P = ap.P;
+    P.blob = blob;
+    P.segments = c->d_aov_seg;
+    HIP_TRY(hipEventRecord(c->dn_ev[0], c->stream));
+    HIP_TRY(launch_aov(P, ap.features, c->d_guide, c->d_albedo, c->d_ids, c->stream));
+    HIP_TRY(hipEventRecord(c->dn_ev[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float t = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&t, c->dn_ev[0], c->dn_ev[1]));
+    ms = t;
+    // instances are flattened renderer by renderer in description order (mrt_pack.cpp): the first flat index of each renderer
+    c->inst_first.assign(ap.P.n_rend, 0u);
+    for (u32 i = ap.P.n_inst; i-- > 0;) c->inst_first[ap.blob[ap.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    c->aov_ready = true;
+    return MRT_OK;
+}
+
+int mrt_aov(mrt_ctx *c, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance)
+{
+    if (!c) return fail(MRT_ERR_ARG, "mrt_aov: null context");
+    int rc = set_device(c);
+    if (rc) return rc;
+    bool cached;
+    double ms;
+    if ((rc = aov_compute(c, cached, ms))) return rc;
+    const size_t np = (size_t)c->pk.nw * c->pk.nh;
+    if (depth || normal) {
+        std::vector<float> g(np * 4u);
+        HIP_TRY(hipMemcpy(g.data(), c->d_guide, np * 4u * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < np; ++p) {
+            if (depth) depth[p] = g[4 * p + 3];
+            if (normal) for (int k = 0; k < 3; ++k) normal[3 * p + k] = g[4 * p + k];
+        }
+    }
+    if (albedo) HIP_TRY(hipMemcpy(albedo, c->d_albedo, np * 3u * sizeof(float), hipMemcpyDeviceToHost));
+    if (renderer || instance) {
+        std::vector<i32> ids(np * 2u);
+        HIP_TRY(hipMemcpy(ids.data(), c->d_ids, np * 2u * sizeof(i32), hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < np; ++p) {
+            const i32 r = ids[2 * p];
+            if (renderer) renderer[p] = r;
+            if (instance) instance[p] = r < 0 ? -1 : ids[2 * p + 1] - (i32)c->inst_first[(u32)r];
+        }
+    }
+    ok();
+    return MRT_OK;
+}
+
+// Filter options -> passes and the three 1/sigma^2, formed in f32 (sigma = +inf: 0, the term is off)
+static int denoise_opts(const mrt_denoise_opts *o, const char *fn, u32 &passes, float &sc, float &sn, float &sp)
+{
+    mrt_denoise_opts d;
+    memset(&d, 0, sizeof d);
+    d.passes = MRT_DENOISE_PASSES;
+    d.sigma_color = MRT_DENOISE_SIGMA_COLOR; d.sigma_normal = MRT_DENOISE_SIGMA_NORMAL; d.sigma_plane = MRT_DENOISE_SIGMA_PLANE;
+    if (!o) o = &d;
+    if (o->passes > kDnMaxPasses) return fail(MRT_ERR_ARG, "%s: passes %u > %u", fn, o->passes, kDnMaxPasses);
+    const float sg[3] = {o->sigma_color, o->sigma_normal, o->sigma_plane};
+    for (float s : sg) if (!(s > 0.0f)) return fail(MRT_ERR_ARG, "%s: sigma %g is not > 0", fn, (double)s);
+    passes = o->passes;
+    sc = 1.0f / (sg[0] * sg[0]);
+    sn = 1.0f / (sg[1] * sg[1]);
+    sp = 1.0f / (sg[2] * sg[2]);
+    return MRT_OK;
+}
+
+// The filtered means of the accumulator into the context's output plane (*out, on the device); an observation like mrt_img
+static int denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *info, const char *fn, const float **out)
+{
+    u32 passes;
+    float sc, sn, sp;
+    int rc = denoise_opts(o, fn, passes, sc, sn, sp);
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = settle(c))) return rc;
+    const float *src = c->d_full ? c->d_full : c->d_accum;
+    const u32 count = c->d_full ? c->full_count : c->count;
+    if (!c->d_full && c->shard_count != 1) return fail(MRT_ERR_STATE, "%s: this context holds only its own rows; gather and mrt_set_accum first", fn);
+    if (count == 0) return fail(MRT_ERR_STATE, "%s: no samples accumulated", fn);
+    bool cached;
+    double aov_ms;
+    if ((rc = aov_compute(c, cached, aov_ms))) return rc;
+    const u32 nw = c->pk.nw, nh = c->pk.nh;
+    const size_t np = (size_t)nw * nh;
+    if (!c->d_dn) HIP_TRY(hipMalloc((void **)&c->d_dn, np * 11u * sizeof(float)));
+    float *e0 = c->d_dn, *e1 = e0 + 4u * np, *dst = e1 + 4u * np;
+    const u32 n_tiles = ((nw + 7u) / 8u) * ((nh + 7u) / 8u);
+    const u32 *tc = c->adaptive ? c->d_adapt + 3u * (size_t)n_tiles : nullptr;     // per-tile counts of the last adaptive call
+    HIP_TRY(hipEventRecord(c->dn_ev[0], c->stream));
+    HIP_TRY(launch_denoise(src, 1.0f / (float)count, tc, c->d_guide, c->d_albedo, nw, nh, passes, sc, sn, sp, e0, e1, dst, c->stream));
+    HIP_TRY(hipEventRecord(c->dn_ev[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->dn_ev[0], c->dn_ev[1]));
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->aov_ms = aov_ms; info->filter_ms = ms; info->passes = passes; info->aov_cached = cached ? 1u : 0u;
+    }
+    *out = dst;
+    return MRT_OK;
+}
+
+int mrt_denoise(mrt_ctx *c, const mrt_denoise_opts *o, float *rgb, mrt_denoise_info *info)
+{
+    if (!c || !rgb) return fail(MRT_ERR_ARG, "mrt_denoise: null argument");
+    const float *dst = nullptr;
+    int rc = denoise_run(c, o, info, "mrt_denoise", &dst);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(rgb, dst, (size_t)c->pk.nw * c->pk.nh * 3u * sizeof(float), hipMemcpyDeviceToHost));
+    ok();
+    return MRT_OK;
+}
+
+// mrt_img on the filtered means: tonemap_channel(c', 1.0f, gamma, wexp), then the Lanczos3 path of mrt_img
+int mrt_img_denoised(mrt_ctx *c, const mrt_denoise_opts *o, uint8_t *rgb8, mrt_denoise_info *info)
+{
+    if (!c || !rgb8) return fail(MRT_ERR_ARG, "mrt_img_denoised: null argument");
+    const float *dst = nullptr;
+    int rc = denoise_run(c, o, info, "mrt_img_denoised", &dst);
+    if (rc) return rc;
+    if ((rc = img_prepare(c))) return rc;
+    const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
+    const float wexp = (1.0f - c->pk.exp) * (1.0f - c->pk.exp);
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(launch_tonemap(dst, c->d_ss, nw * nh, 1.0f, c->pk.gamma, wexp, c->stream));
+    if (rw == nw && rh == nh) return img_read_back(c, rgb8, c->d_ss, (size_t)nw * nh * 3);
     HIP_TRY(launch_lanczos_v(c->d_ss, c->d_tmp, nw, rh, c->d_vl, c->d_vc, c->d_vw, c->vcap, c->stream));
     HIP_TRY(launch_lanczos_h(c->d_tmp, c->d_out, nw, rw, rh, c->d_hl, c->d_hc, c->d_hw, c->hcap, c->stream));
     return img_read_back(c, rgb8, c->d_out, (size_t)rw * rh * 3);

@@ -1261,6 +1261,16 @@ MRT_HD void camera_ray(const Params &P, const float *camF, V3 focus, u32 pk, V3 
     o = add(pos, muls(d, kE));
 }
 
+// camera_ray with the lens position at cam_pos (the lens centre, no draws): the first-hit AOV pass (mrt_denoise.h)
+MRT_HD void camera_ray_centre(const Params &P, const float *camF, V3 focus, V3 &o, V3 &d)
+{
+    const V3 pos = v3(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
+    const V3 new_dir = norm(sub(focus, pos));
+    if (P.cam_ident && nzfin3(new_dir)) d = new_dir;
+    else d = m3mul(camF + 9, m3mul(camF, new_dir));
+    o = add(pos, muls(d, kE));
+}
+
 // gen_bool(0.80) of src/rt.rs:564,579 takes the f64 literal 0.80: the threshold is floor(0.8 * 2^32), not the f32 0.8
 constexpr u32 kThr080 = 3435973836u;
 

@@ -203,6 +203,43 @@ class Sampler:
         _lib.check(_lib.lib().mrt_img(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
+    def aov(self) -> dict:
+        """First-hit AOVs of the supersampled frame (mrt_aov): depth f32 [nh][nw] (inf: miss), normal and albedo f32
+        [nh][nw][3], renderer and instance int32 [nh][nw] (indices into the scene's renderers and that renderer's instances,
+        -1: miss).  Computed once per context and kept."""
+        self._need()
+        out = {"depth": np.empty((self.nh, self.nw), np.float32), "normal": np.empty((self.nh, self.nw, 3), np.float32),
+               "albedo": np.empty((self.nh, self.nw, 3), np.float32), "renderer": np.empty((self.nh, self.nw), np.int32),
+               "instance": np.empty((self.nh, self.nw), np.int32)}
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _lib.check(_lib.lib().mrt_aov(self._ctx, out["depth"].ctypes.data_as(fp), out["normal"].ctypes.data_as(fp),
+                                      out["albedo"].ctypes.data_as(fp), out["renderer"].ctypes.data_as(ip),
+                                      out["instance"].ctypes.data_as(ip)))
+        return out
+
+    def denoise(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None) -> np.ndarray:
+        """The accumulated means filtered by the AOV-guided a-trous filter (mrt_denoise), f32 [nh][nw][3].  info: a dict that
+        receives mrt_denoise_info."""
+        self._need()
+        o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane)
+        out = np.empty((self.nh, self.nw, 3), np.float32)
+        di = _abi.DenoiseInfo()
+        _lib.check(_lib.lib().mrt_denoise(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(di)))
+        if info is not None:
+            info.update({k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"})
+        return out
+
+    def img_denoised(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None) -> np.ndarray:
+        """img() of the denoised means (mrt_img_denoised), uint8 [res_h][res_w][3]."""
+        self._need()
+        o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane)
+        out = np.empty((self.res[1], self.res[0], 3), np.uint8)
+        di = _abi.DenoiseInfo()
+        _lib.check(_lib.lib().mrt_img_denoised(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(di)))
+        if info is not None:
+            info.update({k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"})
+        return out
+
     # -- extras of the C ABI -----------------------------------------------------------------
     def _need(self):
         if self._ctx is None:

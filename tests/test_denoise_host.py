@@ -1,0 +1,392 @@
+"""First-hit AOVs and the a-trous denoiser without a GPU: csrc/mrt_denoise.h compiled for x86 (tests/emu/denoise_probe.cpp)
+against a numpy float32 restatement of the filter, bit for bit; the x86 AOV pass against analytic closest
+hits; the filter's quality on an oracle render; the Python option and CLI helpers."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+f32 = np.float32
+K5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], f32)
+
+
+def build_probe(out_dir):
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no g++")
+    out = os.path.join(str(out_dir), "libdenoise_probe.so")
+    fma = []
+    try:
+        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
+            fma = ["-mfma"]      # as tests/emu/Makefile: the kernels' fused multiply-adds (cull margins) in hardware
+    except OSError:
+        pass
+    cs = os.path.join(ROOT, "micro_raytracer_amd", "csrc")
+    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
+                           "-Wno-unused-function", "-o", out, os.path.join(ROOT, "tests", "emu", "denoise_probe.cpp"),
+                           os.path.join(cs, "mrt_pack.cpp")])
+    L = C.CDLL(out)
+    fp, u32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    L.dn_error.restype = C.c_char_p
+    L.dn_aov.argtypes = [C.c_void_p, fp, fp, i32p, i32p]
+    L.dn_filter.argtypes = [fp, u32p, fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, fp]
+    return L
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    return build_probe(tmp_path_factory.mktemp("denoise"))
+
+
+def _p(a, t=C.c_float):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def x86_aov(L, holder, nw, nh):
+    g = np.zeros((nh, nw, 8), f32)
+    alb = np.zeros((nh, nw, 3), f32)
+    rend = np.zeros((nh, nw), np.int32)
+    inst = np.zeros((nh, nw), np.int32)
+    rc = L.dn_aov(C.cast(holder.ptr(), C.c_void_p), _p(g), _p(alb), _p(rend, C.c_int32), _p(inst, C.c_int32))
+    assert rc == 0, L.dn_error()
+    return g, alb, rend, inst
+
+
+def x86_filter(L, A, counts, g, alb, passes, sc, sn, sp):
+    nh, nw = counts.shape
+    out = np.zeros((nh, nw, 3), f32)
+    L.dn_filter(_p(np.ascontiguousarray(A, f32)), _p(np.ascontiguousarray(counts, np.uint32), C.c_uint32),
+                _p(np.ascontiguousarray(g, f32)), _p(np.ascontiguousarray(alb, f32)), nw, nh, passes, sc, sn, sp, _p(out))
+    return out
+
+
+def inv_sq(sigma):
+    s = f32(sigma)
+    with np.errstate(over="ignore"):
+        return f32(f32(1.0) / (s * s))
+
+
+def np_filter(A, counts, g, alb, passes, sc, sn, sp):
+    """The formula of DESIGN.md §13 in float32, in its operation order (taps with w > 0 only)."""
+    nh, nw = counts.shape
+    with np.errstate(all="ignore"):
+        c = A * (f32(1.0) / counts.astype(f32))[..., None]
+        if passes == 0:
+            return c
+        hit = g[..., 7]
+        D = np.where((hit != 0)[..., None], np.fmax(alb, f32(1 / 256)), f32(1.0))
+        e = c / D
+        n, t, x = g[..., 0:3], g[..., 3], g[..., 4:7]
+        for i in range(passes):
+            s = 1 << i
+            sci = f32(f32(sc) * f32(4 ** i))
+            num = np.zeros_like(e)
+            den = np.zeros((nh, nw), f32)
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    ys, xs = np.arange(nh) + s * dy, np.arange(nw) + s * dx
+                    vy, vx = (ys >= 0) & (ys < nh), (xs >= 0) & (xs < nw)
+                    inside = vy[:, None] & vx[None, :]
+                    yq, xq = np.clip(ys, 0, nh - 1), np.clip(xs, 0, nw - 1)
+                    eq, hq, nq, xq_ = e[yq][:, xq], hit[yq][:, xq], n[yq][:, xq], x[yq][:, xq]
+                    k = f32(K5[dx + 2] * K5[dy + 2])
+                    d = e - eq
+                    wc = np.fmax(f32(0), f32(1) - ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) * f32(sci))
+                    m = n - nq
+                    wn = np.fmax(f32(0), f32(1) - ((m[..., 0] * m[..., 0] + m[..., 1] * m[..., 1]) + m[..., 2] * m[..., 2]) * f32(sn))
+                    u = xq_ - x
+                    r = ((n[..., 0] * u[..., 0] + n[..., 1] * u[..., 1]) + n[..., 2] * u[..., 2]) / t
+                    wp = np.fmax(f32(0), f32(1) - (r * r) * f32(sp))
+                    on = hit != 0
+                    wn = np.where(on, wn, f32(1))
+                    wp = np.where(on, wp, f32(1))
+                    w = ((k * wc) * wn) * wp
+                    w = np.where(inside & (hit == hq), w, f32(0)).astype(f32)
+                    use = w > 0
+                    num = np.where(use[..., None], num + w[..., None] * eq, num)
+                    den = np.where(use, den + w, den)
+            e = np.where((den > 0)[..., None], num / den[..., None], e).astype(f32)
+        return (e * D).astype(f32)
+
+
+def random_case(rng, nh, nw, count=16):
+    """Sums, counts and guides with misses, zero and black albedo, NaN / inf / negative radiance and equal-normal planes."""
+    A = rng.gamma(1.5, 2.0, (nh, nw, 3)).astype(f32) * f32(count)
+    sel = rng.random((nh, nw))
+    A[sel < 0.01] = np.nan
+    A[(sel >= 0.01) & (sel < 0.02)] = np.inf
+    A[(sel >= 0.02) & (sel < 0.03)] *= f32(-1)
+    A[(sel >= 0.03) & (sel < 0.05)] = 0
+    counts = np.full((nh, nw), count, np.uint32)
+    g = np.zeros((nh, nw, 8), f32)
+    hit = rng.random((nh, nw)) > 0.15
+    n = rng.normal(size=(nh, nw, 3))
+    n /= np.linalg.norm(n, axis=2, keepdims=True)
+    plane = rng.random((nh, nw)) < 0.5                   # a plane of equal normals z = 1 at depth ~ 2
+    n[plane] = (0.0, 0.0, 1.0)
+    g[..., 0:3] = n
+    g[..., 3] = rng.uniform(0.5, 4.0, (nh, nw))
+    yy, xx = np.mgrid[0:nh, 0:nw]
+    g[..., 4] = xx * 0.01
+    g[..., 5] = yy * 0.01
+    g[..., 6] = np.where(plane, 2.0, rng.uniform(0, 3, (nh, nw)))
+    g[..., 7] = hit
+    g[~hit, 0:3] = 0
+    g[~hit, 3] = np.inf
+    g[~hit, 4:7] = 0
+    alb = rng.random((nh, nw, 3)).astype(f32)
+    alb[rng.random((nh, nw)) < 0.1] = 0                 # black
+    alb[rng.random((nh, nw)) < 0.05, 1] = 0             # one zero channel
+    alb[~hit] = 0
+    return A, counts, g, alb
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, f32), np.asarray(b, f32)
+    both_nan = np.isnan(a) & np.isnan(b)
+    return int(np.count_nonzero((a.view(np.uint32) != b.view(np.uint32)) & ~both_nan))
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 7), (7, 13), (67, 129)])
+def test_filter_x86_matches_numpy(probe, shape):
+    rng = np.random.default_rng(shape[0] * 1000 + shape[1])
+    nh, nw = shape
+    A, counts, g, alb = random_case(rng, nh, nw)
+    sigmas = [(0.5, 0.25, 0.05), (2.0, np.inf, 0.3), (np.inf, np.inf, np.inf), (0.05, 1.0, np.inf)]
+    for passes in range(7):
+        for sig in sigmas:
+            sc, sn, sp = (inv_sq(s) for s in sig)
+            got = x86_filter(probe, A, counts, g, alb, passes, sc, sn, sp)
+            ref = np_filter(A, counts, g, alb, passes, sc, sn, sp)
+            assert same_bits(got, ref) == 0, (shape, passes, sig)
+
+
+def test_filter_per_pixel_counts(probe):
+    """Adaptive renders: each pixel's own count (here mixed 8x8 tile counts)."""
+    rng = np.random.default_rng(5)
+    nh, nw = 21, 30
+    A, _, g, alb = random_case(rng, nh, nw)
+    tiles = rng.choice([32, 64, 96], size=((nh + 7) // 8, (nw + 7) // 8)).astype(np.uint32)
+    counts = np.repeat(np.repeat(tiles, 8, 0), 8, 1)[:nh, :nw]
+    for passes in (0, 1, 4):
+        sc, sn, sp = inv_sq(0.5), inv_sq(0.25), inv_sq(0.05)
+        assert same_bits(x86_filter(probe, A, counts, g, alb, passes, sc, sn, sp), np_filter(A, counts, g, alb, passes, sc, sn, sp)) == 0
+
+
+def test_filter_passes0_is_the_mean_and_flat_frames_stay(probe):
+    rng = np.random.default_rng(9)
+    A, counts, g, alb = random_case(rng, 9, 11)
+    out = x86_filter(probe, A, counts, g, alb, 0, 1.0, 1.0, 1.0)
+    assert same_bits(out, A * (f32(1) / f32(16))) == 0
+    # a constant image on one plane with one albedo is a fixed point of every pass
+    g[..., 0:3] = (0, 0, 1)
+    g[..., 3] = 2.0
+    g[..., 6] = 2.0
+    g[..., 7] = 1
+    alb[:] = 0.5
+    A2 = np.full_like(A, 8.0)
+    out = x86_filter(probe, A2, counts, g, alb, 5, inv_sq(0.5), inv_sq(0.25), inv_sq(0.05))
+    assert np.array_equal(out, np.full_like(out, 0.5))
+
+
+# ---- AOVs against analytic closest hits --------------------------------------------------------------------------------
+def _analytic_scene(aprt=None):
+    cam = {"pos": [0, -1.5, 0.1], "fov": 60, "gamma": 0.5, "exp": 0.5}
+    if aprt is not None:
+        cam.update({"aprt": aprt, "foc": 1.2})
+    return {
+        "rt": {"sample": 1, "bounce": 2},
+        "frame": {"res": [61, 43], "ssaa": 1, "cam": cam},
+        "scene": {"renderer": [
+            {"type": "plane", "n": [0, 0, 1], "pos": [0, 0, -0.3], "mat": {"albedo": "#808080"}},
+            {"type": "plane", "n": [0, -1, 0], "pos": [0, 1.5, 0]},
+            {"type": "sphere", "r": 0.25, "mat": {"albedo": "#ff0000"},
+             "inst": [[[-0.4, 0.2, 0.0], [0, 0, 1, 0]], [[0.1, 0.6, 0.35], [0, 0, 1, 0]]]},
+            {"type": "box", "sizes": [0.3, 0.4, 0.2], "pos": [0.45, 0.3, -0.05], "mat": {"albedo": "#20c040"}},
+        ]},
+    }
+
+
+def np_first_hits(render):
+    """Closest hit of the lens-centre ray of every pixel, float64: depth, normal, renderer, instance."""
+    fr = render.frame
+    cam = fr.cam
+    w, h = f32(f32(fr.res[0]) * f32(fr.ssaa)), f32(f32(fr.res[1]) * f32(fr.ssaa))
+    nw, nh = int(round(w)), int(round(h))
+    aspect = w / h
+    inv2tan = 1.0 / (2.0 * np.tan(np.radians(cam.fov / 2.0)))
+    yy, xx = np.mgrid[0:nh, 0:nw].astype(np.float64)
+    uvx = aspect * (xx - 0.5 * w) / w
+    uvy = (yy - 0.5 * h) / h
+    d = np.stack([uvx, np.full_like(uvx, inv2tan), -uvy], -1)
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    o = np.asarray(cam.pos, np.float64) + d * 1e-4
+    best = np.full((nh, nw), np.inf)
+    nrm = np.zeros((nh, nw, 3))
+    rid = np.full((nh, nw), -1, np.int32)
+    iid = np.full((nh, nw), -1, np.int32)
+
+    def take(t, n, r, i):
+        better = (t > 0) & (t < best)
+        best[better] = t[better]
+        nrm[better] = n[better]
+        rid[better] = r
+        iid[better] = i
+
+    for r, rd in enumerate(render.scene.renderer):
+        for i, (pos, _) in enumerate(rd.inst):
+            pos = np.asarray(pos, np.float64)
+            if rd.kind == "plane":
+                n = np.asarray(rd.n, np.float64)
+                n = n / np.linalg.norm(n)
+                with np.errstate(all="ignore"):
+                    t = ((pos - o) @ n) / (d @ n)
+                take(np.nan_to_num(t, nan=-1.0), np.broadcast_to(n, d.shape), r, i)
+            elif rd.kind == "sphere":
+                oc = o - pos
+                b = np.sum(oc * d, -1)
+                disc = b * b - (np.sum(oc * oc, -1) - rd.r ** 2)
+                with np.errstate(invalid="ignore"):
+                    t = np.where(disc >= 0, -b - np.sqrt(np.maximum(disc, 0)), -1.0)
+                p = o + d * t[..., None]
+                take(t, (p - pos) / rd.r, r, i)
+            elif rd.kind == "box":
+                half = 0.5 * np.asarray(rd.sizes, np.float64)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    t1 = (pos - half - o) / d
+                    t2 = (pos + half - o) / d
+                tn = np.max(np.minimum(t1, t2), -1)
+                tf = np.min(np.maximum(t1, t2), -1)
+                t = np.where((tn <= tf) & (tf > 0), tn, -1.0)
+                p = o + d * t[..., None]
+                q = (p - pos) / half
+                ax = np.argmax(np.abs(q), -1)
+                n = np.zeros_like(q)
+                np.put_along_axis(n, ax[..., None], np.sign(np.take_along_axis(q, ax[..., None], -1)), -1)
+                take(t, n, r, i)
+    return best, nrm, rid, iid
+
+
+def id_edges(rid, iid):
+    key = rid.astype(np.int64) * 1000 + iid
+    e = np.zeros(key.shape, bool)
+    for a in (0, 1):
+        diff = np.diff(key, axis=a) != 0
+        if a == 0:
+            e[1:] |= diff
+            e[:-1] |= diff
+        else:
+            e[:, 1:] |= diff
+            e[:, :-1] |= diff
+    return e
+
+
+@pytest.mark.parametrize("aprt", [None, 0.3])
+def test_aov_x86_matches_analytic(probe, aprt):
+    """aprt 0.3: a large lens -- the AOV ray must still leave from its centre (a sample's lens position would move every hit)."""
+    from micro_raytracer_amd import _abi, load_render
+    render = load_render(_analytic_scene(aprt))
+    holder = _abi.build_desc(render)
+    nw, nh = render.frame.res
+    g, alb, rend, inst = x86_aov(probe, holder, nw, nh)
+    depth, nrm, rid, iid = np_first_hits(render)
+    edge = id_edges(rid, iid)
+    bad_ids = (rend != rid) | (inst != iid)
+    assert np.count_nonzero(bad_ids & ~edge) == 0
+    assert np.count_nonzero(bad_ids) <= max(1, int(0.001 * rend.size)) or np.all(bad_ids <= edge)
+    ok = ~bad_ids & ~edge & (rid >= 0)
+    assert ok.sum() > 0.5 * rend.size
+    assert np.allclose(g[..., 3][ok], depth[ok], rtol=1e-5, atol=0)
+    assert np.allclose(g[..., 0:3][ok], nrm[ok], rtol=1e-5, atol=1e-5)
+    miss = rend < 0
+    assert np.all(np.isinf(g[..., 3][miss])) and np.all(g[..., 0:3][miss] == 0) and np.all(alb[miss] == 0) and np.all(inst[miss] == -1)
+    # the hit point is the ray's point at the depth; albedo is the material's
+    hits = rend >= 0
+    assert np.all(g[..., 7][hits] == 1) and np.all(g[..., 7][miss] == 0)
+    assert np.allclose(alb[rend == 2], [1.0, 0.0, 0.0])
+
+
+def test_aov_ids_follow_description_order(probe):
+    """Renderer ids index mrt_scene.renderer; instance ids index that renderer's inst list."""
+    from micro_raytracer_amd import _abi, load_render
+    render = load_render(_analytic_scene())
+    g, alb, rend, inst = x86_aov(probe, _abi.build_desc(render), *render.frame.res)
+    assert {0, 1, 2, 3} <= set(np.unique(rend).tolist())
+    assert set(np.unique(inst[rend == 2])) == {0, 1}
+    assert set(np.unique(inst[(rend >= 0) & (rend != 2)])) == {0}
+
+
+# ---- quality against the oracle -------------------------------------------------------------------------------------
+def tonemapped(mean, gamma, exp):
+    """f of tonemap_channel (before the x 255), float64."""
+    wexp = (1.0 - exp) ** 2
+    g = np.power(np.maximum(np.nan_to_num(mean.astype(np.float64), nan=0.0), 0.0), gamma)
+    return g * (1.0 + g / wexp) / (1.0 + g)
+
+
+def test_quality_cornell_16spp(probe, oracle_mod):
+    from micro_raytracer_amd import _abi, load_render, scenes
+    render = load_render(scenes.cornell_box(res=(64, 64)))
+    holder = _abi.build_desc(render)
+    o = oracle_mod.Oracle(holder, seed=3)
+    o.execute(16)
+    A, _ = o.accum()
+    gt = oracle_mod.Oracle(holder, seed=777)
+    gt.execute(1024)
+    G, _ = gt.accum()
+    g, alb, _, _ = x86_aov(probe, holder, 64, 64)
+    counts = np.full((64, 64), 16, np.uint32)
+    out = x86_filter(probe, A, counts, g, alb, 3, inv_sq(_abi.DENOISE_SIGMA_COLOR), inv_sq(_abi.DENOISE_SIGMA_NORMAL),
+                     inv_sq(_abi.DENOISE_SIGMA_PLANE))
+    cam = render.frame.cam
+    ref = tonemapped(G / f32(1024), cam.gamma, cam.exp)
+    raw = np.sqrt(np.mean((tonemapped(A / f32(16), cam.gamma, cam.exp) - ref) ** 2))
+    den = np.sqrt(np.mean((tonemapped(out, cam.gamma, cam.exp) - ref) ** 2))
+    print(f"cornell 64x64 16 spp: raw RMSE {raw:.4f}, denoised (3 passes) {den:.4f}, ratio {den / raw:.3f}")
+    assert den <= 0.5 * raw
+
+
+# ---- Python options and CLI helpers ------------------------------------------------------------------------------------
+def test_denoise_opts_defaults_match_header():
+    import re
+    from micro_raytracer_amd import _abi
+    hdr = open(os.path.join(ROOT, "include", "mrt.h")).read()
+    val = {k: float(v.rstrip("uf")) for k, v in re.findall(r"#define MRT_DENOISE_(\w+) ([0-9.]+[uf]?)", hdr)}
+    assert val == {"PASSES": _abi.DENOISE_PASSES, "SIGMA_COLOR": _abi.DENOISE_SIGMA_COLOR,
+                   "SIGMA_NORMAL": _abi.DENOISE_SIGMA_NORMAL, "SIGMA_PLANE": _abi.DENOISE_SIGMA_PLANE}
+    o = _abi.denoise_opts()
+    assert (o.passes, o.sigma_color, o.sigma_normal, o.sigma_plane) == (5, f32(0.5), f32(0.25), f32(0.05))
+    o = _abi.denoise_opts(2, sigma_normal=float("inf"))
+    assert o.passes == 2 and np.isinf(o.sigma_normal) and o.sigma_color == f32(_abi.DENOISE_SIGMA_COLOR)
+    assert C.sizeof(_abi.DenoiseOpts) == 32 and C.sizeof(_abi.DenoiseInfo) == 32
+
+
+def test_lib_symbols_list_the_new_entry_points():
+    from micro_raytracer_amd import _lib
+    for s in ("mrt_aov", "mrt_denoise", "mrt_img_denoised"):
+        assert s in _lib.SYMBOLS
+        assert s in open(os.path.join(ROOT, "include", "mrt.h")).read()
+
+
+def test_cli_aov_images():
+    from micro_raytracer_amd.__main__ import aov_images
+    depth = np.array([[1.0, 3.0], [np.inf, 2.0]], f32)
+    normal = np.zeros((2, 2, 3), f32)
+    normal[0, 0] = (1, 0, -1)
+    albedo = np.full((2, 2, 3), 0.5, f32)
+    im = aov_images({"depth": depth, "normal": normal, "albedo": albedo})
+    assert im["depth"].shape == (2, 2, 3) and im["depth"].dtype == np.uint8
+    assert im["depth"][0, 0, 0] == 0 and im["depth"][0, 1, 0] == 255 and im["depth"][1, 0, 0] == 0 and im["depth"][1, 1, 0] == 128
+    assert tuple(im["normal"][0, 0]) == (255, 128, 0)
+    assert np.all(im["albedo"] == 128)
+
+
+def test_cli_rejects_bad_passes():
+    from micro_raytracer_amd.__main__ import main
+    with pytest.raises(SystemExit):
+        main(["scene.json", "--denoise", "--denoise-passes", "9"])
