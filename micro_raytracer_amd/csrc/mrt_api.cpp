@@ -13,6 +13,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mrt.h"
@@ -41,6 +42,15 @@ int fail(int code, const char *fmt, ...)
 }
 void ok() { g_status = MRT_OK; }
 
+// an error path that still waits for work already launched: the caller gets the first error, rc, whatever `cleanup` runs into
+template <class F> int keep_first_error(int rc, F &&cleanup)
+{
+    const std::string keep = g_err;
+    cleanup();
+    g_err = keep; g_status = rc;
+    return rc;
+}
+
 // A HIP call whose failure is tolerated: HIP 7 keeps the last *real* error pending (hipGetLastError no longer reports the
 // last call's status), so the pending error is cleared here or the next launch's hipGetLastError() would report it.
 bool hip_tolerated(hipError_t e)
@@ -55,6 +65,31 @@ bool hip_tolerated(hipError_t e)
         hipError_t e_ = (expr);                                                                                \
         if (e_ != hipSuccess) return fail(MRT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));    \
     } while (0)
+
+// ---- owners of device resources: every allocation, event and stream of a context is released by its owner's destructor ----
+// `n` elements of T in device memory.  alloc frees what is held, then asks for `count` elements (`bytes` instead when it is
+// not 0: MRT_PARTIAL_FAIL_ALLOC asks for an impossible size), and leaves the owner empty when that fails.
+template <class T> struct DeviceMem {
+    T *p = nullptr;
+    size_t n = 0;
+    DeviceMem() = default;
+    DeviceMem(DeviceMem &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    ~DeviceMem() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    hipError_t alloc(size_t count, size_t bytes = 0)
+    {
+        reset();
+        const hipError_t e = hipMalloc((void **)&p, bytes ? bytes : count * sizeof(T));
+        if (e == hipSuccess) n = count; else p = nullptr;
+        return e;
+    }
+};
+struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+using Event = std::unique_ptr<ihipEvent_t, EventDestroy>;
+using Stream = std::unique_ptr<ihipStream_t, StreamDestroy>;
+hipError_t create(Event &ev) { hipEvent_t e; const hipError_t r = hipEventCreate(&e); if (r == hipSuccess) ev.reset(e); return r; }
+hipError_t create(Stream &st) { hipStream_t s; const hipError_t r = hipStreamCreateWithFlags(&s, hipStreamNonBlocking); if (r == hipSuccess) st.reset(s); return r; }
 
 // ---- RCCL, loaded on demand (only in-process multi-device contexts need it; signatures from rccl/rccl.h) ----
 typedef struct ncclComm *ncclComm_t;
@@ -123,14 +158,63 @@ hipError_t configure_pt_once(int device)      // the caller has made `device` cu
     return hipSuccess;
 }
 
+// ---- per-feature state: built whole on first use (a group's by mrt_create), held by the context through a unique_ptr ----
+
+// look-ahead of the eager per-call path: two sets of per-sample planes [n][padded_rows][nw][3], set i: samples [base[i], + n[i])
+struct Lookahead {
+    Stream stream;                                // the look-ahead launches; the folds run on the context's stream
+    Event ev0[2], ev1[2];                         // around set i's trace launch, on `stream`
+    DeviceMem<u32> counter;                       // tile counter of persistent look-ahead launches (the eager launches keep their own)
+    DeviceMem<float> planes[2];
+    u32 base[2] = {0, 0}, n[2] = {0, 0};
+};
+// adaptive sampling (mrt_execute_adaptive)
+struct Adaptive {
+    DeviceMem<float> half;                        // H: [padded_rows][nw][3], per pixel the sum of its even-numbered rounds
+    DeviceMem<u32> tiles;                         // [n_tiles] x 5 + 1: two tile lists, keep flags, per-tile count, per-tile converged flag, list length
+    u32 n_tiles = 0;
+    std::vector<u32> tile_count;                  // per-tile counts of the last adaptive call (host copy)
+    u32 *counts() const { return tiles.p + 3u * (size_t)n_tiles; }      // ... on the device, where the tone map and the denoiser read them
+};
+// the image path (mrt_img, mrt_img_ss, mrt_img_denoised); Lanczos3 to the output resolution when it differs: the taps of both
+// passes (vl ... hcap), the vertical pass's output (tmp), the image (out)
+struct Image {
+    DeviceMem<unsigned char> ss;                  // the tone-mapped supersampled frame [nh][nw][3]
+    DeviceMem<u32> vl, vc, hl, hc;
+    DeviceMem<float> vw, hw, tmp;
+    DeviceMem<unsigned char> out;
+    u32 vcap = 0, hcap = 0;
+};
+// first-hit AOVs and the denoiser (mrt_aov, mrt_denoise: DESIGN.md §13), on the context's device; the AOVs depend on scene and
+// camera only and survive mrt_reset
+struct Aov {
+    DeviceMem<float> guide;                       // [2][nh][nw] float4: (normal, depth), (world point, hit flag)
+    DeviceMem<float> albedo;                      // [nh][nw][3]
+    DeviceMem<i32> ids;                           // [nh][nw][2]: renderer, flat instance index
+    DeviceMem<unsigned long long> seg;            // the AOV kernel's diagnostic counters (mrt_trace.h count_fallback)
+    DeviceMem<u32> blob;                          // the scene the AOV kernel reads when the context's is not it (deep staging, multi-device contexts)
+    Event ev[2];                                  // around the AOV pass, then around the filter
+    std::vector<u32> inst_first;                  // flat index of each renderer's first instance (ids -> mrt_scene order)
+    DeviceMem<float> dn;                          // two e planes ([nh][nw] float4) and the filtered means [nh][nw][3]: the first mrt_denoise
+};
+// in-process multi-device context (mrt_opts.n_devices > 1): one sharded sub-context per device, gathered on device 0
+struct Group {
+    std::vector<std::unique_ptr<mrt_ctx>> subs;
+    std::vector<ncclComm_t> comms;
+    DeviceMem<float> gather;                      // [n_devices][padded_rows][nw][3] on device 0
+    DeviceMem<u32> rowmap;                        // [n_devices][padded_rows] frame row of each gathered row (0xffffffff: padding)
+    void release();                               // the sub-contexts, then the comms
+    ~Group();
+};
+
 }  // namespace
 
 struct mrt_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // img timing; on a group context: around scatter_rows
-    hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;  // sub-context of a group: around this rank's part of the ncclGather, on its stream
-    std::vector<hipEvent_t> evs;                  // 3 per launch of the last execute: start, after pt_megakernel, after reduce_chunks
+    Stream stream;                                // declared first: destroyed last
+    Event ev0, ev1;                               // img timing; on a group context: around scatter_rows
+    Event ev_g0, ev_g1;                           // sub-context of a group: around this rank's part of the ncclGather, on its stream
+    std::vector<Event> evs;                       // 3 per launch of the last execute: start, after pt_megakernel, after reduce_chunks
     u32 ev_used = 0;
     bool stats_pending = false;                   // event times / segment counter of the last execute not read back yet
     bool count_segments = false;                  // MRT_FLAG_COUNT_SEGMENTS
@@ -147,70 +231,58 @@ struct mrt_ctx {
     bool knob_partial_fail = false;               // MRT_PARTIAL_FAIL_ALLOC: the chunk-plane allocation asks for an impossible size
     bool debug_fallbacks = false;                 // MRT_DEBUG_FALLBACKS: mrt_get_stats prints the reference-walk fallbacks of the mesh queries
     u32 pending = 0;                              // samples requested by deferred mrt_execute calls and not traced yet
-    // Look-ahead of the eager per-call path (the reference's callers run one Sampler::execute per sample, src/cli.rs:162-170):
-    // see run_lookahead.  Two sets of per-sample planes [n][padded_rows][nw][3]; set i holds samples [la_base[i], la_base[i] + la_n[i]).
+    // look-ahead of the eager per-call path (the reference's callers run one Sampler::execute per sample): see run_lookahead
     bool la_enabled = false;                      // eager single-device context without MRT_FLAG_NO_LOOKAHEAD / MRT_LOOKAHEAD=0
     u32 la_max = 32;                              // samples per look-ahead launch at most (MRT_LOOKAHEAD=n)
     u32 la_streak = 0;                            // consecutive one-sample calls so far
-    hipStream_t la_stream = nullptr;              // the look-ahead launches; the folds run on `stream`
-    float *d_la[2] = {nullptr, nullptr};
-    size_t la_floats[2] = {0, 0};
-    u32 la_base[2] = {0, 0}, la_n[2] = {0, 0};
-    hipEvent_t la_ev0[2] = {nullptr, nullptr}, la_ev1[2] = {nullptr, nullptr};   // around set i's trace launch, on la_stream
-    u32 *d_la_counter = nullptr;                  // tile counter of persistent look-ahead launches (the eager launches keep their own)
+    std::unique_ptr<Lookahead> la;
     Packed pk;
+    std::unique_ptr<Packed> aov_pk;               // deep-staged contexts: the scene as packed without them (binary triangle BVHs) for the AOV kernel
     Params P;
-    u32 *d_blob = nullptr;
-    float *d_accum = nullptr;            // [padded_rows][nw][3], rows past local_rows stay zero
-    float *d_accum_own = nullptr;        // library-owned allocation (d_accum may point to caller memory)
-    float *d_partial = nullptr;          // chunk sums of a sample-split launch
-    size_t partial_floats = 0;
+    DeviceMem<u32> blob;                          // the packed scene (none on a group context: it lives on the sub-contexts)
+    float *d_accum = nullptr;                     // [padded_rows][nw][3], rows past local_rows stay zero: accum_own or caller memory
+    DeviceMem<float> accum_own;
+    DeviceMem<float> partial;                     // chunk sums of a sample-split launch
     u32 padded_rows = 0;
-    unsigned long long *d_segments = nullptr;
-    u32 count = 0;                       // Sampler.last_count
+    DeviceMem<unsigned long long> segments;       // segment counter + tile counter + 4 phase clocks (debug builds)
+    u32 count = 0;                                // Sampler.last_count
     uint64_t seed = 0;
     u32 shard_index = 0, shard_count = 1, shard_rows = 8, local_rows = 0;
-    std::vector<u32> row_of;             // local row -> frame row
-    bool whole_frame = true;             // accumulator holds every row (shard_count == 1 or after set_accum)
-    float *d_full = nullptr;             // [nh][nw][3] when a sharded context received a full frame
+    std::vector<u32> row_of;                      // local row -> frame row
+    DeviceMem<float> full;                        // [nh][nw][3]: a group's frame, or the full frame a sharded context received
     u32 full_count = 0;
-    u32 block_threads = 256;             // workgroup size of the batched launches
-    bool small_plain_grid = false;       // launches of less than one sample chunk (the per-sample calls of the reference's callers) take
-                                         // the plain grid, one workgroup per 2x2 wave tiles: no tile counter to reset and draw from
-    u32 persist_grid = 0;                // persistent grid of the batched shape
+    u32 block_threads = 256;                      // workgroup size of the batched launches
+    bool small_plain_grid = false;                // launches of less than one sample chunk (the per-sample calls of the reference's callers) take
+                                                  // the plain grid, one workgroup per 2x2 wave tiles: no tile counter to reset and draw from
+    u32 persist_grid = 0;                         // persistent grid of the batched shape
     bool scene_in_lds = true;
-    // img resources (lazy)
-    unsigned char *d_ss = nullptr, *d_out = nullptr;
-    float *d_tmp = nullptr;
-    u32 *d_vl = nullptr, *d_vc = nullptr, *d_hl = nullptr, *d_hc = nullptr;
-    float *d_vw = nullptr, *d_hw = nullptr;
-    u32 vcap = 0, hcap = 0;
     mrt_stats stats;
-    // in-process multi-device context (mrt_opts.n_devices > 1): one sharded sub-context per device, gathered on device 0
-    std::vector<mrt_ctx *> subs;
-    std::vector<ncclComm_t> comms;
-    float *d_gather = nullptr;           // [n_devices][padded_rows][nw][3] on device 0
-    u32 *d_rowmap = nullptr;             // [n_devices][padded_rows] frame row of each gathered row (0xffffffff: padding)
-    // adaptive sampling (mrt_execute_adaptive), allocated by the first adaptive call
-    bool adaptive = false;               // the accumulator holds an adaptive render: per-tile counts, count = the smallest
-    float *d_half = nullptr;             // H: [padded_rows][nw][3], per pixel the sum of its even-numbered rounds
-    u32 *d_adapt = nullptr;              // [n_tiles] x 5 + 1: two tile lists, keep flags, per-tile count, per-tile converged flag, list length
-    std::vector<u32> tile_count;         // per-tile counts of the last adaptive call (host copy)
-    // first-hit AOVs and the denoiser (mrt_aov, mrt_denoise: DESIGN.md §13), on `device`, allocated by the first call; the AOVs
-    // depend on scene and camera only and survive mrt_reset
-    std::unique_ptr<Packed> aov_pk;      // deep-staged contexts: the scene as packed without them (binary triangle BVHs) for the AOV kernel
-    u32 *d_aov_blob = nullptr;           // the scene the AOV kernel reads when d_blob is not it (deep staging, multi-device contexts)
-    unsigned long long *d_aov_seg = nullptr;   // its diagnostic counters (mrt_trace.h count_fallback)
-    float *d_guide = nullptr;            // [2][nh][nw] float4: (normal, depth), (world point, hit flag)
-    float *d_albedo = nullptr;           // [nh][nw][3]
-    i32 *d_ids = nullptr;                // [nh][nw][2]: renderer, flat instance index
-    bool aov_ready = false;
-    std::vector<u32> inst_first;         // flat index of each renderer's first instance (ids -> mrt_scene order)
-    float *d_dn = nullptr;               // two e planes ([nh][nw] float4) and the filtered means [nh][nw][3]
-    hipEvent_t dn_ev[2] = {nullptr, nullptr};
+    std::unique_ptr<Group> group;
+    bool adaptive = false;                        // the accumulator holds an adaptive render: per-tile counts, count = the smallest
+    std::unique_ptr<Adaptive> ad;
+    std::unique_ptr<Image> img;
+    bool aov_ready = false;                       // the AOVs have been computed
+    std::unique_ptr<Aov> aov;
+    // The sub-contexts and the RCCL comms go first; then this context's own resources on its device -- the look-ahead planes
+    // only after the launches that write them have ended -- and its stream last (members are destroyed in reverse order).
+    ~mrt_ctx()
+    {
+        if (group) group->release();
+        if (!stream) return;                      // nothing was created on the device
+        (void)hipSetDevice(device);
+        if (la) (void)hipStreamSynchronize(la->stream.get());
+    }
 };
 
 namespace {
+
+void Group::release()
+{
+    subs.clear();
+    for (ncclComm_t cm : comms) if (cm) g_rccl.CommDestroy(cm);
+    comms.clear();
+}
+Group::~Group() { release(); }
 
 // floats of one [padded_rows][nw][3] plane: the accumulator, H, a chunk plane, a look-ahead plane
 size_t plane_floats(const mrt_ctx *c) { return (size_t)c->padded_rows * c->pk.nw * 3; }
@@ -221,28 +293,21 @@ int set_device(const mrt_ctx *c)
     return MRT_OK;
 }
 
-void free_ctx(mrt_ctx *c)
+// The frame an observation reads and its sample count: the full frame of a group, or of a sharded context that received one,
+// else the accumulator -- rgb is null when that holds only the context's own rows.
+struct Frame { const float *rgb; u32 count; };
+Frame frame_of(const mrt_ctx *c)
 {
-    if (!c) return;
-    for (mrt_ctx *sub : c->subs) free_ctx(sub);
-    for (ncclComm_t cm : c->comms) if (cm) g_rccl.CommDestroy(cm);
-    (void)hipSetDevice(c->device);
-    if (c->d_gather) (void)hipFree(c->d_gather);
-    if (c->d_rowmap) (void)hipFree(c->d_rowmap);
-    if (c->la_stream) { (void)hipStreamSynchronize(c->la_stream); (void)hipStreamDestroy(c->la_stream); }
-    for (int i = 0; i < 2; ++i) { if (c->la_ev0[i]) (void)hipEventDestroy(c->la_ev0[i]); if (c->la_ev1[i]) (void)hipEventDestroy(c->la_ev1[i]); }
-    void *ptrs[] = {c->d_blob, c->d_accum_own, c->d_partial, c->d_segments, c->d_full, c->d_ss, c->d_out, c->d_tmp, c->d_vl, c->d_vc, c->d_hl, c->d_hc, c->d_vw, c->d_hw,
-                    c->d_la[0], c->d_la[1], c->d_la_counter, c->d_half, c->d_adapt, c->d_aov_blob, c->d_aov_seg, c->d_guide, c->d_albedo, c->d_ids,
-                    c->d_dn};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev_g0) (void)hipEventDestroy(c->ev_g0);
-    if (c->ev_g1) (void)hipEventDestroy(c->ev_g1);
-    for (hipEvent_t e : c->evs) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c->full.p) return {c->full.p, c->full_count};
+    return {c->shard_count == 1 ? c->d_accum : nullptr, c->count};
+}
+// ... for an observation of the whole frame's means (the image, the denoiser), refused without the whole frame or a sample
+int whole_frame(const mrt_ctx *c, const char *fn, const char *empty_note, Frame &f)
+{
+    f = frame_of(c);
+    if (!f.rgb) return fail(MRT_ERR_STATE, "%s: this context holds only its own rows; gather and mrt_set_accum first", fn);
+    if (f.count == 0) return fail(MRT_ERR_STATE, "%s: no samples accumulated%s", fn, empty_note);
+    return MRT_OK;
 }
 
 }  // namespace
@@ -402,56 +467,51 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     const u32 shard_count = opts->shard_count ? opts->shard_count : 1;
     if (opts->shard_index >= shard_count) { fail(MRT_ERR_ARG, "mrt_create: shard_index %u >= shard_count %u", opts->shard_index, shard_count); return nullptr; }
 
-    mrt_ctx *c = new mrt_ctx();
+    std::unique_ptr<mrt_ctx> c(new mrt_ctx());              // every failure below: the context is destroyed with what it holds
     std::string err;
     const int rc = pack_scene(desc, c->pk, err);
-    if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); delete c; return nullptr; }
+    if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); return nullptr; }
     Plan plan;
     plan_launch(desc, c->pk, plan);          // may re-pack the scene (deep staging: 4-wide triangle BVHs), before anything is uploaded
     if (c->pk.tbvh_wide) {                   // the AOV kernel (scene through L2, no F_DEEP build) walks the binary triangle BVHs
         c->aov_pk.reset(new Packed());
-        if (pack_scene(desc, *c->aov_pk, err) != MRT_OK) { fail(MRT_ERR_SCENE, "mrt_create: %s", err.c_str()); delete c; return nullptr; }
+        if (pack_scene(desc, *c->aov_pk, err) != MRT_OK) { fail(MRT_ERR_SCENE, "mrt_create: %s", err.c_str()); return nullptr; }
     }
 
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fail(MRT_ERR_DEVICE, "mrt_create: no HIP device (this backend has no CPU path)");
-        delete c; return nullptr;
-    }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fail(MRT_ERR_DEVICE, "mrt_create: no HIP device (this backend has no CPU path)"); return nullptr; }
     int dev = opts->device;
     if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
-    if (dev >= ndev) { fail(MRT_ERR_ARG, "mrt_create: device %d of %d", dev, ndev); delete c; return nullptr; }
+    if (dev >= ndev) { fail(MRT_ERR_ARG, "mrt_create: device %d of %d", dev, ndev); return nullptr; }
     c->device = dev;
     c->seed = opts->seed;
     c->shard_index = opts->shard_index; c->shard_count = shard_count;
     c->shard_rows = opts->shard_rows ? opts->shard_rows : 8;
-    c->whole_frame = shard_count == 1;
 
     // rows of this shard: row block b (shard_rows rows) belongs to shard b % shard_count
     const u32 nh = c->pk.nh;
     for (u32 y = 0; y < nh; ++y) if ((y / c->shard_rows) % shard_count == c->shard_index) c->row_of.push_back(y);
     c->local_rows = (u32)c->row_of.size();
 
-    auto bail = [&](int code, const char *what, hipError_t e) { fail(code, "mrt_create: %s: %s", what, hipGetErrorString(e)); free_ctx(c); return (mrt_ctx *)nullptr; };
+    auto bail = [&](int code, const char *what, hipError_t e) { fail(code, "mrt_create: %s: %s", what, hipGetErrorString(e)); return (mrt_ctx *)nullptr; };
     hipError_t e;
     if ((e = hipSetDevice(dev)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipStreamCreate", e);
-    if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipEventCreate", e);
-    if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipEventCreate", e);
-    const size_t all_bytes = (size_t)c->pk.blob.size() * 4;
-    if ((e = hipMalloc((void **)&c->d_blob, all_bytes ? all_bytes : 16)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(scene)", e);
-    if ((e = hipMemcpy(c->d_blob, c->pk.blob.data(), all_bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemcpy(scene)", e);
+    if ((e = create(c->stream)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipStreamCreate", e);
+    if ((e = create(c->ev0)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipEventCreate", e);
+    if ((e = create(c->ev1)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipEventCreate", e);
+    const size_t all_words = c->pk.blob.size();
+    if ((e = c->blob.alloc(all_words ? all_words : 4)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(scene)", e);
+    if ((e = hipMemcpy(c->blob.p, c->pk.blob.data(), all_words * 4, hipMemcpyHostToDevice)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemcpy(scene)", e);
     {
         const u32 n_blocks = (nh + c->shard_rows - 1) / c->shard_rows;
         c->padded_rows = ((n_blocks + shard_count - 1) / shard_count) * c->shard_rows;
         if (shard_count == 1) c->padded_rows = nh;
     }
-    const size_t acc_bytes = plane_floats(c) * sizeof(float);
-    if ((e = hipMalloc((void **)&c->d_accum_own, acc_bytes)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(accumulator)", e);
-    c->d_accum = c->d_accum_own;
-    if ((e = hipMemset(c->d_accum, 0, acc_bytes)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
-    if ((e = hipMalloc((void **)&c->d_segments, 8 * sizeof(unsigned long long))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc", e);   // + tile counter + 4 phase clocks (debug builds)
-    if ((e = hipMemset(c->d_segments, 0, 8 * sizeof(unsigned long long))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
+    if ((e = c->accum_own.alloc(plane_floats(c.get()))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(accumulator)", e);
+    c->d_accum = c->accum_own.p;
+    if ((e = hipMemset(c->d_accum, 0, plane_floats(c.get()) * sizeof(float))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
+    if ((e = c->segments.alloc(8)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc", e);
+    if ((e = hipMemset(c->segments.p, 0, 8 * sizeof(unsigned long long))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
 
     c->scene_in_lds = plan.in_lds;
     c->small_plain_grid = plan.small_plain_grid;
@@ -465,8 +525,8 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     c->P = c->pk.P;
     c->P.local_rows = c->local_rows; c->P.shard_index = c->shard_index; c->P.shard_count = c->shard_count; c->P.shard_rows = c->shard_rows;
     c->P.seed_lo = (u32)c->seed; c->P.seed_hi = (u32)(c->seed >> 32);
-    c->P.blob = c->d_blob; c->P.accum = c->d_accum; c->P.segments = c->d_segments;
-    c->P.tile_counter = reinterpret_cast<u32 *>(c->d_segments + 1);
+    c->P.blob = c->blob.p; c->P.accum = c->d_accum; c->P.segments = c->segments.p;
+    c->P.tile_counter = reinterpret_cast<u32 *>(c->segments.p + 1);
     {
         // persistent launches (workgroups of more than one wavefront): as many workgroups as fit the device at once; each
         // wavefront then draws 8x8 tiles from a counter, so no CU waits for the slowest wavefront of a workgroup
@@ -498,12 +558,12 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
     c->la_enabled = !c->defer && !c->count_segments && (opts->flags & MRT_FLAG_NO_LOOKAHEAD) == 0;
     if (const char *f = getenv("MRT_LOOKAHEAD")) { const int v = atoi(f); if (v <= 1) c->la_enabled = false; else c->la_max = v > 64 ? 64u : (u32)v; }
     {   // both plane sets together stay below 4 GiB (32 samples of a 1080p frame: 2 x 0.8 GB; a 4K frame gets 20 per launch)
-        const size_t plane_bytes = plane_floats(c) * sizeof(float);
+        const size_t plane_bytes = plane_floats(c.get()) * sizeof(float);
         const size_t fit = plane_bytes ? ((size_t)2u << 30) / plane_bytes : 0;
         if (fit < 2) c->la_enabled = false; else if (fit < c->la_max) c->la_max = (u32)fit;
     }
     ok();
-    return c;
+    return c.release();
 }
 
 // In-process multi-device context: n sharded sub-contexts (device r renders row blocks b = r mod n), one RCCL
@@ -514,47 +574,48 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
     if (!g_rccl.load(err)) { fail(MRT_ERR_DEVICE, "mrt_create: %s", err.c_str()); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || (u32)ndev < n) { fail(MRT_ERR_DEVICE, "mrt_create: n_devices = %u but %d HIP device(s) are visible", n, ndev); return nullptr; }
-    mrt_ctx *g = new mrt_ctx();
+    std::unique_ptr<mrt_ctx> g(new mrt_ctx());              // every failure below: the context is destroyed with what it holds
     const int rc = pack_scene(desc, g->pk, err);
-    if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); delete g; return nullptr; }
+    if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); return nullptr; }
     g->device = 0; g->seed = opts->seed;
     g->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || env_on("MRT_DEFER");
     g->shard_count = 1; g->shard_index = 0; g->shard_rows = opts->shard_rows ? opts->shard_rows : 8;
     g->local_rows = g->pk.nh; g->padded_rows = g->pk.nh;
     for (u32 y = 0; y < g->pk.nh; ++y) g->row_of.push_back(y);
+    g->group.reset(new Group());
+    Group &gr = *g->group;
     for (u32 r = 0; r < n; ++r) {
         mrt_opts o = *opts;
         o.n_devices = 0; o.device = (int)r; o.shard_index = r; o.shard_count = n; o.shard_rows = g->shard_rows;
         o.flags &= ~MRT_FLAG_DEFER;                   // the group defers, not its shards
-        mrt_ctx *sub = create_single(desc, &o);
-        if (!sub) { free_ctx(g); return nullptr; }
-        g->subs.push_back(sub);
+        gr.subs.emplace_back(create_single(desc, &o));
+        if (!gr.subs.back()) return nullptr;
     }
-    auto bail = [&](const char *what, const char *why) { fail(MRT_ERR_DEVICE, "mrt_create: %s: %s", what, why); free_ctx(g); return (mrt_ctx *)nullptr; };
+    auto bail = [&](const char *what, const char *why) { fail(MRT_ERR_DEVICE, "mrt_create: %s: %s", what, why); return (mrt_ctx *)nullptr; };
     hipError_t e;
     if ((e = hipSetDevice(0)) != hipSuccess) return bail("hipSetDevice", hipGetErrorString(e));
-    if ((e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", hipGetErrorString(e));
-    if ((e = hipEventCreate(&g->ev0)) != hipSuccess || (e = hipEventCreate(&g->ev1)) != hipSuccess) return bail("hipEventCreate", hipGetErrorString(e));
-    const u32 pr = g->subs[0]->padded_rows, nw = g->pk.nw, nh = g->pk.nh;
-    const size_t plane = plane_floats(g->subs[0]);
-    if ((e = hipMalloc((void **)&g->d_full, (size_t)nh * nw * 3 * sizeof(float))) != hipSuccess) return bail("hipMalloc(frame)", hipGetErrorString(e));
-    if ((e = hipMemset(g->d_full, 0, (size_t)nh * nw * 3 * sizeof(float))) != hipSuccess) return bail("hipMemset", hipGetErrorString(e));
-    if ((e = hipMalloc((void **)&g->d_gather, plane * n * sizeof(float))) != hipSuccess) return bail("hipMalloc(gather)", hipGetErrorString(e));
+    if ((e = create(g->stream)) != hipSuccess) return bail("hipStreamCreate", hipGetErrorString(e));
+    if ((e = create(g->ev0)) != hipSuccess || (e = create(g->ev1)) != hipSuccess) return bail("hipEventCreate", hipGetErrorString(e));
+    const u32 pr = gr.subs[0]->padded_rows, nw = g->pk.nw, nh = g->pk.nh;
+    const size_t plane = plane_floats(gr.subs[0].get());
+    if ((e = g->full.alloc((size_t)nh * nw * 3)) != hipSuccess) return bail("hipMalloc(frame)", hipGetErrorString(e));
+    if ((e = hipMemset(g->full.p, 0, (size_t)nh * nw * 3 * sizeof(float))) != hipSuccess) return bail("hipMemset", hipGetErrorString(e));
+    if ((e = gr.gather.alloc(plane * n)) != hipSuccess) return bail("hipMalloc(gather)", hipGetErrorString(e));
     std::vector<u32> rowmap((size_t)n * pr, 0xffffffffu);
-    for (u32 r = 0; r < n; ++r) for (u32 i = 0; i < g->subs[r]->local_rows; ++i) rowmap[(size_t)r * pr + i] = g->subs[r]->row_of[i];
-    if ((e = hipMalloc((void **)&g->d_rowmap, rowmap.size() * sizeof(u32))) != hipSuccess) return bail("hipMalloc(rowmap)", hipGetErrorString(e));
-    if ((e = hipMemcpy(g->d_rowmap, rowmap.data(), rowmap.size() * sizeof(u32), hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(rowmap)", hipGetErrorString(e));
+    for (u32 r = 0; r < n; ++r) for (u32 i = 0; i < gr.subs[r]->local_rows; ++i) rowmap[(size_t)r * pr + i] = gr.subs[r]->row_of[i];
+    if ((e = gr.rowmap.alloc(rowmap.size())) != hipSuccess) return bail("hipMalloc(rowmap)", hipGetErrorString(e));
+    if ((e = hipMemcpy(gr.rowmap.p, rowmap.data(), rowmap.size() * sizeof(u32), hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(rowmap)", hipGetErrorString(e));
     std::vector<int> devs(n);
     for (u32 r = 0; r < n; ++r) devs[r] = (int)r;
-    g->comms.assign(n, nullptr);
-    const int nrc = g_rccl.CommInitAll(g->comms.data(), (int)n, devs.data());
+    gr.comms.assign(n, nullptr);
+    const int nrc = g_rccl.CommInitAll(gr.comms.data(), (int)n, devs.data());
     if (nrc != 0) return bail("ncclCommInitAll", g_rccl.GetErrorString(nrc));
     g->P = g->pk.P;
     memset(&g->stats, 0, sizeof g->stats);
-    g->stats.block_threads = g->subs[0]->block_threads; g->stats.lds_bytes = g->subs[0]->stats.lds_bytes; g->stats.scene_bytes = g->subs[0]->stats.scene_bytes;
-    g->stats.kernel_features = g->subs[0]->stats.kernel_features; g->stats.scene_in_lds = g->subs[0]->stats.scene_in_lds;
+    g->stats.block_threads = gr.subs[0]->block_threads; g->stats.lds_bytes = gr.subs[0]->stats.lds_bytes; g->stats.scene_bytes = gr.subs[0]->stats.scene_bytes;
+    g->stats.kernel_features = gr.subs[0]->stats.kernel_features; g->stats.scene_in_lds = gr.subs[0]->stats.scene_in_lds;
     ok();
-    return g;
+    return g.release();
 }
 
 mrt_ctx *mrt_create(const mrt_render_desc *desc, const mrt_opts *opts)
@@ -572,7 +633,7 @@ mrt_ctx *mrt_create(const mrt_render_desc *desc, const mrt_opts *opts)
     return create_single(desc, opts);
 }
 
-void mrt_destroy(mrt_ctx *ctx) { free_ctx(ctx); }
+void mrt_destroy(mrt_ctx *ctx) { delete ctx; }
 
 // Lazy half of the per-execute statistics: HIP-event times and (MRT_FLAG_COUNT_SEGMENTS) the segment counter are read
 // back when somebody asks (mrt_get_stats), not on every mrt_execute -- the reference's callers run one pass per call
@@ -586,26 +647,26 @@ static int resolve_stats(mrt_ctx *c)
     double k = 0, r = 0;
     for (u32 i = 0; i + 2u < c->ev_used; i += 3u) {
         float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, c->evs[i], c->evs[i + 1]));
-        HIP_TRY(hipEventElapsedTime(&b, c->evs[i + 1], c->evs[i + 2]));
+        HIP_TRY(hipEventElapsedTime(&a, c->evs[i].get(), c->evs[i + 1].get()));
+        HIP_TRY(hipEventElapsedTime(&b, c->evs[i + 1].get(), c->evs[i + 2].get()));
         k += a; r += b;
     }
     c->stats.kernel_ms = k;
     c->stats.reduce_ms = c->stats.k_split > 1u ? r : 0.0;
     if (c->count_segments) {
         unsigned long long seg = 0;
-        HIP_TRY(hipMemcpy(&seg, c->d_segments, sizeof seg, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&seg, c->segments.p, sizeof seg, hipMemcpyDeviceToHost));
         c->stats.segments = seg;
     }
     if (c->debug_fallbacks) {
         unsigned long long t[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpy(t, c->d_segments + 5, sizeof t, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t, c->segments.p + 5, sizeof t, hipMemcpyDeviceToHost));
         fprintf(stderr, "[mrt fallbacks] since mrt_create: NaN directions (shortcut) %llu, walk area full %llu, rays the triangle BVH may not cull %llu\n", t[0], t[1], t[2]);
     }
 #ifdef MRT_PHASE_TIMING
     {   // debug build: shader-clock ticks per phase, summed over wavefronts since the context was created
         unsigned long long t[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpy(t, c->d_segments + 2, sizeof t, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t, c->segments.p + 2, sizeof t, hipMemcpyDeviceToHost));
         const double tot = (double)(t[0] + t[1] + t[2] + t[3]);
         fprintf(stderr, "[mrt phase ticks] closest-hit query %.3f  shading %.3f  shadow query %.3f  ray set-up / regeneration %.3f  (total %.4g wave-ticks)\n",
                 t[0] / tot, t[1] / tot, t[2] / tot, t[3] / tot, tot);
@@ -636,12 +697,7 @@ static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks,
         while (cap > k_split && plane * cap * sizeof(float) > budget) cap /= 2u;
         const size_t need = plane * (n_chunks < cap ? n_chunks : cap);
         if (need * sizeof(float) > budget) k_split = 1u;                       // not even k_split planes fit: one lane per pixel
-        else if (need > c->partial_floats) {
-            if (c->d_partial) { (void)hipFree(c->d_partial); c->d_partial = nullptr; c->partial_floats = 0; }
-            const size_t ask = c->knob_partial_fail ? ((size_t)1 << 60) : need * sizeof(float);
-            if (!hip_tolerated(hipMalloc((void **)&c->d_partial, ask))) { c->d_partial = nullptr; k_split = 1u; }
-            else c->partial_floats = need;
-        }
+        else if (need > c->partial.n && !hip_tolerated(c->partial.alloc(need, c->knob_partial_fail ? (size_t)1 << 60 : 0))) k_split = 1u;
     }
     if (planes && k_split < 2u) return fail(MRT_ERR_LIMIT, "mrt_execute_adaptive: no memory for the chunk planes of a round");
     return MRT_OK;
@@ -671,7 +727,7 @@ static int launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *
     int rc = split_policy(c, wave_tiles, n_chunks, planes, k_split, cap);
     if (rc) return rc;
     const size_t plane = plane_floats(c);
-    c->P.partial = c->d_partial;
+    c->P.partial = c->partial.p;
     c->P.partial_stride = plane;
     const u32 s_end = base + n;
     while (base < s_end) {
@@ -689,15 +745,15 @@ static int launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *
         c->P.sample_base = base;
         c->P.k_split = ks;
         if (ks > ks_max) ks_max = ks;
-        while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->evs.push_back(e); }
-        hipEvent_t *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
+        while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { Event e; HIP_TRY(create(e)); c->evs.push_back(std::move(e)); }
+        const Event *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
         c->P.persist_grid = (c->small_plain_grid && stop - base < kChunk) ? 0u : c->persist_grid;
-        if ((rc = launch_trace(c, c->P, c->stream, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, tl))) return rc;
+        if ((rc = launch_trace(c, c->P, c->stream.get(), ev ? ev[0].get() : nullptr, ev ? ev[1].get() : nullptr, tl))) return rc;
         if (ks > 1u) {
-            if (tl) HIP_TRY(launch_reduce_chunks_listed(c->d_accum, half, c->d_partial, tl->tiles, tl->n, c->pk.nw, c->pk.nh, plane, nc, c->stream));
-            else HIP_TRY(launch_reduce_chunks(c->d_accum, c->d_partial, (size_t)c->local_rows * c->pk.nw * 3, plane, nc, c->stream));
+            if (tl) HIP_TRY(launch_reduce_chunks_listed(c->d_accum, half, c->partial.p, tl->tiles, tl->n, c->pk.nw, c->pk.nh, plane, nc, c->stream.get()));
+            else HIP_TRY(launch_reduce_chunks(c->d_accum, c->partial.p, (size_t)c->local_rows * c->pk.nw * 3, plane, nc, c->stream.get()));
         }
-        if (ev) { HIP_TRY(hipEventRecord(ev[2], c->stream)); c->ev_used += 3u; }
+        if (ev) { HIP_TRY(hipEventRecord(ev[2].get(), c->stream.get())); c->ev_used += 3u; }
         c->stats.launches += 1u;
         base = stop;
     }
@@ -718,7 +774,7 @@ static int exec_launch(mrt_ctx *c, uint32_t n_samples)
     if (rc) return rc;
     reset_exec_stats(c);
     if (!(n_samples && c->local_rows)) return MRT_OK;
-    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
+    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->segments.p, 0, sizeof(unsigned long long), c->stream.get()));
     u32 ks_max = 0;                                  // (the uniform path reports the policy's k_split)
     if ((rc = launch_batch(c, c->count, n_samples, nullptr, nullptr, false, c->stats.k_split, ks_max))) return rc;
     c->stats.block_threads = c->block_threads;
@@ -732,7 +788,7 @@ static int exec_finish(mrt_ctx *c, uint32_t n_samples)
     int rc = set_device(c);
     if (rc) return rc;
     if (n_samples && c->local_rows) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream.get()));
         c->stats.samples = (uint64_t)c->local_rows * c->pk.nw * n_samples;
         c->stats_pending = true;
     }
@@ -742,59 +798,60 @@ static int exec_finish(mrt_ctx *c, uint32_t n_samples)
 
 static int exec_group(mrt_ctx *g, uint32_t n_samples)
 {
-    const u32 n = (u32)g->subs.size();
+    Group &gr = *g->group;
+    const u32 n = (u32)gr.subs.size();
     int rc = MRT_OK;
     u32 launched = 0;
-    for (; launched < n; ++launched) if ((rc = exec_launch(g->subs[launched], n_samples))) break;
+    for (; launched < n; ++launched) if ((rc = exec_launch(gr.subs[launched].get(), n_samples))) break;
     // an error from here on still waits for everything that was launched, so no kernel is left running on a buffer
     // the caller may free; the first error is the one reported
-    auto drain = [&](u32 upto) { for (u32 r = 0; r < upto; ++r) { if (hipSetDevice(g->subs[r]->device) == hipSuccess) (void)hipStreamSynchronize(g->subs[r]->stream); } (void)hipGetLastError(); };
-    if (rc) { const std::string keep = g_err; drain(launched + (launched < n ? 1u : 0u)); g_err = keep; g_status = rc; return rc; }
+    auto drain = [&](u32 upto) { for (u32 r = 0; r < upto; ++r) { if (hipSetDevice(gr.subs[r]->device) == hipSuccess) (void)hipStreamSynchronize(gr.subs[r]->stream.get()); } (void)hipGetLastError(); };
+    if (rc) return keep_first_error(rc, [&] { drain(launched + (launched < n ? 1u : 0u)); });
     // one gather per batch: rank r sends its padded shard accumulator, device 0 receives rank i at offset i * plane.
     // gather_ms is device time, not host time around asynchronous launches: every sub-stream records an event after its
     // kernels (before its part of the gather) and one after it; the slowest stream's interval plus scatter_rows is the
     // exchange.  A rank whose kernels finish early waits inside the collective for the slowest one, so the figure is an
     // upper bound of the transfer itself; kernel_ms (the slowest rank's kernels) is reported next to it.
-    const size_t plane = plane_floats(g->subs[0]);
+    const size_t plane = plane_floats(gr.subs[0].get());
     hipError_t he = hipSuccess;
     for (u32 r = 0; r < n && he == hipSuccess; ++r) {
-        mrt_ctx *s = g->subs[r];
+        mrt_ctx *s = gr.subs[r].get();
         if ((he = hipSetDevice(s->device)) != hipSuccess) break;
-        if (!s->ev_g0 && (he = hipEventCreate(&s->ev_g0)) != hipSuccess) break;
-        if (!s->ev_g1 && (he = hipEventCreate(&s->ev_g1)) != hipSuccess) break;
-        he = hipEventRecord(s->ev_g0, s->stream);
+        if (!s->ev_g0 && (he = create(s->ev_g0)) != hipSuccess) break;
+        if (!s->ev_g1 && (he = create(s->ev_g1)) != hipSuccess) break;
+        he = hipEventRecord(s->ev_g0.get(), s->stream.get());
     }
     int nrc = he == hipSuccess ? g_rccl.GroupStart() : 0;
     if (he == hipSuccess && nrc == 0) {
         for (u32 r = 0; r < n && nrc == 0 && he == hipSuccess; ++r) {
-            if ((he = hipSetDevice(g->subs[r]->device)) != hipSuccess) break;
-            nrc = g_rccl.Gather(g->subs[r]->d_accum, r == 0 ? g->d_gather : nullptr, plane, kNcclFloat, 0, g->comms[r], g->subs[r]->stream);
+            if ((he = hipSetDevice(gr.subs[r]->device)) != hipSuccess) break;
+            nrc = g_rccl.Gather(gr.subs[r]->d_accum, r == 0 ? gr.gather.p : nullptr, plane, kNcclFloat, 0, gr.comms[r], gr.subs[r]->stream.get());
         }
         const int nrc2 = g_rccl.GroupEnd();                         // always closed, whatever happened inside the group
         if (nrc == 0) nrc = nrc2;
     }
     for (u32 r = 0; r < n && he == hipSuccess && nrc == 0; ++r) {
-        if ((he = hipSetDevice(g->subs[r]->device)) != hipSuccess) break;
-        he = hipEventRecord(g->subs[r]->ev_g1, g->subs[r]->stream);
+        if ((he = hipSetDevice(gr.subs[r]->device)) != hipSuccess) break;
+        he = hipEventRecord(gr.subs[r]->ev_g1.get(), gr.subs[r]->stream.get());
     }
     if (he != hipSuccess || nrc != 0) {
         drain(n);
         if (he != hipSuccess) return fail(MRT_ERR_DEVICE, "HIP call failed around the gather group: %s", hipGetErrorString(he));
         return fail(MRT_ERR_DEVICE, "ncclGather: %s", g_rccl.GetErrorString(nrc));
     }
-    for (mrt_ctx *s : g->subs) if ((rc = exec_finish(s, n_samples))) { const std::string keep = g_err; drain(n); g_err = keep; g_status = rc; return rc; }    // syncs every stream (kernel + gather)
+    for (auto &s : gr.subs) if ((rc = exec_finish(s.get(), n_samples))) return keep_first_error(rc, [&] { drain(n); });    // syncs every stream (kernel + gather)
     HIP_TRY(hipSetDevice(g->device));
-    HIP_TRY(hipEventRecord(g->ev0, g->stream));
-    HIP_TRY(launch_scatter_rows(g->d_full, g->d_gather, g->d_rowmap, n * g->subs[0]->padded_rows, g->pk.nw * 3u, g->stream));
-    HIP_TRY(hipEventRecord(g->ev1, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipEventRecord(g->ev0.get(), g->stream.get()));
+    HIP_TRY(launch_scatter_rows(g->full.p, gr.gather.p, gr.rowmap.p, n * gr.subs[0]->padded_rows, g->pk.nw * 3u, g->stream.get()));
+    HIP_TRY(hipEventRecord(g->ev1.get(), g->stream.get()));
+    HIP_TRY(hipStreamSynchronize(g->stream.get()));
     g->count += n_samples;
     g->full_count = g->count;
     memset(&g->stats, 0, offsetof(mrt_stats, lds_bytes));
     g->stats.reduce_ms = 0;
     double gather_ms = 0;
-    for (mrt_ctx *s : g->subs) {
-        if ((rc = resolve_stats(s))) return rc;
+    for (const auto &s : gr.subs) {
+        if ((rc = resolve_stats(s.get()))) return rc;
         if (s->stats.kernel_ms > g->stats.kernel_ms) g->stats.kernel_ms = s->stats.kernel_ms;
         if (s->stats.reduce_ms > g->stats.reduce_ms) g->stats.reduce_ms = s->stats.reduce_ms;
         g->stats.samples += s->stats.samples; g->stats.segments += s->stats.segments; g->stats.launches += s->stats.launches;
@@ -803,13 +860,13 @@ static int exec_group(mrt_ctx *g, uint32_t n_samples)
         // a sub-context without rows of its own (a frame of fewer row blocks than devices) or a call with n_samples == 0
         // still joined the gather, but exec_finish did not synchronise its stream: wait for its closing event here, or
         // hipEventElapsedTime answers hipErrorNotReady after the counts have been advanced
-        HIP_TRY(hipEventSynchronize(s->ev_g1));
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev_g0, s->ev_g1));
+        HIP_TRY(hipEventSynchronize(s->ev_g1.get()));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev_g0.get(), s->ev_g1.get()));
         if (ms > gather_ms) gather_ms = ms;
     }
     HIP_TRY(hipSetDevice(g->device));
-    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1)); gather_ms += ms; }      // + placing the rows into the frame
-    g->stats.k_split = g->subs[0]->stats.k_split;
+    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, g->ev0.get(), g->ev1.get())); gather_ms += ms; }      // + placing the rows into the frame
+    g->stats.k_split = gr.subs[0]->stats.k_split;
     g->stats.gather_ms = gather_ms;
     return MRT_OK;
 }
@@ -828,36 +885,35 @@ static int exec_group(mrt_ctx *g, uint32_t n_samples)
 // the work it has used; any other call (n != 1, reset, set_accum) drops what was traced ahead.
 static void la_drop(mrt_ctx *c)
 {
-    if (c->la_stream && (c->la_n[0] || c->la_n[1])) (void)hipStreamSynchronize(c->la_stream);
-    c->la_n[0] = c->la_n[1] = 0;
+    if (c->la && (c->la->n[0] || c->la->n[1])) (void)hipStreamSynchronize(c->la->stream.get());
+    if (c->la) c->la->n[0] = c->la->n[1] = 0;
     c->la_streak = 0;
 }
 
-// launch the trace of samples [base, base + n) into plane set i (asynchronous, on la_stream)
+// launch the trace of samples [base, base + n) into plane set i (asynchronous, on the look-ahead stream, created by the first call)
 static int la_launch(mrt_ctx *c, int i, u32 base, u32 n)
 {
     const size_t plane = plane_floats(c);
-    if (!c->la_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->la_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) { HIP_TRY(hipEventCreate(&c->la_ev0[k])); HIP_TRY(hipEventCreate(&c->la_ev1[k])); }
-        HIP_TRY(hipMalloc((void **)&c->d_la_counter, sizeof(u32)));
+    if (!c->la) {
+        std::unique_ptr<Lookahead> la(new Lookahead());
+        HIP_TRY(create(la->stream));
+        for (int k = 0; k < 2; ++k) { HIP_TRY(create(la->ev0[k])); HIP_TRY(create(la->ev1[k])); }
+        HIP_TRY(la->counter.alloc(1));
+        c->la = std::move(la);
     }
-    if (plane * n > c->la_floats[i]) {
-        if (c->d_la[i]) { (void)hipFree(c->d_la[i]); c->d_la[i] = nullptr; c->la_floats[i] = 0; }
-        if (!hip_tolerated(hipMalloc((void **)&c->d_la[i], plane * n * sizeof(float)))) { c->d_la[i] = nullptr; return MRT_ERR_LIMIT; }     // the caller falls back
-        c->la_floats[i] = plane * n;
-    }
+    Lookahead &la = *c->la;
+    if (plane * n > la.planes[i].n && !hip_tolerated(la.planes[i].alloc(plane * n))) return MRT_ERR_LIMIT;     // the caller falls back
     Params P = c->P;
     P.n_samples = n; P.sample_base = base; P.k_split = 1u; P.to_planes = 1u;
-    P.partial = c->d_la[i]; P.partial_stride = plane;
+    P.partial = la.planes[i].p; P.partial_stride = plane;
     P.count_segments = 0u;
     // small scenes: the plain grid (their persistent grid fills every wave slot of the chip and would keep the folds out until
     // the launch has ended); larger ones leave slots free and keep their persistent workgroups, with a tile counter of their own
     P.persist_grid = c->small_plain_grid ? 0u : c->persist_grid;
-    P.tile_counter = c->d_la_counter;
-    const int rc = launch_trace(c, P, c->la_stream, c->la_ev0[i], c->la_ev1[i], nullptr);
+    P.tile_counter = la.counter.p;
+    const int rc = launch_trace(c, P, la.stream.get(), la.ev0[i].get(), la.ev1[i].get(), nullptr);
     if (rc) return rc;
-    c->la_base[i] = base; c->la_n[i] = n;
+    la.base[i] = base; la.n[i] = n;
     return MRT_OK;
 }
 
@@ -871,7 +927,7 @@ static int run_lookahead(mrt_ctx *c)
     if (rc) return rc;
     const u32 k = c->count;
     int s = -1;
-    for (int i = 0; i < 2; ++i) if (c->la_n[i] && k >= c->la_base[i] && k < c->la_base[i] + c->la_n[i]) s = i;
+    if (c->la) for (int i = 0; i < 2; ++i) if (c->la->n[i] && k >= c->la->base[i] && k < c->la->base[i] + c->la->n[i]) s = i;
     if (s < 0) {
         // nothing traced ahead for this sample (first use, or what was ahead has been dropped): start both sets
         la_drop(c);
@@ -880,14 +936,15 @@ static int run_lookahead(mrt_ctx *c)
         const u32 n1 = 2u * n0 < c->la_max ? 2u * n0 : c->la_max;
         if ((unsigned long long)k + n0 + n1 > 0xffffffffull) return kLaPlain;      // (a set's base + n must not wrap)
         if ((rc = la_launch(c, 0, k, n0))) return rc;
-        if ((rc = la_launch(c, 1, k + n0, n1))) { (void)hipStreamSynchronize(c->la_stream); c->la_n[0] = c->la_n[1] = 0; return rc; }
+        if ((rc = la_launch(c, 1, k + n0, n1))) { (void)hipStreamSynchronize(c->la->stream.get()); c->la->n[0] = c->la->n[1] = 0; return rc; }
         s = 0;
     }
+    Lookahead &la = *c->la;
     const size_t plane = plane_floats(c);
     const size_t words = (size_t)c->local_rows * c->pk.nw * 3;
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->la_ev1[s], 0));
-    HIP_TRY(launch_reduce_chunks(c->d_accum, c->d_la[s] + (size_t)(k - c->la_base[s]) * plane, words, plane, 1u, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                // the fold has run, so the set's launch has ended too
+    HIP_TRY(hipStreamWaitEvent(c->stream.get(), la.ev1[s].get(), 0));
+    HIP_TRY(launch_reduce_chunks(c->d_accum, la.planes[s].p + (size_t)(k - la.base[s]) * plane, words, plane, 1u, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));                // the fold has run, so the set's launch has ended too
     c->count += 1u;
     reset_exec_stats(c);
     c->stats.launches = 1u; c->stats.k_split = 1u;
@@ -895,15 +952,15 @@ static int run_lookahead(mrt_ctx *c)
     c->stats.block_threads = c->block_threads;
     if (c->event_timing) {
         float ms = 0;
-        if (hip_tolerated(hipEventElapsedTime(&ms, c->la_ev0[s], c->la_ev1[s]))) c->stats.kernel_ms = (double)ms / (double)c->la_n[s];   // this sample's share of its launch
+        if (hip_tolerated(hipEventElapsedTime(&ms, la.ev0[s].get(), la.ev1[s].get()))) c->stats.kernel_ms = (double)ms / (double)la.n[s];   // this sample's share of its launch
     }
-    if (k + 1u == c->la_base[s] + c->la_n[s]) {
+    if (k + 1u == la.base[s] + la.n[s]) {
         // the set is spent (its last plane has been folded): the next launch goes into it, behind the other set's, twice as long
         const int o = 1 - s;
-        const unsigned long long nb = (unsigned long long)c->la_base[o] + c->la_n[o];
-        const u32 nn = 2u * c->la_n[o] < c->la_max ? 2u * c->la_n[o] : c->la_max;
-        c->la_n[s] = 0;
-        if (c->la_n[o] && nb + nn <= 0xffffffffull) (void)la_launch(c, s, (u32)nb, nn);      // (a failure here only means a later call starts over)
+        const unsigned long long nb = (unsigned long long)la.base[o] + la.n[o];
+        const u32 nn = 2u * la.n[o] < c->la_max ? 2u * la.n[o] : c->la_max;
+        la.n[s] = 0;
+        if (la.n[o] && nb + nn <= 0xffffffffull) (void)la_launch(c, s, (u32)nb, nn);      // (a failure here only means a later call starts over)
     }
     return MRT_OK;
 }
@@ -911,7 +968,7 @@ static int run_lookahead(mrt_ctx *c)
 static int run_samples(mrt_ctx *c, uint32_t n_samples)
 {
     int rc;
-    if (!c->subs.empty()) return exec_group(c, n_samples);
+    if (c->group) return exec_group(c, n_samples);
     if (c->la_enabled && n_samples == 1u && c->local_rows) {
         if (c->la_streak >= 2u) {
             rc = run_lookahead(c);
@@ -920,7 +977,7 @@ static int run_samples(mrt_ctx *c, uint32_t n_samples)
         } else {
             ++c->la_streak;
         }
-    } else if (c->la_n[0] || c->la_n[1] || c->la_streak) {
+    } else {
         la_drop(c);
     }
     if ((rc = exec_launch(c, n_samples))) return rc;
@@ -937,6 +994,13 @@ static int settle(mrt_ctx *c)
     return run_samples(c, n);
 }
 constexpr u32 kDeferLimit = 1024u;        // booked samples that trigger a launch by themselves (one full-size batch)
+
+// the prologue of the entry points that observe or replace the accumulator: the context's device, then what was booked
+static int enter(mrt_ctx *c)
+{
+    const int rc = set_device(c);
+    return rc ? rc : settle(c);
+}
 
 int mrt_execute(mrt_ctx *c, uint32_t n_samples, double *seconds)
 {
@@ -964,18 +1028,24 @@ static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
 {
     const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u, n_ty = (nh + 7u) / 8u, n_tiles = n_tx * n_ty;
     const size_t acc_floats = plane_floats(c);
-    if (!c->d_half) HIP_TRY(hipMalloc((void **)&c->d_half, acc_floats * sizeof(float)));
-    if (!c->d_adapt) HIP_TRY(hipMalloc((void **)&c->d_adapt, (5u * (size_t)n_tiles + 1u) * sizeof(u32)));
-    u32 *lists[2] = {c->d_adapt, c->d_adapt + n_tiles};
-    u32 *keep = c->d_adapt + 2u * (size_t)n_tiles, *tcount = c->d_adapt + 3u * (size_t)n_tiles, *tconv = c->d_adapt + 4u * (size_t)n_tiles;
-    u32 *d_n = c->d_adapt + 5u * (size_t)n_tiles;
+    if (!c->ad) {
+        std::unique_ptr<Adaptive> ad(new Adaptive());
+        HIP_TRY(ad->half.alloc(acc_floats));
+        HIP_TRY(ad->tiles.alloc(5u * (size_t)n_tiles + 1u));
+        ad->n_tiles = n_tiles;
+        c->ad = std::move(ad);
+    }
+    Adaptive &ad = *c->ad;
+    u32 *lists[2] = {ad.tiles.p, ad.tiles.p + n_tiles};
+    u32 *keep = ad.tiles.p + 2u * (size_t)n_tiles, *tcount = ad.counts(), *tconv = ad.tiles.p + 4u * (size_t)n_tiles;
+    u32 *d_n = ad.tiles.p + 5u * (size_t)n_tiles;
     std::vector<u32> all(n_tiles);
     for (u32 t = 0; t < n_tiles; ++t) all[t] = t;
     HIP_TRY(hipMemcpy(lists[0], all.data(), n_tiles * sizeof(u32), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(c->d_accum, 0, acc_floats * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_half, 0, acc_floats * sizeof(float), c->stream));
-    HIP_TRY(hipMemsetAsync(tcount, 0, 2u * (size_t)n_tiles * sizeof(u32), c->stream));
-    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->d_segments, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_accum, 0, acc_floats * sizeof(float), c->stream.get()));
+    HIP_TRY(hipMemsetAsync(ad.half.p, 0, acc_floats * sizeof(float), c->stream.get()));
+    HIP_TRY(hipMemsetAsync(tcount, 0, 2u * (size_t)n_tiles * sizeof(u32), c->stream.get()));
+    if (c->count_segments) HIP_TRY(hipMemsetAsync(c->segments.p, 0, sizeof(unsigned long long), c->stream.get()));
     u32 n_active = n_tiles, n = 0, rounds = 0, cur = 0;
     while (n_active) {
         for (int r = 0; r < 2; ++r, ++rounds, n += a->step) {
@@ -984,27 +1054,27 @@ static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
             const bool even = (rounds & 1u) == 0u;
             const TileList tl{lists[cur], n_active};
             u32 k_split = 1;
-            const int rc = launch_batch(c, n, a->step, &tl, even ? c->d_half : nullptr, even, k_split, c->stats.k_split);
+            const int rc = launch_batch(c, n, a->step, &tl, even ? ad.half.p : nullptr, even, k_split, c->stats.k_split);
             if (rc) return rc;
         }
         if (n < a->min_samples) continue;
         // the stop rule at count n for every tile still running; the next list, and its length (the one read-back of a step)
-        HIP_TRY(launch_adapt_eval(c->d_accum, c->d_half, lists[cur], n_active, nw, nh, n, a->threshold, n >= a->max_samples, keep, tcount, tconv,
-                                  lists[cur ^ 1u], d_n, c->stream));
-        HIP_TRY(hipMemcpyAsync(&n_active, d_n, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(launch_adapt_eval(c->d_accum, ad.half.p, lists[cur], n_active, nw, nh, n, a->threshold, n >= a->max_samples, keep, tcount, tconv,
+                                  lists[cur ^ 1u], d_n, c->stream.get()));
+        HIP_TRY(hipMemcpyAsync(&n_active, d_n, sizeof(u32), hipMemcpyDeviceToHost, c->stream.get()));
+        HIP_TRY(hipStreamSynchronize(c->stream.get()));
         cur ^= 1u;
     }
     std::vector<u32> conv(n_tiles);
-    c->tile_count.assign(n_tiles, 0u);
-    HIP_TRY(hipMemcpy(c->tile_count.data(), tcount, n_tiles * sizeof(u32), hipMemcpyDeviceToHost));
+    ad.tile_count.assign(n_tiles, 0u);
+    HIP_TRY(hipMemcpy(ad.tile_count.data(), tcount, n_tiles * sizeof(u32), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(conv.data(), tconv, n_tiles * sizeof(u32), hipMemcpyDeviceToHost));
     uint64_t samples = 0;
     u32 lo = 0xffffffffu, hi = 0, n_conv = 0;
     for (u32 t = 0; t < n_tiles; ++t) {
         const u32 ty = t / n_tx, tx = t - ty * n_tx;
         const u32 px = ((nw - tx * 8u) < 8u ? nw - tx * 8u : 8u) * ((nh - ty * 8u) < 8u ? nh - ty * 8u : 8u);
-        const u32 k = c->tile_count[t];
+        const u32 k = ad.tile_count[t];
         samples += (uint64_t)k * px;
         lo = k < lo ? k : lo;
         hi = k > hi ? k : hi;
@@ -1038,8 +1108,8 @@ int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, d
         return fail(MRT_ERR_ARG, "mrt_execute_adaptive: min_samples %u and max_samples %u must be positive multiples of 2 * step = %llu", a->min_samples, a->max_samples, two);
     if (a->min_samples > a->max_samples) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: min_samples %u > max_samples %u", a->min_samples, a->max_samples);
     if (!(a->threshold >= 0.0f)) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: threshold %g is not >= 0", (double)a->threshold);
-    if (!c->subs.empty() || c->shard_count > 1u) return fail(MRT_ERR_STATE, "mrt_execute_adaptive: sharded and multi-device contexts are not supported");
-    if (c->adaptive || c->count || c->pending || c->d_full)
+    if (c->group || c->shard_count > 1u) return fail(MRT_ERR_STATE, "mrt_execute_adaptive: sharded and multi-device contexts are not supported");
+    if (c->adaptive || c->count || c->pending || c->full.p)
         return fail(MRT_ERR_STATE, "mrt_execute_adaptive: the context holds samples (an adaptive render starts from none): mrt_reset first");
     const auto t0 = std::chrono::steady_clock::now();
     int rc = set_device(c);
@@ -1047,16 +1117,13 @@ int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, d
     la_drop(c);
     reset_exec_stats(c);
     c->stats.k_split = 1; c->stats.deferred = 0;
-    if ((rc = adapt_run(c, a, info))) {
-        // nothing half done stays behind: the context is an empty uniform one again
-        const std::string keep = g_err;
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float));
-        (void)hipGetLastError();
-        c->adaptive = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
-        g_err = keep; g_status = rc;
-        return rc;
-    }
+    if ((rc = adapt_run(c, a, info)))
+        return keep_first_error(rc, [&] {            // nothing half done stays behind: the context is an empty uniform one again
+            (void)hipStreamSynchronize(c->stream.get());
+            (void)hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float));
+            (void)hipGetLastError();
+            c->adaptive = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
+        });
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     ok();
     return MRT_OK;
@@ -1065,13 +1132,11 @@ int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, d
 int mrt_sample_counts(mrt_ctx *c, uint32_t *counts)
 {
     if (!c || !counts) return fail(MRT_ERR_ARG, "mrt_sample_counts: null argument");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
+    if (const int rc = enter(c)) return rc;
     const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u;
-    const u32 uniform = c->d_full ? c->full_count : c->count;
+    const u32 uniform = frame_of(c).count;
     for (u32 y = 0; y < nh; ++y)
-        for (u32 x = 0; x < nw; ++x) counts[(size_t)y * nw + x] = c->adaptive ? c->tile_count[(y / 8u) * n_tx + x / 8u] : uniform;
+        for (u32 x = 0; x < nw; ++x) counts[(size_t)y * nw + x] = c->adaptive ? c->ad->tile_count[(y / 8u) * n_tx + x / 8u] : uniform;
     ok();
     return MRT_OK;
 }
@@ -1080,9 +1145,8 @@ int mrt_adapt_half(mrt_ctx *c, float *rgb)
 {
     if (!c || !rgb) return fail(MRT_ERR_ARG, "mrt_adapt_half: null argument");
     if (!c->adaptive) return fail(MRT_ERR_STATE, "mrt_adapt_half: no adaptive render on this context since its last reset");
-    int rc = set_device(c);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(rgb, c->d_half, (size_t)c->pk.nw * c->pk.nh * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (const int rc = set_device(c)) return rc;
+    HIP_TRY(hipMemcpy(rgb, c->ad->half.p, (size_t)c->pk.nw * c->pk.nh * 3 * sizeof(float), hipMemcpyDeviceToHost));
     ok();
     return MRT_OK;
 }
@@ -1100,17 +1164,10 @@ int mrt_dims(const mrt_ctx *c, uint32_t *nw, uint32_t *nh, uint32_t *local_rows)
 int mrt_accum_local(mrt_ctx *c, float *rgb, uint32_t *rows)
 {
     if (!c) return fail(MRT_ERR_ARG, "mrt_accum_local: null context");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
-    if (!c->subs.empty()) {       // a multi-device context owns every row
-        if (rows) memcpy(rows, c->row_of.data(), sizeof(u32) * c->local_rows);
-        if (rgb) HIP_TRY(hipMemcpy(rgb, c->d_full, (size_t)c->pk.nh * c->pk.nw * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        ok();
-        return MRT_OK;
-    }
+    if (const int rc = enter(c)) return rc;
     if (rows) memcpy(rows, c->row_of.data(), sizeof(u32) * c->local_rows);
-    if (rgb && c->local_rows) HIP_TRY(hipMemcpy(rgb, c->d_accum, (size_t)c->local_rows * c->pk.nw * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    const float *src = c->group ? c->full.p : c->d_accum;         // a multi-device context owns every row
+    if (rgb && c->local_rows) HIP_TRY(hipMemcpy(rgb, src, (size_t)c->local_rows * c->pk.nw * 3 * sizeof(float), hipMemcpyDeviceToHost));
     ok();
     return MRT_OK;
 }
@@ -1118,22 +1175,16 @@ int mrt_accum_local(mrt_ctx *c, float *rgb, uint32_t *rows)
 int mrt_accum(mrt_ctx *c, float *rgb, uint32_t *count)
 {
     if (!c) return fail(MRT_ERR_ARG, "mrt_accum: null context");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
+    if (const int rc = enter(c)) return rc;
+    const Frame f = frame_of(c);
     const size_t row_bytes = (size_t)c->pk.nw * 3 * sizeof(float);
-    if (rgb) {
-        if (c->d_full) {
-            HIP_TRY(hipMemcpy(rgb, c->d_full, row_bytes * c->pk.nh, hipMemcpyDeviceToHost));
-        } else if (c->shard_count == 1) {
-            HIP_TRY(hipMemcpy(rgb, c->d_accum, row_bytes * c->pk.nh, hipMemcpyDeviceToHost));
-        } else {
-            std::vector<float> tmp((size_t)c->local_rows * c->pk.nw * 3);
-            if (c->local_rows) HIP_TRY(hipMemcpy(tmp.data(), c->d_accum, row_bytes * c->local_rows, hipMemcpyDeviceToHost));
-            for (u32 r = 0; r < c->local_rows; ++r) memcpy((char *)rgb + row_bytes * c->row_of[r], (char *)tmp.data() + row_bytes * r, row_bytes);
-        }
+    if (rgb && f.rgb) HIP_TRY(hipMemcpy(rgb, f.rgb, row_bytes * c->pk.nh, hipMemcpyDeviceToHost));
+    else if (rgb) {                           // a shard's own rows, in their places
+        std::vector<float> tmp((size_t)c->local_rows * c->pk.nw * 3);
+        if (c->local_rows) HIP_TRY(hipMemcpy(tmp.data(), c->d_accum, row_bytes * c->local_rows, hipMemcpyDeviceToHost));
+        for (u32 r = 0; r < c->local_rows; ++r) memcpy((char *)rgb + row_bytes * c->row_of[r], (char *)tmp.data() + row_bytes * r, row_bytes);
     }
-    if (count) *count = c->d_full ? c->full_count : c->count;
+    if (count) *count = f.count;
     ok();
     return MRT_OK;
 }
@@ -1141,9 +1192,9 @@ int mrt_accum(mrt_ctx *c, float *rgb, uint32_t *count)
 int mrt_accum_device_ptr(mrt_ctx *c, void **dev_ptr, size_t *bytes)
 {
     if (!c) return fail(MRT_ERR_ARG, "mrt_accum_device_ptr: null context");
-    { int rc = set_device(c); if (rc) return rc; if ((rc = settle(c))) return rc; }
+    if (const int rc = enter(c)) return rc;
     c->handed_out = true;                     // from now on the caller may read the accumulator behind the library's back (sticky)
-    if (dev_ptr) *dev_ptr = c->subs.empty() ? c->d_accum : c->d_full;
+    if (dev_ptr) *dev_ptr = c->group ? c->full.p : c->d_accum;
     if (bytes) *bytes = plane_floats(c) * sizeof(float);
     ok();
     return MRT_OK;
@@ -1160,12 +1211,10 @@ int mrt_padded_rows(const mrt_ctx *c, uint32_t *rows)
 int mrt_bind_accum(mrt_ctx *c, void *dev_ptr, size_t bytes)
 {
     if (!c) return fail(MRT_ERR_ARG, "mrt_bind_accum: null context");
-    if (!c->subs.empty()) return fail(MRT_ERR_STATE, "mrt_bind_accum: not available on a multi-device context");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
+    if (c->group) return fail(MRT_ERR_STATE, "mrt_bind_accum: not available on a multi-device context");
+    if (const int rc = enter(c)) return rc;
     const size_t need = plane_floats(c) * sizeof(float);
-    float *dst = dev_ptr ? (float *)dev_ptr : c->d_accum_own;
+    float *dst = dev_ptr ? (float *)dev_ptr : c->accum_own.p;
     if (dev_ptr && bytes < need) return fail(MRT_ERR_ARG, "mrt_bind_accum: buffer of %zu bytes, need %zu", bytes, need);     // nothing changed
     if (dst != c->d_accum) {
         HIP_TRY(hipMemcpy(dst, c->d_accum, need, hipMemcpyDeviceToDevice));
@@ -1177,55 +1226,47 @@ int mrt_bind_accum(mrt_ctx *c, void *dev_ptr, size_t bytes)
     return MRT_OK;
 }
 
-int mrt_set_accum_device(mrt_ctx *c, const void *dev_rgb, uint32_t count)
+// mrt_set_accum / mrt_set_accum_device on a single-device context: the whole frame into the accumulator, or, on a sharded
+// context, next to its own rows (only mrt_img and mrt_accum read it there)
+static int set_frame(mrt_ctx *c, const void *rgb, hipMemcpyKind kind, uint32_t count)
 {
-    if (!c || !dev_rgb) return fail(MRT_ERR_ARG, "mrt_set_accum_device: null argument");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
-    la_drop(c);                                   // the sample count changes under what was traced ahead
-    c->adaptive = false;
-    const size_t bytes = (size_t)c->pk.nw * c->pk.nh * 3 * sizeof(float);
-    if (!c->subs.empty()) return fail(MRT_ERR_STATE, "mrt_set_accum_device: use mrt_set_accum on a multi-device context");
+    const size_t floats = (size_t)c->pk.nw * c->pk.nh * 3;
     if (c->shard_count == 1) {
-        HIP_TRY(hipMemcpy(c->d_accum, dev_rgb, bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(c->d_accum, rgb, floats * sizeof(float), kind));
         c->count = count;
     } else {
-        if (!c->d_full) HIP_TRY(hipMalloc((void **)&c->d_full, bytes));
-        HIP_TRY(hipMemcpy(c->d_full, dev_rgb, bytes, hipMemcpyDeviceToDevice));
+        if (!c->full.p) HIP_TRY(c->full.alloc(floats));
+        HIP_TRY(hipMemcpy(c->full.p, rgb, floats * sizeof(float), kind));
         c->full_count = count;
     }
     ok();
     return MRT_OK;
 }
 
+int mrt_set_accum_device(mrt_ctx *c, const void *dev_rgb, uint32_t count)
+{
+    if (!c || !dev_rgb) return fail(MRT_ERR_ARG, "mrt_set_accum_device: null argument");
+    if (const int rc = enter(c)) return rc;
+    la_drop(c); c->adaptive = false;              // the sample count changes under what was traced ahead
+    if (c->group) return fail(MRT_ERR_STATE, "mrt_set_accum_device: use mrt_set_accum on a multi-device context");
+    return set_frame(c, dev_rgb, hipMemcpyDeviceToDevice, count);
+}
+
 int mrt_set_accum(mrt_ctx *c, const float *rgb, uint32_t count)
 {
     if (!c || !rgb) return fail(MRT_ERR_ARG, "mrt_set_accum: null argument");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
-    la_drop(c);
-    c->adaptive = false;
+    if (const int rc = enter(c)) return rc;
+    la_drop(c); c->adaptive = false;
+    if (!c->group) return set_frame(c, rgb, hipMemcpyHostToDevice, count);
     const size_t row_bytes = (size_t)c->pk.nw * 3 * sizeof(float);
-    if (!c->subs.empty()) {
-        HIP_TRY(hipMemcpy(c->d_full, rgb, row_bytes * c->pk.nh, hipMemcpyHostToDevice));
-        for (mrt_ctx *s : c->subs) {
-            HIP_TRY(hipSetDevice(s->device));
-            for (u32 i = 0; i < s->local_rows; ++i)
-                HIP_TRY(hipMemcpy((char *)s->d_accum + row_bytes * i, (const char *)rgb + row_bytes * s->row_of[i], row_bytes, hipMemcpyHostToDevice));
-            s->count = count;
-        }
-        c->count = count; c->full_count = count;
-    } else if (c->shard_count == 1) {
-        HIP_TRY(hipMemcpy(c->d_accum, rgb, row_bytes * c->pk.nh, hipMemcpyHostToDevice));
-        c->count = count;
-    } else {
-        // a sharded context keeps the gathered frame next to its own rows (it is only read by mrt_img / mrt_accum)
-        if (!c->d_full) HIP_TRY(hipMalloc((void **)&c->d_full, row_bytes * c->pk.nh));
-        HIP_TRY(hipMemcpy(c->d_full, rgb, row_bytes * c->pk.nh, hipMemcpyHostToDevice));
-        c->full_count = count;
+    HIP_TRY(hipMemcpy(c->full.p, rgb, row_bytes * c->pk.nh, hipMemcpyHostToDevice));
+    for (auto &s : c->group->subs) {
+        HIP_TRY(hipSetDevice(s->device));
+        for (u32 i = 0; i < s->local_rows; ++i)
+            HIP_TRY(hipMemcpy((char *)s->d_accum + row_bytes * i, (const char *)rgb + row_bytes * s->row_of[i], row_bytes, hipMemcpyHostToDevice));
+        s->count = count;
     }
+    c->count = count; c->full_count = count;
     ok();
     return MRT_OK;
 }
@@ -1236,93 +1277,88 @@ int mrt_reset(mrt_ctx *c)
     c->pending = 0;                           // booked samples of a deferred context are dropped with everything else
     int rc = set_device(c);
     if (rc) return rc;
-    la_drop(c);
-    c->adaptive = false;
-    if (!c->subs.empty()) {
-        for (mrt_ctx *s : c->subs) if ((rc = mrt_reset(s))) return rc;
+    la_drop(c); c->adaptive = false;
+    if (c->group) {
+        for (auto &s : c->group->subs) if ((rc = mrt_reset(s.get()))) return rc;
         HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipMemset(c->d_full, 0, (size_t)c->pk.nh * c->pk.nw * 3 * sizeof(float)));
-        c->count = 0; c->full_count = 0;
-        ok();
-        return MRT_OK;
+        HIP_TRY(hipMemset(c->full.p, 0, (size_t)c->pk.nh * c->pk.nw * 3 * sizeof(float)));
+    } else {
+        HIP_TRY(hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float)));
+        c->full.reset();
     }
-    HIP_TRY(hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float)));
-    if (c->d_full) { (void)hipFree(c->d_full); c->d_full = nullptr; }
     c->count = 0; c->full_count = 0;
     ok();
     return MRT_OK;
 }
 
+// The image buffers, created whole by the first call: a failure half-way leaves the context as it was, and the next call
+// starts over
 static int img_prepare(mrt_ctx *c)
 {
+    if (c->img) return MRT_OK;
     const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
-    if (!c->d_ss) HIP_TRY(hipMalloc((void **)&c->d_ss, (size_t)nw * nh * 3));
-    if (rw == nw && rh == nh) return MRT_OK;
-    if (rw == 0 || rh == 0) return fail(MRT_ERR_SCENE, "mrt_img: zero output resolution");
-    if (!c->d_out) {
-        // everything is allocated and filled through locals and committed to the context only when all of it succeeded: a
-        // failure half-way leaves the context as it was (d_out still null), so the next mrt_img starts over instead of
-        // allocating over live pointers
+    const bool resize = rw != nw || rh != nh;
+    if (resize && (rw == 0 || rh == 0)) return fail(MRT_ERR_SCENE, "mrt_img: zero output resolution");
+    std::unique_ptr<Image> im(new Image());
+    const int rc = [&]() -> int {
+        HIP_TRY(im->ss.alloc((size_t)nw * nh * 3));
+        if (!resize) return MRT_OK;
         ResampleTaps v, h;
         lanczos3_taps(nh, rh, v);
         lanczos3_taps(nw, rw, h);
-        u32 *vl = nullptr, *vc = nullptr, *hl = nullptr, *hc = nullptr;
-        float *vw = nullptr, *hw = nullptr, *tmp = nullptr;
-        unsigned char *out = nullptr;
-        auto build = [&]() -> int {
-            HIP_TRY(hipMalloc((void **)&vl, sizeof(u32) * rh));
-            HIP_TRY(hipMalloc((void **)&vc, sizeof(u32) * rh));
-            HIP_TRY(hipMalloc((void **)&vw, sizeof(float) * (size_t)rh * v.cap));
-            HIP_TRY(hipMalloc((void **)&hl, sizeof(u32) * rw));
-            HIP_TRY(hipMalloc((void **)&hc, sizeof(u32) * rw));
-            HIP_TRY(hipMalloc((void **)&hw, sizeof(float) * (size_t)rw * h.cap));
-            HIP_TRY(hipMemcpy(vl, v.left.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(vc, v.count.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(vw, v.weight.data(), sizeof(float) * (size_t)rh * v.cap, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(hl, h.left.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(hc, h.count.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(hw, h.weight.data(), sizeof(float) * (size_t)rw * h.cap, hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc((void **)&tmp, sizeof(float) * (size_t)nw * rh * 3));
-            HIP_TRY(hipMalloc((void **)&out, (size_t)rw * rh * 3));
-            return MRT_OK;
-        };
-        const int rc = build();
-        if (rc) {
-            void *ptrs[] = {vl, vc, vw, hl, hc, hw, tmp, out};
-            for (void *q : ptrs) if (q) (void)hipFree(q);
-            (void)hipGetLastError();
-            return rc;
-        }
-        c->vcap = v.cap; c->hcap = h.cap;
-        c->d_vl = vl; c->d_vc = vc; c->d_vw = vw; c->d_hl = hl; c->d_hc = hc; c->d_hw = hw; c->d_tmp = tmp; c->d_out = out;
-    }
-    return MRT_OK;
-}
-
-static int img_tonemap(mrt_ctx *c)
-{
-    const float *src = c->d_full ? c->d_full : c->d_accum;
-    const u32 count = c->d_full ? c->full_count : c->count;
-    if (!c->d_full && c->shard_count != 1) return fail(MRT_ERR_STATE, "mrt_img: this context holds only its own rows; gather and mrt_set_accum first");
-    if (count == 0) return fail(MRT_ERR_STATE, "mrt_img: no samples accumulated (the reference would panic on an empty map, src/sampler.rs:85)");
-    const float rc = 1.0f / (float)count;
-    const float wexp = (1.0f - c->pk.exp) * (1.0f - c->pk.exp);
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    if (c->adaptive) {                        // each pixel with its tile's 1/count (tile counts of the last adaptive call)
-        const u32 n_tiles = ((c->pk.nw + 7u) / 8u) * ((c->pk.nh + 7u) / 8u);
-        HIP_TRY(launch_tonemap_tiles(src, c->d_ss, c->d_adapt + 3u * (size_t)n_tiles, c->pk.nw, c->pk.nh, c->pk.gamma, wexp, c->stream));
+        HIP_TRY(im->vl.alloc(rh));
+        HIP_TRY(im->vc.alloc(rh));
+        HIP_TRY(im->vw.alloc((size_t)rh * v.cap));
+        HIP_TRY(im->hl.alloc(rw));
+        HIP_TRY(im->hc.alloc(rw));
+        HIP_TRY(im->hw.alloc((size_t)rw * h.cap));
+        HIP_TRY(hipMemcpy(im->vl.p, v.left.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(im->vc.p, v.count.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(im->vw.p, v.weight.data(), sizeof(float) * (size_t)rh * v.cap, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(im->hl.p, h.left.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(im->hc.p, h.count.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(im->hw.p, h.weight.data(), sizeof(float) * (size_t)rw * h.cap, hipMemcpyHostToDevice));
+        HIP_TRY(im->tmp.alloc((size_t)nw * rh * 3));
+        HIP_TRY(im->out.alloc((size_t)rw * rh * 3));
+        im->vcap = v.cap; im->hcap = h.cap;
         return MRT_OK;
-    }
-    HIP_TRY(launch_tonemap(src, c->d_ss, c->pk.nw * c->pk.nh, rc, c->pk.gamma, wexp, c->stream));
+    }();
+    if (rc) { im.reset(); (void)hipGetLastError(); return rc; }     // (what failed is not left pending for the next launch)
+    c->img = std::move(im);
     return MRT_OK;
 }
 
-// the end of mrt_img / mrt_img_ss: close the timing of the image kernels, wait for them and copy `bytes` of `src` out
-static int img_read_back(mrt_ctx *c, uint8_t *rgb8, const unsigned char *src, size_t bytes)
+static int img_tonemap(mrt_ctx *c, const char *fn)
 {
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1)); c->stats.img_ms = ms; }
+    Frame f;
+    if (const int rc = whole_frame(c, fn, " (the reference would panic on an empty map, src/sampler.rs:85)", f)) return rc;
+    const float wexp = (1.0f - c->pk.exp) * (1.0f - c->pk.exp);
+    HIP_TRY(hipEventRecord(c->ev0.get(), c->stream.get()));
+    if (c->adaptive)                          // each pixel with its tile's 1/count (tile counts of the last adaptive call)
+        HIP_TRY(launch_tonemap_tiles(f.rgb, c->img->ss.p, c->ad->counts(), c->pk.nw, c->pk.nh, c->pk.gamma, wexp, c->stream.get()));
+    else
+        HIP_TRY(launch_tonemap(f.rgb, c->img->ss.p, c->pk.nw * c->pk.nh, 1.0f / (float)f.count, c->pk.gamma, wexp, c->stream.get()));
+    return MRT_OK;
+}
+
+// The end of the image entry points: the tone-mapped frame, through Lanczos3 when `resize` asks for the output resolution and it
+// differs (image 0.24 resize copies when the dimensions match); then close the timing of the image kernels, wait for them and
+// copy the image out
+static int img_finish(mrt_ctx *c, uint8_t *rgb8, bool resize)
+{
+    const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
+    const Image &im = *c->img;
+    const unsigned char *src = im.ss.p;
+    size_t bytes = (size_t)nw * nh * 3;
+    if (resize && (rw != nw || rh != nh)) {
+        HIP_TRY(launch_lanczos_v(im.ss.p, im.tmp.p, nw, rh, im.vl.p, im.vc.p, im.vw.p, im.vcap, c->stream.get()));
+        HIP_TRY(launch_lanczos_h(im.tmp.p, im.out.p, nw, rw, rh, im.hl.p, im.hc.p, im.hw.p, im.hcap, c->stream.get()));
+        src = im.out.p;
+        bytes = (size_t)rw * rh * 3;
+    }
+    HIP_TRY(hipEventRecord(c->ev1.get(), c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    { float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get())); c->stats.img_ms = ms; }
     HIP_TRY(hipMemcpy(rgb8, src, bytes, hipMemcpyDeviceToHost));
     ok();
     return MRT_OK;
@@ -1331,27 +1367,17 @@ static int img_read_back(mrt_ctx *c, uint8_t *rgb8, const unsigned char *src, si
 int mrt_img_ss(mrt_ctx *c, uint8_t *rgb8)
 {
     if (!c || !rgb8) return fail(MRT_ERR_ARG, "mrt_img_ss: null argument");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
-    if ((rc = img_prepare(c))) return rc;
-    if ((rc = img_tonemap(c))) return rc;
-    return img_read_back(c, rgb8, c->d_ss, (size_t)c->pk.nw * c->pk.nh * 3);
+    int rc;
+    if ((rc = enter(c)) || (rc = img_prepare(c)) || (rc = img_tonemap(c, "mrt_img_ss"))) return rc;
+    return img_finish(c, rgb8, false);
 }
 
 int mrt_img(mrt_ctx *c, uint8_t *rgb8)
 {
     if (!c || !rgb8) return fail(MRT_ERR_ARG, "mrt_img: null argument");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = settle(c))) return rc;
-    if ((rc = img_prepare(c))) return rc;
-    if ((rc = img_tonemap(c))) return rc;
-    const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
-    if (rw == nw && rh == nh) return img_read_back(c, rgb8, c->d_ss, (size_t)nw * nh * 3);      // image 0.24 resize copies when the dimensions match
-    HIP_TRY(launch_lanczos_v(c->d_ss, c->d_tmp, nw, rh, c->d_vl, c->d_vc, c->d_vw, c->vcap, c->stream));
-    HIP_TRY(launch_lanczos_h(c->d_tmp, c->d_out, nw, rw, rh, c->d_hl, c->d_hc, c->d_hw, c->hcap, c->stream));
-    return img_read_back(c, rgb8, c->d_out, (size_t)rw * rh * 3);
+    int rc;
+    if ((rc = enter(c)) || (rc = img_prepare(c)) || (rc = img_tonemap(c, "mrt_img"))) return rc;
+    return img_finish(c, rgb8, true);
 }
 
 // ---- first-hit AOVs and the a-trous denoiser -------------------------------------------------------------------
@@ -1362,37 +1388,35 @@ static int aov_compute(mrt_ctx *c, bool &cached, double &ms)
     ms = 0.0;
     if (c->aov_ready) return MRT_OK;
     const Packed &ap = c->aov_pk ? *c->aov_pk : c->pk;
-    const size_t np = (size_t)ap.nw * ap.nh;
-    if (!c->d_guide) HIP_TRY(hipMalloc((void **)&c->d_guide, np * 8u * sizeof(float)));
-    if (!c->d_albedo) HIP_TRY(hipMalloc((void **)&c->d_albedo, np * 3u * sizeof(float)));
-    if (!c->d_ids) HIP_TRY(hipMalloc((void **)&c->d_ids, np * 2u * sizeof(i32)));
-    if (!c->d_aov_seg) {
-        HIP_TRY(hipMalloc((void **)&c->d_aov_seg, 8u * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(c->d_aov_seg, 0, 8u * sizeof(unsigned long long)));
-    }
-    const u32 *blob = c->d_blob;
-    if (c->aov_pk || !blob) {                 // deep staging, or a multi-device context (its scene lives on the sub-contexts)
-        if (!c->d_aov_blob) {
-            const size_t bytes = ap.blob.size() * 4u;
-            HIP_TRY(hipMalloc((void **)&c->d_aov_blob, bytes ? bytes : 16u));
-            HIP_TRY(hipMemcpy(c->d_aov_blob, ap.blob.data(), bytes, hipMemcpyHostToDevice));
+    const bool own_blob = c->aov_pk || !c->blob.p;      // deep staging, or a multi-device context (its scene lives on the sub-contexts)
+    if (!c->aov) {
+        const size_t np = (size_t)ap.nw * ap.nh;
+        std::unique_ptr<Aov> a(new Aov());
+        HIP_TRY(a->guide.alloc(np * 8u));
+        HIP_TRY(a->albedo.alloc(np * 3u));
+        HIP_TRY(a->ids.alloc(np * 2u));
+        HIP_TRY(a->seg.alloc(8u));
+        HIP_TRY(hipMemset(a->seg.p, 0, 8u * sizeof(unsigned long long)));
+        if (own_blob) {
+            const size_t words = ap.blob.size();
+            HIP_TRY(a->blob.alloc(words ? words : 4u));
+            HIP_TRY(hipMemcpy(a->blob.p, ap.blob.data(), words * 4u, hipMemcpyHostToDevice));
         }
-        blob = c->d_aov_blob;
+        for (Event &e : a->ev) HIP_TRY(create(e));
+        c->aov = std::move(a);
     }
-    for (hipEvent_t &e : c->dn_ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    Aov &a = *c->aov;
     Params P = ap.P;
-    P.blob = blob;
-    P.segments = c->d_aov_seg;
-    HIP_TRY(hipEventRecord(c->dn_ev[0], c->stream));
-    HIP_TRY(launch_aov(P, ap.features, c->d_guide, c->d_albedo, c->d_ids, c->stream));
-    HIP_TRY(hipEventRecord(c->dn_ev[1], c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float t = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&t, c->dn_ev[0], c->dn_ev[1]));
-    ms = t;
+    P.blob = own_blob ? a.blob.p : c->blob.p;
+    P.segments = a.seg.p;
+    HIP_TRY(hipEventRecord(a.ev[0].get(), c->stream.get()));
+    HIP_TRY(launch_aov(P, ap.features, a.guide.p, a.albedo.p, a.ids.p, c->stream.get()));
+    HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    { float t = 0.0f; HIP_TRY(hipEventElapsedTime(&t, a.ev[0].get(), a.ev[1].get())); ms = t; }
     // instances are flattened renderer by renderer in description order (mrt_pack.cpp): the first flat index of each renderer
-    c->inst_first.assign(ap.P.n_rend, 0u);
-    for (u32 i = ap.P.n_inst; i-- > 0;) c->inst_first[ap.blob[ap.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    a.inst_first.assign(ap.P.n_rend, 0u);
+    for (u32 i = ap.P.n_inst; i-- > 0;) a.inst_first[ap.blob[ap.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
     c->aov_ready = true;
     return MRT_OK;
 }
@@ -1400,28 +1424,28 @@ static int aov_compute(mrt_ctx *c, bool &cached, double &ms)
 int mrt_aov(mrt_ctx *c, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance)
 {
     if (!c) return fail(MRT_ERR_ARG, "mrt_aov: null context");
-    int rc = set_device(c);
-    if (rc) return rc;
     bool cached;
     double ms;
-    if ((rc = aov_compute(c, cached, ms))) return rc;
+    int rc;
+    if ((rc = set_device(c)) || (rc = aov_compute(c, cached, ms))) return rc;
+    const Aov &a = *c->aov;
     const size_t np = (size_t)c->pk.nw * c->pk.nh;
     if (depth || normal) {
         std::vector<float> g(np * 4u);
-        HIP_TRY(hipMemcpy(g.data(), c->d_guide, np * 4u * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(g.data(), a.guide.p, np * 4u * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t p = 0; p < np; ++p) {
             if (depth) depth[p] = g[4 * p + 3];
             if (normal) for (int k = 0; k < 3; ++k) normal[3 * p + k] = g[4 * p + k];
         }
     }
-    if (albedo) HIP_TRY(hipMemcpy(albedo, c->d_albedo, np * 3u * sizeof(float), hipMemcpyDeviceToHost));
+    if (albedo) HIP_TRY(hipMemcpy(albedo, a.albedo.p, np * 3u * sizeof(float), hipMemcpyDeviceToHost));
     if (renderer || instance) {
         std::vector<i32> ids(np * 2u);
-        HIP_TRY(hipMemcpy(ids.data(), c->d_ids, np * 2u * sizeof(i32), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ids.data(), a.ids.p, np * 2u * sizeof(i32), hipMemcpyDeviceToHost));
         for (size_t p = 0; p < np; ++p) {
             const i32 r = ids[2 * p];
             if (renderer) renderer[p] = r;
-            if (instance) instance[p] = r < 0 ? -1 : ids[2 * p + 1] - (i32)c->inst_first[(u32)r];
+            if (instance) instance[p] = r < 0 ? -1 : ids[2 * p + 1] - (i32)a.inst_first[(u32)r];
         }
     }
     ok();
@@ -1451,29 +1475,23 @@ static int denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *
 {
     u32 passes;
     float sc, sn, sp;
-    int rc = denoise_opts(o, fn, passes, sc, sn, sp);
-    if (rc) return rc;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = settle(c))) return rc;
-    const float *src = c->d_full ? c->d_full : c->d_accum;
-    const u32 count = c->d_full ? c->full_count : c->count;
-    if (!c->d_full && c->shard_count != 1) return fail(MRT_ERR_STATE, "%s: this context holds only its own rows; gather and mrt_set_accum first", fn);
-    if (count == 0) return fail(MRT_ERR_STATE, "%s: no samples accumulated", fn);
+    Frame f;
     bool cached;
     double aov_ms;
-    if ((rc = aov_compute(c, cached, aov_ms))) return rc;
+    int rc;
+    if ((rc = denoise_opts(o, fn, passes, sc, sn, sp)) || (rc = enter(c)) || (rc = whole_frame(c, fn, "", f)) || (rc = aov_compute(c, cached, aov_ms))) return rc;
+    Aov &a = *c->aov;
     const u32 nw = c->pk.nw, nh = c->pk.nh;
     const size_t np = (size_t)nw * nh;
-    if (!c->d_dn) HIP_TRY(hipMalloc((void **)&c->d_dn, np * 11u * sizeof(float)));
-    float *e0 = c->d_dn, *e1 = e0 + 4u * np, *dst = e1 + 4u * np;
-    const u32 n_tiles = ((nw + 7u) / 8u) * ((nh + 7u) / 8u);
-    const u32 *tc = c->adaptive ? c->d_adapt + 3u * (size_t)n_tiles : nullptr;     // per-tile counts of the last adaptive call
-    HIP_TRY(hipEventRecord(c->dn_ev[0], c->stream));
-    HIP_TRY(launch_denoise(src, 1.0f / (float)count, tc, c->d_guide, c->d_albedo, nw, nh, passes, sc, sn, sp, e0, e1, dst, c->stream));
-    HIP_TRY(hipEventRecord(c->dn_ev[1], c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!a.dn.p) HIP_TRY(a.dn.alloc(np * 11u));
+    float *e0 = a.dn.p, *e1 = e0 + 4u * np, *dst = e1 + 4u * np;
+    const u32 *tc = c->adaptive ? c->ad->counts() : nullptr;     // per-tile counts of the last adaptive call
+    HIP_TRY(hipEventRecord(a.ev[0].get(), c->stream.get()));
+    HIP_TRY(launch_denoise(f.rgb, 1.0f / (float)f.count, tc, a.guide.p, a.albedo.p, nw, nh, passes, sc, sn, sp, e0, e1, dst, c->stream.get()));
+    HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->dn_ev[0], c->dn_ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, a.ev[0].get(), a.ev[1].get()));
     if (info) {
         memset(info, 0, sizeof *info);
         info->aov_ms = aov_ms; info->filter_ms = ms; info->passes = passes; info->aov_cached = cached ? 1u : 0u;
@@ -1498,23 +1516,18 @@ int mrt_img_denoised(mrt_ctx *c, const mrt_denoise_opts *o, uint8_t *rgb8, mrt_d
 {
     if (!c || !rgb8) return fail(MRT_ERR_ARG, "mrt_img_denoised: null argument");
     const float *dst = nullptr;
-    int rc = denoise_run(c, o, info, "mrt_img_denoised", &dst);
-    if (rc) return rc;
-    if ((rc = img_prepare(c))) return rc;
-    const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
+    int rc;
+    if ((rc = denoise_run(c, o, info, "mrt_img_denoised", &dst)) || (rc = img_prepare(c))) return rc;
     const float wexp = (1.0f - c->pk.exp) * (1.0f - c->pk.exp);
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    HIP_TRY(launch_tonemap(dst, c->d_ss, nw * nh, 1.0f, c->pk.gamma, wexp, c->stream));
-    if (rw == nw && rh == nh) return img_read_back(c, rgb8, c->d_ss, (size_t)nw * nh * 3);
-    HIP_TRY(launch_lanczos_v(c->d_ss, c->d_tmp, nw, rh, c->d_vl, c->d_vc, c->d_vw, c->vcap, c->stream));
-    HIP_TRY(launch_lanczos_h(c->d_tmp, c->d_out, nw, rw, rh, c->d_hl, c->d_hc, c->d_hw, c->hcap, c->stream));
-    return img_read_back(c, rgb8, c->d_out, (size_t)rw * rh * 3);
+    HIP_TRY(hipEventRecord(c->ev0.get(), c->stream.get()));
+    HIP_TRY(launch_tonemap(dst, c->img->ss.p, c->pk.nw * c->pk.nh, 1.0f, c->pk.gamma, wexp, c->stream.get()));
+    return img_finish(c, rgb8, true);
 }
 
 int mrt_get_stats(mrt_ctx *c, mrt_stats *out)
 {
     if (!c || !out) return fail(MRT_ERR_ARG, "mrt_get_stats: null argument");
-    if (c->pending) { int rc = set_device(c); if (rc) return rc; if ((rc = settle(c))) return rc; }      // an observation: booked samples are traced first
+    if (c->pending) { const int rc = enter(c); if (rc) return rc; }      // an observation: booked samples are traced first
     if (c->stats_pending) { const int rc = resolve_stats(c); if (rc) return rc; }
     *out = c->stats;
     ok();
@@ -1554,23 +1567,15 @@ int mrt_selftest_math(int device, int op, const float *a, const float *b, float 
     if (device < 0) device = 0;
     HIP_TRY(hipSetDevice(device));
     if (n == 0) { ok(); return MRT_OK; }
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
     const size_t bytes = n * sizeof(float);
-    auto run = [&]() -> int {                 // every exit goes through the frees below
-        HIP_TRY(hipMalloc((void **)&da, bytes));
-        HIP_TRY(hipMalloc((void **)&dout, bytes));
-        HIP_TRY(hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
-        if (b) { HIP_TRY(hipMalloc((void **)&db, bytes)); HIP_TRY(hipMemcpy(db, b, bytes, hipMemcpyHostToDevice)); }
-        HIP_TRY(launch_math_selftest(op, da, db, dout, n, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-        return MRT_OK;
-    };
-    const int rc = run();
-    if (da) (void)hipFree(da);
-    if (dout) (void)hipFree(dout);
-    if (db) (void)hipFree(db);
-    if (rc) return rc;
+    DeviceMem<float> da, dout, db;
+    HIP_TRY(da.alloc(n));
+    HIP_TRY(dout.alloc(n));
+    HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
+    if (b) { HIP_TRY(db.alloc(n)); HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice)); }
+    HIP_TRY(launch_math_selftest(op, da.p, db.p, dout.p, n, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
     ok();
     return MRT_OK;
 }
@@ -1583,29 +1588,22 @@ int mrt_selftest_sweep(int device, int op, uint64_t first, uint64_t count, uint3
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MRT_ERR_DEVICE, "mrt_selftest_sweep: no HIP device");
     if (device < 0) device = 0;
     HIP_TRY(hipSetDevice(device));
-    unsigned long long *d_mis = nullptr;
-    float *d_ex = nullptr;
+    DeviceMem<unsigned long long> d_mis;
+    DeviceMem<float> d_ex;
     unsigned long long mis = 0;
     float ex[4] = {0, 0, 0, 0};
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_mis, sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc((void **)&d_ex, 4 * sizeof(float)));
-        HIP_TRY(hipMemset(d_mis, 0, sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(d_ex, 0, 4 * sizeof(float)));
-        const uint64_t slice = 1ull << 28;                 // one launch per 2^28 elements
-        for (uint64_t done = 0; done < count; done += slice) {
-            const uint64_t n = count - done < slice ? count - done : slice;
-            HIP_TRY(launch_math_sweep(op, first + done, n, seed, d_mis, d_ex, nullptr));
-        }
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(&mis, d_mis, sizeof mis, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ex, d_ex, sizeof ex, hipMemcpyDeviceToHost));
-        return MRT_OK;
-    };
-    const int rc = run();
-    if (d_mis) (void)hipFree(d_mis);
-    if (d_ex) (void)hipFree(d_ex);
-    if (rc) return rc;
+    HIP_TRY(d_mis.alloc(1));
+    HIP_TRY(d_ex.alloc(4));
+    HIP_TRY(hipMemset(d_mis.p, 0, sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(d_ex.p, 0, 4 * sizeof(float)));
+    const uint64_t slice = 1ull << 28;                 // one launch per 2^28 elements
+    for (uint64_t done = 0; done < count; done += slice) {
+        const uint64_t n = count - done < slice ? count - done : slice;
+        HIP_TRY(launch_math_sweep(op, first + done, n, seed, d_mis.p, d_ex.p, nullptr));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&mis, d_mis.p, sizeof mis, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ex, d_ex.p, sizeof ex, hipMemcpyDeviceToHost));
     *mismatches = mis;
     if (example) memcpy(example, ex, sizeof ex);
     ok();

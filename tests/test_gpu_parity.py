@@ -298,6 +298,56 @@ def test_more_shards_than_row_blocks_and_context_churn():
         s.close()
 
 
+def _device_free_bytes():
+    """hipMemGetInfo of the HIP runtime libmrt_hip.so is bound to, looked up through the library's own handle (as
+    test_image_path.DeviceBuffer does), after the device has gone idle."""
+    import ctypes as C
+    from micro_raytracer_amd import _lib
+    _lib.lib()
+    hip = C.CDLL(_lib.LIB_PATH)
+    hip.hipMemGetInfo.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    free, total = C.c_size_t(), C.c_size_t()
+    assert hip.hipDeviceSynchronize() == 0
+    assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+def test_context_churn_returns_every_resource_made_on_first_use():
+    """Contexts that have made every resource created on first use give all of it back when destroyed: the look-ahead
+    stream, events and planes, the chunk planes of a sample-split batch, the adaptive buffers, the AOVs, the denoiser's
+    planes, the image buffers with the Lanczos taps, and a row shard's full frame.  Device free memory must not drift over
+    the cycles.  On the MI355X it stays the same to the byte; the tolerance, half of one 9.4 MB plane of this frame, only
+    allows for the runtime's own pools, and a leaked plane still fails."""
+    from micro_raytracer_amd import Sampler, scenes
+    render, _ = make_holder(scenes.cornell_box(res=(512, 384), ssaa=2, sample=64, bounce=3))
+    nw, nh = 1024, 768                               # traced at twice the output size: img_denoised resizes with Lanczos3
+    plane = nw * nh * 3 * 4
+
+    def cycle():
+        s = Sampler(seed=3)
+        for _ in range(4):                           # the third one-sample call in a row starts the look-ahead
+            s.execute(render, n_samples=1)
+        s.execute(render, n_samples=64)              # a sample-split batch through the chunk planes
+        assert s.stats()["k_split"] > 1
+        s.aov()
+        assert s.img_denoised().shape == (384, 512, 3)
+        s.close()
+        a = Sampler(seed=3)
+        a.execute_adaptive(render, 0.05, min_samples=32, max_samples=64)
+        a.close()
+        sh = Sampler(seed=3, shard_index=1, shard_count=2)
+        sh.create(render)
+        sh.set_accum(np.ones((nh, nw, 3), np.float32), 1)     # a row shard keeps the full frame next to its own rows
+        sh.close()
+
+    cycle()                                          # first use: code objects, runtime pools
+    free = []
+    for _ in range(4):
+        cycle()
+        free.append(_device_free_bytes())
+    assert max(free) - min(free) < plane // 2, (free, plane)
+
+
 def test_one_execute_is_cut_into_bounded_launches_without_changing_a_bit(monkeypatch):
     """mrt_execute bounds the sample-split buffer by cutting a large n_samples into launches of at most 64 chunks
     (1024 samples): 4096 samples in one call == 4 x 1024 == k_split 1, bit for bit, and the launch count shows the cut."""
