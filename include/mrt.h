@@ -360,6 +360,30 @@ typedef struct mrt_plan {
 } mrt_plan;
 int mrt_plan_launch(const mrt_render_desc *desc, mrt_plan *out);
 
+/* ---- per-corner attributes of triangles and meshes (not in the reference) --------------------
+ * Optional smooth shading normals and texture coordinates, one entry per corner in the order of the renderer's vertices
+ * (a MRT_KIND_TRIANGLE renderer counts as n_tris = 1).  Either pointer may be NULL:
+ *   uv[n_tris][3][2]   texture coordinates (finite); the hit's UV is interpolated, wrapped into [0, 1) like a plane's and looked up
+ *                      nearest-texel.  Only a renderer WITH uv may carry texture maps (mrt_material.tex ... emap).
+ *   vn[n_tris][3][3]   object-space normals, any length; the shading normal is interpolated and replaces the face normal
+ *                      wherever the path tracer uses one (a degenerate triangle or a zero / non-finite result: the face normal).
+ * attrs[r] belongs to scene.renderer[r]; n_renderer must equal scene.n_renderer.  Attributes on a sphere, plane or box, or a
+ * non-finite uv: MRT_ERR_SCENE.  Borrowed for the duration of the call only, like the descriptor. */
+typedef struct mrt_tri_attrs {
+    const float *uv;
+    const float *vn;
+} mrt_tri_attrs;
+
+typedef struct mrt_desc_ext {
+    uint32_t n_renderer;
+    const mrt_tri_attrs *attrs;
+    uint32_t reserved[4];
+} mrt_desc_ext;
+
+/* mrt_create / mrt_plan_launch of a scene with attributes; ext == NULL (or no attribute in it): exactly mrt_create / mrt_plan_launch. */
+mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext);
+int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mrt_plan *out);
+
 /* Test hook: run one device math-contract function elementwise on the GPU.
  * op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 pow(a,b), 5 1/a, 6 sqrt(a), 7 a/b.  b may be NULL for unary ops. */
 int mrt_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n);

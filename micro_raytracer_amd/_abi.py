@@ -86,6 +86,14 @@ class Plan(C.Structure):
                 ("small_plain_grid", C.c_uint32), ("walk_cap", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class TriAttrs(C.Structure):
+    _fields_ = [("uv", C.POINTER(C.c_float)), ("vn", C.POINTER(C.c_float))]
+
+
+class DescExt(C.Structure):
+    _fields_ = [("n_renderer", C.c_uint32), ("attrs", C.POINTER(TriAttrs)), ("reserved", C.c_uint32 * 4)]
+
+
 class Adapt(C.Structure):
     _fields_ = [("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("step", C.c_uint32), ("threshold", C.c_float),
                 ("reserved", C.c_uint32 * 4)]
@@ -139,10 +147,15 @@ class DescHolder:
 
     def __init__(self):
         self.desc = RenderDesc()
+        self.ext = None        # mrt_desc_ext when a triangle / mesh renderer carries per-corner uv / vn, else None
         self.keep = []
 
     def ptr(self):
         return C.byref(self.desc)
+
+    def ext_ptr(self):
+        """The mrt_desc_ext argument of mrt_create_ext / mrt_plan_launch_ext (None: NULL)."""
+        return None if self.ext is None else C.cast(C.byref(self.ext), C.c_void_p)
 
 
 def build_desc(render) -> DescHolder:
@@ -180,8 +193,21 @@ def build_desc(render) -> DescHolder:
         return tex_index[key]
 
     rends = (Renderer * max(1, len(sc.renderer)))()
+    attrs = (TriAttrs * max(1, len(sc.renderer)))()
+    any_attr = False
     for i, r in enumerate(sc.renderer):
         o = rends[i]
+        n_tris = 1 if r.kind == "triangle" else (np.asarray(r.mesh).reshape(-1, 9).shape[0] if r.kind == "mesh" else 0)
+        for key, width in (("uv", 2), ("vn", 3)):
+            a = getattr(r, key, None)
+            if a is None:
+                continue
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+            if n_tris and a.size != n_tris * 3 * width:
+                raise ValueError(f"renderer {i}: {key} has {a.size} floats, {n_tris} triangle(s) need {n_tris * 3 * width}")
+            h.keep.append(a)
+            setattr(attrs[i], key, a.ctypes.data_as(C.POINTER(C.c_float)))
+            any_attr = True
         o.kind = KIND_IDS[r.kind]
         params = np.zeros(9, np.float32)
         if r.kind == "sphere":
@@ -215,6 +241,11 @@ def build_desc(render) -> DescHolder:
     h.keep.append(rends)
     d.scene.renderer = C.cast(rends, C.POINTER(Renderer))
     d.scene.n_renderer = len(sc.renderer)
+    if any_attr:
+        h.keep.append(attrs)
+        h.ext = DescExt()
+        h.ext.n_renderer = len(sc.renderer)
+        h.ext.attrs = C.cast(attrs, C.POINTER(TriAttrs))
 
     lights = (Light * max(1, len(sc.light)))()
     for i, l in enumerate(sc.light):

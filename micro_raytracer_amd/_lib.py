@@ -17,6 +17,7 @@ SYMBOLS = (
     "mrt_set_accum_device", "mrt_save_image", "mrt_selftest_sweep", "mrt_plan_launch",
     "mrt_execute_adaptive", "mrt_sample_counts", "mrt_adapt_half",
     "mrt_aov", "mrt_denoise", "mrt_img_denoised",
+    "mrt_create_ext", "mrt_plan_launch_ext",
 )
 
 
@@ -50,6 +51,9 @@ def lib():
     vp, u32, u32p, f32p, u8p = C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
     L.mrt_create.restype = vp
     L.mrt_create.argtypes = [vp, C.POINTER(_abi.Opts)]
+    L.mrt_create_ext.restype = vp
+    L.mrt_create_ext.argtypes = [vp, C.POINTER(_abi.Opts), vp]
+    L.mrt_plan_launch_ext.argtypes = [vp, vp, C.POINTER(_abi.Plan)]
     L.mrt_destroy.restype = None
     L.mrt_destroy.argtypes = [vp]
     L.mrt_execute.argtypes = [vp, u32, C.POINTER(C.c_double)]
@@ -93,7 +97,11 @@ def plan_launch(render_or_holder):
     """What mrt_create would stage in LDS for this scene and the launch shape it would take (host only, no device needed)."""
     h = render_or_holder if hasattr(render_or_holder, "ptr") else _abi.build_desc(render_or_holder)
     pl = _abi.Plan()
-    check(lib().mrt_plan_launch(C.cast(h.ptr(), C.c_void_p), C.byref(pl)))
+    ext = h.ext_ptr() if hasattr(h, "ext_ptr") else None
+    if ext is None:
+        check(lib().mrt_plan_launch(C.cast(h.ptr(), C.c_void_p), C.byref(pl)))
+    else:
+        check(lib().mrt_plan_launch_ext(C.cast(h.ptr(), C.c_void_p), ext, C.byref(pl)))
     d = {k: getattr(pl, k) for k, _ in pl._fields_ if k != "reserved"}
     d["staging"] = _abi.STAGING[pl.staging]
     return d

@@ -341,7 +341,7 @@ struct Plan {
     size_t staged_bytes = 0;
 };
 
-void plan_launch(const mrt_render_desc *desc, Packed &pk, Plan &pl)
+void plan_launch(const mrt_render_desc *desc, const mrt_desc_ext *ext, Packed &pk, Plan &pl)
 {
     // ---- what is staged in LDS, and the launch shape -------------------------------------------------------------------
     // LDS per workgroup = staged scene + lane stash (+ the mesh kernels' walk areas): pt_lds_bytes knows.  Staging levels:
@@ -401,7 +401,7 @@ void plan_launch(const mrt_render_desc *desc, Packed &pk, Plan &pl)
             // walk areas of one 1024-thread workgroup; the rest of the LDS holds the first nodes of the table
             PackOpts po; po.tbvh_wide = true;
             Packed again; std::string err2;
-            bool ok2 = pack_scene(desc, again, err2, po) == MRT_OK && again.tbvh_wide;
+            bool ok2 = pack_scene(desc, again, err2, po, ext) == MRT_OK && again.tbvh_wide;
             const size_t fixed = (size_t)ST_SLOTS * 1024u * sizeof(float) + (size_t)deep_cap * 1024u * sizeof(u32) + 1024u;
             const size_t front = ok2 ? (size_t)again.P.off_tbvh * 4 : 0;
             ok2 = ok2 && front + fixed < kLdsLimit;
@@ -445,7 +445,7 @@ void plan_launch(const mrt_render_desc *desc, Packed &pk, Plan &pl)
         const u32 f = (u32)atoi(force);
         if ((f == 64u && !cold) || f == 256u || f == 512u || f == 1024u) { if (fits(f, cold)) { want = f; marker = cold; pl.small_plain_grid = false; } }
     }
-    pk.features = (pk.features & 31u) | marker | (pk.all_ident ? (u32)F_IDENT : 0u);      // (pt_instantiation: which shapes have F_IDENT builds)
+    pk.features = (pk.features & (31u | F_VATTR)) | marker | (pk.all_ident ? (u32)F_IDENT : 0u);      // (pt_instantiation: which shapes have F_IDENT builds)
     // the leaf queue of the warm mesh kernels takes what the LDS has left while the workgroups per CU stay the same (967-triangle
     // bench scene: 13 entries, +2 % over 8: fewer walks need a second round)
     if (in_lds && marker == kWarm && mesh_walk && has_walk_area(pk.features)) {
@@ -462,20 +462,20 @@ void plan_launch(const mrt_render_desc *desc, Packed &pk, Plan &pl)
 
 }  // namespace
 
-static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
+static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext)
 {
     const u32 shard_count = opts->shard_count ? opts->shard_count : 1;
     if (opts->shard_index >= shard_count) { fail(MRT_ERR_ARG, "mrt_create: shard_index %u >= shard_count %u", opts->shard_index, shard_count); return nullptr; }
 
     std::unique_ptr<mrt_ctx> c(new mrt_ctx());              // every failure below: the context is destroyed with what it holds
     std::string err;
-    const int rc = pack_scene(desc, c->pk, err);
+    const int rc = pack_scene(desc, c->pk, err, PackOpts(), ext);
     if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); return nullptr; }
     Plan plan;
-    plan_launch(desc, c->pk, plan);          // may re-pack the scene (deep staging: 4-wide triangle BVHs), before anything is uploaded
+    plan_launch(desc, ext, c->pk, plan);          // may re-pack the scene (deep staging: 4-wide triangle BVHs), before anything is uploaded
     if (c->pk.tbvh_wide) {                   // the AOV kernel (scene through L2, no F_DEEP build) walks the binary triangle BVHs
         c->aov_pk.reset(new Packed());
-        if (pack_scene(desc, *c->aov_pk, err) != MRT_OK) { fail(MRT_ERR_SCENE, "mrt_create: %s", err.c_str()); return nullptr; }
+        if (pack_scene(desc, *c->aov_pk, err, PackOpts(), ext) != MRT_OK) { fail(MRT_ERR_SCENE, "mrt_create: %s", err.c_str()); return nullptr; }
     }
 
     int ndev = 0;
@@ -568,14 +568,14 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts)
 
 // In-process multi-device context: n sharded sub-contexts (device r renders row blocks b = r mod n), one RCCL
 // ncclGather of the padded shard accumulators to device 0 per mrt_execute, rows placed into the frame by scatter_rows.
-static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, u32 n)
+static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext, u32 n)
 {
     std::string err;
     if (!g_rccl.load(err)) { fail(MRT_ERR_DEVICE, "mrt_create: %s", err.c_str()); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || (u32)ndev < n) { fail(MRT_ERR_DEVICE, "mrt_create: n_devices = %u but %d HIP device(s) are visible", n, ndev); return nullptr; }
     std::unique_ptr<mrt_ctx> g(new mrt_ctx());              // every failure below: the context is destroyed with what it holds
-    const int rc = pack_scene(desc, g->pk, err);
+    const int rc = pack_scene(desc, g->pk, err, PackOpts(), ext);
     if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); return nullptr; }
     g->device = 0; g->seed = opts->seed;
     g->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || env_on("MRT_DEFER");
@@ -588,7 +588,7 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
         mrt_opts o = *opts;
         o.n_devices = 0; o.device = (int)r; o.shard_index = r; o.shard_count = n; o.shard_rows = g->shard_rows;
         o.flags &= ~MRT_FLAG_DEFER;                   // the group defers, not its shards
-        gr.subs.emplace_back(create_single(desc, &o));
+        gr.subs.emplace_back(create_single(desc, &o, ext));
         if (!gr.subs.back()) return nullptr;
     }
     auto bail = [&](const char *what, const char *why) { fail(MRT_ERR_DEVICE, "mrt_create: %s: %s", what, why); return (mrt_ctx *)nullptr; };
@@ -618,7 +618,9 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
     return g.release();
 }
 
-mrt_ctx *mrt_create(const mrt_render_desc *desc, const mrt_opts *opts)
+mrt_ctx *mrt_create(const mrt_render_desc *desc, const mrt_opts *opts) { return mrt_create_ext(desc, opts, nullptr); }
+
+mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext)
 {
     g_err.clear();
     if (!desc || !opts) { fail(MRT_ERR_ARG, "mrt_create: null argument"); return nullptr; }
@@ -628,9 +630,9 @@ mrt_ctx *mrt_create(const mrt_render_desc *desc, const mrt_opts *opts)
     const bool force_group = getenv("MRT_FORCE_RCCL") != nullptr;               // tests: the group path on one device
     if (n > 1 || (n == 1 && force_group)) {
         if (opts->shard_count > 1) { fail(MRT_ERR_ARG, "mrt_create: n_devices and shard_count are mutually exclusive"); return nullptr; }
-        return create_group(desc, opts, n);
+        return create_group(desc, opts, ext, n);
     }
-    return create_single(desc, opts);
+    return create_single(desc, opts, ext);
 }
 
 void mrt_destroy(mrt_ctx *ctx) { delete ctx; }
@@ -1534,16 +1536,18 @@ int mrt_get_stats(mrt_ctx *c, mrt_stats *out)
     return MRT_OK;
 }
 
-int mrt_plan_launch(const mrt_render_desc *desc, mrt_plan *out)
+int mrt_plan_launch(const mrt_render_desc *desc, mrt_plan *out) { return mrt_plan_launch_ext(desc, nullptr, out); }
+
+int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mrt_plan *out)
 {
     if (!desc || !out) return fail(MRT_ERR_ARG, "mrt_plan_launch: null argument");
     Packed pk;
     std::string err;
-    const int rc = pack_scene(desc, pk, err);
+    const int rc = pack_scene(desc, pk, err, PackOpts(), ext);
     if (rc != MRT_OK) return fail(rc, "mrt_plan_launch: %s", err.c_str());
     const u32 n_nodes = pk.n_tbvh_nodes;
     Plan pl;
-    plan_launch(desc, pk, pl);
+    plan_launch(desc, ext, pk, pl);
     memset(out, 0, sizeof *out);
     out->staging = !pl.in_lds ? 3u : ((pk.features & 128u) ? 2u : ((pk.features & 64u) ? 1u : 0u));
     out->block_threads = pl.block_threads;

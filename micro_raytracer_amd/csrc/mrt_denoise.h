@@ -49,7 +49,7 @@ MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
     const V3 n = hit_normal<FEAT>(S, ob, nh0, h.i0);
     a.g.nx = n.x; a.g.ny = n.y; a.g.nz = n.z; a.g.t = h.t0;
     a.g.px = p0.x; a.g.py = p0.y; a.g.pz = p0.z; a.g.hit = 1.0f;
-    a.albedo = surf_color<FEAT>(S, surf_of<FEAT>(S, h, ob, nh0));
+    a.albedo = surf_color<FEAT>(S, surf_of<FEAT>(S, h, ob, nh0, h.i0));
     a.rend = h.rend; a.inst = (i32)h.inst;
     return a;
 }

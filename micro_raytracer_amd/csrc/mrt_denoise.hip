@@ -128,7 +128,8 @@ __global__ void __launch_bounds__(256) dn_pass(const DnPassArgs A)
 hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo, i32 *ids, hipStream_t stream)
 {
     constexpr u32 FN = F_ALL & ~F_TRI;
-    const u32 inst = ((features & F_TRI) ? (u32)F_ALL : FN) | (features & F_BVH);      // pt_instantiation of the L2 shape
+    const u32 inst = (features & F_VATTR) ? (F_ALL | F_VATTR | (features & F_BVH))       // pt_instantiation of the L2 shape
+                                          : (((features & F_TRI) ? (u32)F_ALL : FN) | (features & F_BVH));
     const dim3 grid((P.nw + 15u) / 16u, (P.nh + 15u) / 16u);
     float4 *g = reinterpret_cast<float4 *>(guide);
     switch (inst) {
@@ -136,6 +137,8 @@ hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo
     case F_ALL: hipLaunchKernelGGL((aov_first_hit<F_ALL>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
     case FN | F_BVH: hipLaunchKernelGGL((aov_first_hit<FN | F_BVH>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
     case F_ALL | F_BVH: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_BVH>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
+    case F_ALL | F_VATTR: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_VATTR>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
+    case F_ALL | F_BVH | F_VATTR: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_BVH | F_VATTR>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
     default: return hipErrorInvalidConfiguration;
     }
     return hipGetLastError();

@@ -369,7 +369,7 @@ u32 to_usize_u32(float v)   // (res as f32 * ssaa) as usize, src/sampler.rs:29-3
 
 }  // namespace
 
-int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const PackOpts &opts)
+int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const PackOpts &opts, const mrt_desc_ext *ext)
 {
     char msg[256];
     if (!d) { err = "null render description"; return MRT_ERR_ARG; }
@@ -377,6 +377,12 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     if ((sc.n_renderer && !sc.renderer) || (sc.n_light && !sc.light) || (sc.n_textures && !sc.textures)) {
         err = "null array with non-zero count"; return MRT_ERR_ARG;
     }
+    if (ext && ext->n_renderer != sc.n_renderer) {
+        snprintf(msg, sizeof msg, "attributes for %u renderers, the scene has %u", ext->n_renderer, sc.n_renderer); err = msg; return MRT_ERR_SCENE;
+    }
+    if (ext && ext->n_renderer && !ext->attrs) { err = "null attribute array"; return MRT_ERR_ARG; }
+    auto uv_of = [&](u32 r) { return ext ? ext->attrs[r].uv : nullptr; };
+    auto vn_of = [&](u32 r) { return ext ? ext->attrs[r].vn : nullptr; };
     out = Packed();
     Params &P = out.P;
     memset(&P, 0, sizeof P);
@@ -421,10 +427,17 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         const int32_t maps[6] = {o.mat.tex, o.mat.rmap, o.mat.mmap, o.mat.gmap, o.mat.omap, o.mat.emap};
         for (int k = 0; k < 6; ++k) {
             if (maps[k] >= (int32_t)sc.n_textures) { snprintf(msg, sizeof msg, "renderer %u: map %d index out of range", r, k); err = msg; return MRT_ERR_SCENE; }
-            if (maps[k] >= 0 && (o.kind == MRT_KIND_TRIANGLE || o.kind == MRT_KIND_MESH)) {
+            if (maps[k] >= 0 && (o.kind == MRT_KIND_TRIANGLE || o.kind == MRT_KIND_MESH) && !uv_of(r)) {
                 snprintf(msg, sizeof msg, "renderer %u: texture maps on a triangle/mesh hit todo!() in the reference (src/rt.rs:546,806)", r);
                 err = msg; return MRT_ERR_SCENE;
             }
+        }
+        if ((uv_of(r) || vn_of(r)) && o.kind != MRT_KIND_TRIANGLE && o.kind != MRT_KIND_MESH) {
+            snprintf(msg, sizeof msg, "renderer %u: per-corner attributes on a renderer that is neither a triangle nor a mesh", r); err = msg; return MRT_ERR_SCENE;
+        }
+        if (const float *uv = uv_of(r)) {
+            const size_t n = (size_t)(o.kind == MRT_KIND_MESH ? o.n_tris : 1u) * 6;
+            for (size_t i = 0; i < n; ++i) if (!std::isfinite(uv[i])) { snprintf(msg, sizeof msg, "renderer %u: non-finite uv", r); err = msg; return MRT_ERR_SCENE; }
         }
         if (o.mat.emap < 0 && !unit(o.mat.emit)) {
             snprintf(msg, sizeof msg, "renderer %u: emit %g outside [0,1] (gen_bool panics, src/rt.rs:968)", r, (double)o.mat.emit); err = msg; return MRT_ERR_SCENE;
@@ -468,6 +481,15 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     std::vector<std::vector<Wide4>> wide;       // per mesh with a triangle BVH: its 4-wide nodes (local child indices)
     std::vector<u32> wide_mesh;                 // ... and the mesh-table record it belongs to
     std::vector<u32> memb_tab, membe_tab, parent_tab;
+    // per-corner attributes (mrt_scene.h REND_VATTR): the rows of all renderers that have any, and each such renderer's first row
+    std::vector<float> vattr_tab;
+    std::vector<std::pair<u32, u32>> vattr_first;
+    auto vattr_row = [&](u32 r, u32 tri) {
+        float row[VATTR_WORDS] = {0};
+        if (const float *vn = vn_of(r)) memcpy(row + VATTR_VN, vn + (size_t)tri * 9, 9 * sizeof(float));
+        if (const float *uv = uv_of(r)) memcpy(row + VATTR_UV, uv + (size_t)tri * 6, 6 * sizeof(float));
+        vattr_tab.insert(vattr_tab.end(), row, row + VATTR_WORDS);
+    };
     u32 n_inst_total = 0;
     for (u32 r = 0; r < sc.n_renderer; ++r) {
         const mrt_renderer &o = sc.renderer[r];
@@ -482,6 +504,13 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         if (o.kind == MRT_KIND_BOX || o.kind == MRT_KIND_MESH) out.features |= 1u;   // F_BOX
         if (o.kind == MRT_KIND_TRIANGLE || o.kind == MRT_KIND_MESH) out.features |= 2u;   // F_TRI
         rec[REND_FLAGS] = any_map ? RF_HAS_MAPS : 0u;
+        const bool has_attr = uv_of(r) || vn_of(r);
+        if (has_attr) {
+            rec[REND_FLAGS] |= (uv_of(r) ? RF_HAS_UV : 0u) | (vn_of(r) ? RF_HAS_VN : 0u);
+            out.features |= 512u;                                                    // F_VATTR
+            vattr_first.push_back({r, (u32)(vattr_tab.size() / VATTR_WORDS)});
+            if (o.kind == MRT_KIND_TRIANGLE) vattr_row(r, 0u);
+        }
         H3 nn = h3(0, 0, 0), nraw = h3(0, 0, 0);
         if (o.kind == MRT_KIND_SPHERE) {
             rec[REND_GEO] = bits(o.param[0] * o.param[0]);
@@ -590,6 +619,7 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
                 const H3 e0 = hsub(b, a), e1 = hsub(c, a);
                 const float g[9] = {a.x, a.y, a.z, e0.x, e0.y, e0.z, e1.x, e1.y, e1.z};
                 tri_tab.insert(tri_tab.end(), g, g + 9);
+                if (has_attr) vattr_row(r, order[t]);          // the rows follow the triangles into the triangle BVH's leaf order
             }
         }
         rend_tab.insert(rend_tab.end(), rec, rec + REND_WORDS);
@@ -811,6 +841,11 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     // the octree leaf lists come last: they are not staged in LDS (only rays the TBVH cannot cull read them)
     P.off_leaf = B.align4(); B.w.insert(B.w.end(), leaf_tab.begin(), leaf_tab.end());
     P.lds_words = P.off_leaf;
+    if (!vattr_tab.empty()) {
+        out.off_vattr = B.align4(); for (float v : vattr_tab) B.f(v);
+        out.n_vattr_rows = (u32)(vattr_tab.size() / VATTR_WORDS);
+        for (const auto &rf : vattr_first) B.w[P.off_rend + (size_t)rf.first * REND_WORDS + REND_VATTR] = out.off_vattr + rf.second * VATTR_WORDS;
+    }
     B.align4();
     P.blob_words = (u32)B.w.size();
     P.walk_cap = tbvh_tab.empty() ? 0u : (out.tbvh_wide ? kWalkCapDefault : 8u);      // mrt_create adjusts it to the LDS budget (plan_launch)

@@ -19,6 +19,7 @@ struct Packed {
     bool all_ident = false;      // every instance untransformed (TAG_IDENT): mrt_create adds F_IDENT to the features
     bool tbvh_wide = false;      // the triangle-BVH table is the 4-wide one (PackOpts)
     u32 n_tex_u8 = 0, n_tex_f32 = 0, n_nodes = 0, n_leaf_ids = 0, n_tris = 0, n_xf = 0, n_bvh_nodes = 0, n_lin = 0, n_tbvh_nodes = 0;
+    u32 off_vattr = 0, n_vattr_rows = 0;   // the per-corner attribute table (mrt_scene.h REND_VATTR): first word, rows (0: no renderer has any)
 };
 
 struct PackOpts {
@@ -27,8 +28,9 @@ struct PackOpts {
     bool tbvh_wide = false;
 };
 
-// Returns MRT_OK or an MRT_ERR_* code with a message in err.
-int pack_scene(const mrt_render_desc *desc, Packed &out, std::string &err, const PackOpts &opts = PackOpts());
+// Returns MRT_OK or an MRT_ERR_* code with a message in err.  ext: per-corner attributes of the triangle / mesh renderers
+// (mrt.h mrt_desc_ext), NULL = none.
+int pack_scene(const mrt_render_desc *desc, Packed &out, std::string &err, const PackOpts &opts = PackOpts(), const mrt_desc_ext *ext = nullptr);
 
 // Flattened octree of one mesh in the layout of mrt_scene.h (exposed for tests).
 struct OctreeFlat {

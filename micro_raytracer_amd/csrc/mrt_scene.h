@@ -30,7 +30,15 @@ constexpr u32 NODE_WORDS = 8;
 
 // REND: [0] kind  [1] inst_off  [2] inst_cnt  [3] flags  [4..15] geometry
 enum : u32 { REND_KIND = 0, REND_INST_OFF = 1, REND_INST_CNT = 2, REND_FLAGS = 3, REND_GEO = 4 };
-enum : u32 { RF_HAS_MAPS = 1u };
+enum : u32 { RF_HAS_MAPS = 1u, RF_HAS_UV = 2u, RF_HAS_VN = 4u };
+// Per-corner attributes of a triangle / mesh renderer (mrt_desc_ext): REND word 15 (free in every geometry
+// layout) = word offset, from the blob start, of the renderer's first row in the attribute table, which lies behind the
+// octree leaf lists -- never staged in LDS, read from global memory at shading time -- and has one row of VATTR_WORDS words
+// per triangle, in the order of the packed triangles (a mesh's rows are permuted with its triangles):
+//   [0..8] vn of corner 0, 1, 2   [9..14] uv of corner 0, 1, 2   [15] 0      (an absent attribute's words are 0)
+enum : u32 { REND_VATTR = 15 };
+constexpr u32 VATTR_WORDS = 16;
+enum : u32 { VATTR_VN = 0, VATTR_UV = 9 };
 // geometry words: sphere [4] r*r | plane [4..6] n^, [7..9] n | box [4..6] half, [7..9] (1/size)*2 |
 // triangle [4..6] v0, [7..9] e0, [10..12] e1 | mesh [4] mesh index
 

@@ -31,11 +31,14 @@ enum : u32 {
     F_DEEP = 128u,    // with F_COLD, meshes beyond the LDS: triangles stay in global memory too (Params.lds_words_hot) and of the
                       // (level-ordered) triangle-BVH table only the first Params.n_tbvh_hot nodes -- the top levels of every
                       // tree -- are staged
-    F_IDENT = 256u    // EVERY instance of the scene is untransformed (default `dir`: both matrices the identity as values): the
+    F_IDENT = 256u,   // EVERY instance of the scene is untransformed (default `dir`: both matrices the identity as values): the
                       // per-instance identity test of the tag and the transform's address are compiled out of the linear scan --
                       // ~30 of ~220 cycles per instance on the Cornell box (8236 -> 8700 Msamples/s).  Exists for the plain
                       // 256-thread kernels of planes / spheres / boxes with and without lights; rays whose shifted origin has a
                       // zero, infinite or NaN component still take the reference's two mat-vecs (xf_vec)
+    F_VATTR = 512u    // some triangle / mesh renderer carries per-corner normals or UVs (mrt.h mrt_desc_ext):
+                      // the interpolation of hit_normal / hit_uv.  Exists with the full feature set only (F_ALL | F_VATTR plus the
+                      // shape markers and F_BVH)
 };
 constexpr u32 plain_feat(u32 feat) { return feat & ~(u32)F_IDENT; }
 // words of the packed scene a kernel instantiation stages in LDS
@@ -1127,11 +1130,75 @@ MRT_HD Obj obj_of(const Scn &S, const Hit &h)
 }
 MRT_HD V3 to_object(const Obj &o, V3 hp) { return add(o.pos, xf_vec(o.X, o.ident, sub(hp, o.pos))); }
 
-// Renderer::normal, src/rt.rs:776-793 with the Normal impls, src/rt.rs:414-466
+// ---- per-corner attributes (not in the reference; DESIGN.md section 14, in operation order) ----
+// Barycentric weights of the hit point p (object space, relative to the instance's position: n_hit - pos, as the sphere's
+// normal takes it) in the triangle v0, v0 + e1, v0 + e2: not clamped, f32, unfused;
+// ok = false for a degenerate triangle (den zero or not finite) or a weight that is not finite.
+struct Bary { float b1, b2; bool ok; };
+MRT_HD bool finite_(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
+MRT_HD Bary tri_bary(V3 p, V3 v0, V3 e1, V3 e2)
+{
+    const V3 q = sub(p, v0);
+    const float d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2), d20 = dot(q, e1), d21 = dot(q, e2);
+    const float den = d00 * d11 - d01 * d01;
+    Bary b;
+    b.b1 = div_(d11 * d20 - d01 * d21, den);
+    b.b2 = div_(d00 * d21 - d01 * d20, den);
+    b.ok = den != 0.0f && finite_(den) && finite_(b.b1) && finite_(b.b2);
+    return b;
+}
+// one component of an attribute with corner values a0, a1, a2: three equal corners give that value back whatever b1, b2
+MRT_HD float bary_mix(const Bary &b, float a0, float a1, float a2) { return a0 + (b.b1 * (a1 - a0) + b.b2 * (a2 - a0)); }
+// shading normal (object space, not normalised) from the corner normals vn[3][3]; the face normal when the triangle is
+// degenerate or the interpolated normal is zero or not finite
+MRT_HD V3 vattr_normal(V3 p, V3 v0, V3 e1, V3 e2, const float *vn)
+{
+    const Bary b = tri_bary(p, v0, e1, e2);
+    const V3 n = v3(bary_mix(b, vn[0], vn[3], vn[6]), bary_mix(b, vn[1], vn[4], vn[7]), bary_mix(b, vn[2], vn[5], vn[8]));
+    const bool good = b.ok && finite_(n.x) && finite_(n.y) && finite_(n.z) && !(n.x == 0.0f && n.y == 0.0f && n.z == 0.0f);
+    return good ? n : cross(e1, e2);
+}
+// texture coordinates from the corner values uv[3][2], each wrapped into [0, 1) like a plane's; corner 0's for a degenerate triangle
+MRT_HD UV vattr_uv(V3 p, V3 v0, V3 e1, V3 e2, const float *uv)
+{
+    const Bary b = tri_bary(p, v0, e1, e2);
+    UV r;
+    r.x = fract_(b.ok ? bary_mix(b, uv[0], uv[2], uv[4]) : uv[0]);
+    if (r.x < 0.0f) r.x = 1.0f + r.x;
+    r.y = fract_(b.ok ? bary_mix(b, uv[1], uv[3], uv[5]) : uv[1]);
+    if (r.y < 0.0f) r.y = 1.0f + r.y;
+    return r;
+}
+// v0, e1, e2 (words 0, 3, 6) of the hit triangle, and its row of the attribute table: global memory at every staging level
+template <u32 FEAT>
+MRT_HD const float *vattr_tri(const Scn &S, const Obj &o, i32 tri_idx)
+{
+    if (o.kind == KIND_TRIANGLE) return o.R + REND_GEO;
+    const float *M = S.F + S.P->off_mesh + ldu(o.R, REND_GEO) * MESH_WORDS;
+    return ((FEAT & F_DEEP) ? S.G : S.F) + S.P->off_tri + (ldu(M, MESH_TRI0) + (u32)tri_idx) * TRI_WORDS;
+}
+// n4 16-byte reads of the hit triangle's row of the attribute table, from 16-byte group first4 on
+template <u32 N4>
+MRT_HD void vattr_row(const Scn &S, const Obj &o, i32 tri_idx, u32 first4, float *out)
+{
+    const float *A = S.G + ldu(o.R, REND_VATTR) + (o.kind == KIND_TRIANGLE ? 0u : (u32)tri_idx) * VATTR_WORDS + first4 * 4u;
+    for (u32 k = 0; k < N4; ++k) { const F4 v = ld4(A, k * 4u); out[k * 4u] = v.x; out[k * 4u + 1u] = v.y; out[k * 4u + 2u] = v.z; out[k * 4u + 3u] = v.w; }
+}
+
+// Renderer::normal, src/rt.rs:776-793 with the Normal impls, src/rt.rs:414-466; triangles / meshes with corner normals: the
+// interpolated shading normal in the face normal's place (F_VATTR)
 template <u32 FEAT>
 MRT_HD V3 hit_normal(const Scn &S, const Obj &o, V3 n_hit, i32 tri_idx)
 {
     if (o.kind == KIND_PLANE) return ld3(o.IX, INSTX_PLANE_NW);          // norm(R*(L*n)) is per instance
+    if constexpr (FEAT & F_VATTR) {
+        if ((o.kind == KIND_TRIANGLE || o.kind == KIND_MESH) && (ldu(o.R, REND_FLAGS) & RF_HAS_VN)) {
+            const float *T = vattr_tri<FEAT>(S, o, tri_idx);
+            float a[12];                                                 // words 0..11 of the row: vn in 0..8
+            vattr_row<3>(S, o, tri_idx, 0u, a);
+            return norm(xf_vec(o.X, o.ident, vattr_normal(sub(n_hit, o.pos), ld3(T, 0), ld3(T, 3), ld3(T, 6), a + VATTR_VN)));
+        }
+    }
     V3 n = v3(0.0f, 0.0f, 0.0f);
     if (o.kind == KIND_SPHERE) n = sub(n_hit, o.pos);
     else if ((FEAT & F_BOX) && o.kind == KIND_BOX) n = box_normal(ld3(o.R, REND_GEO + 3), n_hit, o.pos);
@@ -1144,9 +1211,11 @@ MRT_HD V3 hit_normal(const Scn &S, const Obj &o, V3 n_hit, i32 tri_idx)
     return norm(xf_vec(o.X, o.ident, n));
 }
 
-// Renderer::to_uv, src/rt.rs:795-809 with the UV impls, src/rt.rs:468-542 (triangle / mesh maps are
-// rejected by mrt_create: the reference hits todo!())
-MRT_HD UV hit_uv(const Obj &o, V3 n_hit)
+// Renderer::to_uv, src/rt.rs:795-809 with the UV impls, src/rt.rs:468-542.  Triangles and meshes: the reference hits todo!();
+// with corner UVs (F_VATTR kernels, RF_HAS_UV) the interpolated UV of triangle tri_idx at the object-space hit point, wrapped
+// like the plane's; without them (0, 0), and mrt_create rejects their texture maps
+template <u32 FEAT>
+MRT_HD UV hit_uv(const Scn &S, const Obj &o, V3 n_hit, i32 tri_idx)
 {
     UV r;
     if (o.kind == KIND_SPHERE) {
@@ -1162,6 +1231,14 @@ MRT_HD UV hit_uv(const Obj &o, V3 n_hit)
         r = box_uv(ld3(o.R, REND_GEO + 3), n_hit, o.pos);
     } else {
         r.x = 0.0f; r.y = 0.0f;
+        if constexpr (FEAT & F_VATTR) {
+            if (ldu(o.R, REND_FLAGS) & RF_HAS_UV) {
+                const float *T = vattr_tri<FEAT>(S, o, tri_idx);
+                float a[8];                                              // words 8..15 of the row: uv in 9..14
+                vattr_row<2>(S, o, tri_idx, 2u, a);
+                r = vattr_uv(sub(n_hit, o.pos), ld3(T, 0), ld3(T, 3), ld3(T, 6), a + (VATTR_UV - 8u));
+            }
+        }
     }
     return r;
 }
@@ -1173,7 +1250,7 @@ struct Surf {
     UV uv;
 };
 template <u32 FEAT>
-MRT_HD Surf surf_of(const Scn &S, const Hit &h, const Obj &o, V3 n_hit)
+MRT_HD Surf surf_of(const Scn &S, const Hit &h, const Obj &o, V3 n_hit, i32 tri_idx)
 {
     Surf s;
     s.M = S.F + S.P->off_mat + (u32)h.rend * MAT_WORDS;
@@ -1181,7 +1258,7 @@ MRT_HD Surf surf_of(const Scn &S, const Hit &h, const Obj &o, V3 n_hit)
     s.uv.x = 0.0f; s.uv.y = 0.0f;
     if constexpr (FEAT & F_MAPS) {
         s.maps = (ldu(o.R, REND_FLAGS) & RF_HAS_MAPS) != 0;
-        if (s.maps) s.uv = hit_uv(o, n_hit);
+        if (s.maps) s.uv = hit_uv<FEAT>(S, o, n_hit, tri_idx);
     }
     return s;
 }
@@ -1417,7 +1494,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
             if constexpr (kHit) { st.put(ST_P0Y, p0_.y); st.put(ST_P0Z, p0_.z); }
             auto p0 = [&]() { if constexpr (kHit) return v3(p0_.x, st.get(ST_P0Y), st.get(ST_P0Z)); else return p0_; };
             const V3 nh0 = to_object(ob, p0_);
-            const Surf sf0 = surf_of<FEAT>(S, h, ob, nh0);
+            const Surf sf0 = surf_of<FEAT>(S, h, ob, nh0, h.i0);
             const float opacity0 = surf_scalar<FEAT>(S, sf0, MAP_OPACITY, MAT_OPACITY);
             const float metal_c = sf0.M[MAT_METAL];                     // hit.obj.mat.metal, not the map (src/rt.rs:564)
 
@@ -1439,7 +1516,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
                 const V3 nhh = refr ? to_object(ob, hp) : nh0;
                 hn = hit_normal<FEAT>(S, ob, nhh, refr ? h.i1 : h.i0);
                 sfh = sf0;
-                if (refr) sfh = surf_of<FEAT>(S, h, ob, nhh);
+                if (refr) sfh = surf_of<FEAT>(S, h, ob, nhh, h.i1);
                 float rough = surf_scalar<FEAT>(S, sfh, MAP_ROUGH, MAT_ROUGH);            // Ray::reflect / Ray::refract, src/rt.rs:559-589
                 const float opac = refr ? surf_scalar<FEAT>(S, sfh, MAP_OPACITY, MAT_OPACITY) : opacity0;
                 const u32 dbase = dim_of(b, refr ? SL_REFR_COIN : SL_REFL_COIN);    // coin, u1, u2 are consecutive slots

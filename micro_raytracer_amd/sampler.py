@@ -57,7 +57,7 @@ def _fingerprint(render: Render):
         out.append((l.kind, arr(l.v), l.pwr, arr(l.color)))
     for o in render.scene.renderer:
         m = o.mat
-        out.append((o.kind, o.r, arr(o.n), arr(o.sizes), arr(o.vtx), arr(o.mesh), arr(m.albedo), m.rough, m.metal, m.glass,
+        out.append((o.kind, o.r, arr(o.n), arr(o.sizes), arr(o.vtx), arr(o.mesh), arr(o.uv), arr(o.vn), arr(m.albedo), m.rough, m.metal, m.glass,
                     m.opacity, m.emit, tuple(tex(getattr(m, k)) for k in _abi.MAP_SLOTS), insts(o.inst)))
     return tuple(out)
 
@@ -111,7 +111,10 @@ class Sampler:
         opts.shard_index, opts.shard_count, opts.shard_rows = self.shard_index, self.shard_count, self.shard_rows
         opts.n_devices = self.n_devices
         opts.flags = self.flags
-        ctx = L.mrt_create(C.cast(self._holder.ptr(), C.c_void_p), C.byref(opts))
+        if self._holder.ext is None:
+            ctx = L.mrt_create(C.cast(self._holder.ptr(), C.c_void_p), C.byref(opts))
+        else:                   # per-corner uv / vn on a triangle or mesh
+            ctx = L.mrt_create_ext(C.cast(self._holder.ptr(), C.c_void_p), C.byref(opts), self._holder.ext_ptr())
         if not ctx:
             raise _lib.MrtError(L.mrt_last_status(), L.mrt_last_error().decode())
         self._ctx, self._render, self._print = ctx, render, fp

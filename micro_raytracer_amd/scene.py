@@ -123,9 +123,10 @@ class Material:
 BACKWARD = np.array([-0.0, -0.0, -1.0, -0.0], np.float32)  # Vec4f::backward(), src/lin.rs:143-145
 
 
-def load_obj(path) -> np.ndarray:
-    """MeshWrapper::load, src/parser.rs:602-618: first object / first group, first three vertices of each face."""
-    pos, tris, groups_seen = [], [], 0
+def _parse_obj(path):
+    """The faces MeshWrapper::load keeps (src/parser.rs:602-618: first object / first group, first three corners of each
+    face) as (positions, uv or None, vn or None): uv / vn are None when any kept corner lacks that index."""
+    pos, vts, vns, tris, tuv, tvn, groups_seen = [], [], [], [], [], [], 0
     with open(path) as f:
         for line in f:
             p = line.split()
@@ -133,18 +134,53 @@ def load_obj(path) -> np.ndarray:
                 continue
             if p[0] == "v":
                 pos.append([float(p[1]), float(p[2]), float(p[3])])
+            elif p[0] == "vt":
+                vts.append([float(p[1]), float(p[2]) if len(p) > 2 else 0.0])
+            elif p[0] == "vn":
+                vns.append([float(p[1]), float(p[2]), float(p[3])])
             elif p[0] in ("o", "g"):
                 if tris:
                     groups_seen += 1
                 if groups_seen:
                     break
             elif p[0] == "f":
-                idx = []
+                corner = []
                 for tok in p[1:4]:
-                    i = int(tok.split("/")[0])
-                    idx.append(i - 1 if i > 0 else len(pos) + i)
-                tris.append([pos[idx[0]], pos[idx[1]], pos[idx[2]]])
-    return np.asarray(tris, dtype=np.float64).astype(np.float32).reshape(-1, 3, 3)
+                    ref = []
+                    for field_, lst in zip((tok.split("/") + ["", ""])[:3], (pos, vts, vns)):
+                        if field_ == "":
+                            ref.append(None)
+                        else:
+                            i = int(field_)
+                            ref.append(i - 1 if i > 0 else len(lst) + i)
+                    corner.append(ref)
+                tris.append([pos[c[0]] for c in corner])
+                tuv.append(None if any(c[1] is None for c in corner) else [vts[c[1]] for c in corner])
+                tvn.append(None if any(c[2] is None for c in corner) else [vns[c[2]] for c in corner])
+    tri = np.asarray(tris, dtype=np.float64).astype(np.float32).reshape(-1, 3, 3)
+    uv = None if not tuv or any(t is None for t in tuv) else np.asarray(tuv, dtype=np.float64).astype(np.float32).reshape(-1, 3, 2)
+    vn = None if not tvn or any(t is None for t in tvn) else np.asarray(tvn, dtype=np.float64).astype(np.float32).reshape(-1, 3, 3)
+    return tri, uv, vn
+
+
+def load_obj(path) -> np.ndarray:
+    """MeshWrapper::load, src/parser.rs:602-618: first object / first group, first three vertices of each face."""
+    return _parse_obj(path)[0]
+
+
+def load_obj_attrs(path, uv=False, vn=False):
+    """(uv, vn) of the faces load_obj keeps: per-corner `vt` as (n,3,2) with v flipped to 1 - v (OBJ's origin is the bottom
+    left corner, texels are stored top row first) and per-corner `vn` as (n,3,3); None for an attribute not asked for.
+    An attribute that is asked for and that the file lacks on some kept corner is an error."""
+    _, t, n = _parse_obj(path)
+    if uv and t is None:
+        raise ValueError(f"{path}: \"uv\": true, but its faces carry no vt indices")
+    if vn and n is None:
+        raise ValueError(f"{path}: \"vn\": true, but its faces carry no vn indices")
+    if uv:
+        t = t.copy()
+        t[..., 1] = f32(1.0) - t[..., 1]
+    return (t if uv else None), (n if vn else None)
 
 
 def mesh_from_json(obj, base_dir=".") -> np.ndarray:
@@ -155,6 +191,18 @@ def mesh_from_json(obj, base_dir=".") -> np.ndarray:
         text = gzip.decompress(base64.b64decode(obj)).decode("utf-8")
         return mesh_from_json(json.loads(text), base_dir)
     return np.asarray(obj, dtype=np.float64).astype(np.float32).reshape(-1, 3, 3)
+
+
+def attr_from_json(obj, width) -> np.ndarray:
+    """Per-corner attribute (n,3,width) from nested lists or the gzip + base64 inline form of meshes."""
+    if isinstance(obj, str):
+        return attr_from_json(json.loads(gzip.decompress(base64.b64decode(obj)).decode("utf-8")), width)
+    return np.asarray(obj, dtype=np.float64).astype(np.float32).reshape(-1, 3, width)
+
+
+def attr_to_inline(a: np.ndarray) -> str:
+    obj = [[[float(c) for c in v] for v in t] for t in np.asarray(a, np.float32)]
+    return base64.b64encode(gzip.compress(json.dumps(obj).encode(), 9)).decode()
 
 
 def mesh_to_inline(tris: np.ndarray) -> str:
@@ -171,6 +219,8 @@ class Renderer:
     sizes: Optional[np.ndarray] = None
     vtx: Optional[np.ndarray] = None
     mesh: Optional[np.ndarray] = None
+    uv: Optional[np.ndarray] = None     # triangle / mesh: per-corner texture coordinates (n,3,2); None: untextured (not in the reference)
+    vn: Optional[np.ndarray] = None     # triangle / mesh: per-corner normals (n,3,3); None: faceted (not in the reference)
     mat: Material = field(default_factory=Material)
     inst: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)
     name: Optional[str] = None
@@ -191,6 +241,25 @@ class Renderer:
             r.mesh = mesh_from_json(obj["mesh"], base_dir)
         else:
             raise ValueError(f"`{kind}` type is unxpected!")
+        # optional per-corner attributes: nested lists / inline, or `true` = from the .obj file the mesh names
+        for key, width in (("uv", 2), ("vn", 3)):
+            val = obj.get(key)
+            if val is None or val is False:
+                continue
+            if kind not in ("triangle", "mesh"):
+                raise ValueError(f"`{key}` on a `{kind}`: only triangles and meshes carry per-corner attributes")
+            if val is True:
+                src = obj.get("mesh")
+                if not (kind == "mesh" and isinstance(src, str) and "." in src):
+                    raise ValueError(f"\"{key}\": true needs a mesh given as an .obj file")
+                got = load_obj_attrs(os.path.join(base_dir, src), uv=key == "uv", vn=key == "vn")
+                val = got[0] if key == "uv" else got[1]
+            else:
+                val = attr_from_json(val, width)
+            n_tris = 1 if kind == "triangle" else r.mesh.shape[0]
+            if val.shape[0] != n_tris:
+                raise ValueError(f"`{key}` has {val.shape[0]} triangles, the {kind} has {n_tris}")
+            setattr(r, key, val)
         r.mat = Material.from_json(obj.get("mat"), base_dir, tex_cache)
         r.name = obj.get("name")
         # Wrapper<Renderer>::unwrap, src/parser.rs:838-853
@@ -345,6 +414,9 @@ def dump_render(r: Render) -> dict:
             e["vtx"] = [fl(v) for v in o.vtx]
         else:
             e["mesh"] = [[fl(v) for v in t] for t in o.mesh]
+        for key in ("uv", "vn"):
+            if getattr(o, key, None) is not None:
+                e[key] = [[fl(v) for v in t] for t in getattr(o, key)]
         m = o.mat
         e["mat"] = {"albedo": fl(m.albedo), "rough": m.rough, "metal": m.metal, "glass": m.glass,
                     "opacity": m.opacity, "emit": m.emit, "tex": tex(m.tex), "rmap": tex(m.rmap),

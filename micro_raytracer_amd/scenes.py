@@ -152,6 +152,43 @@ def mesh_scene(res=(1920, 1080), ssaa=1, sample=256, bounce=8, n_tris=967, inlin
     }
 
 
+def smooth_attrs(tris):
+    """Per-corner attributes of a mesh whose vertices are shared by position: vn (n,3,3) = normalised area-weighted sum of the
+    face normals around each vertex, uv (n,3,2) = the sphere mapping of the vertex direction from the mesh's centroid
+    (u = 0.5 + atan2(x, -y) / 2 pi, v = 0.5 - z / 2 on the unit direction), u unwrapped per triangle so that no triangle
+    spans the seam (the kernel wraps the interpolated value)."""
+    t = np.asarray(tris, np.float64).reshape(-1, 3, 3)
+    face = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])            # length = 2 * area
+    keys = np.round(t.reshape(-1, 3) * 1e6).astype(np.int64)
+    _, inv = np.unique(keys, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    acc = np.zeros((inv.max() + 1, 3))
+    np.add.at(acc, inv, np.repeat(face, 3, axis=0))
+    vn = acc[inv] / np.maximum(np.linalg.norm(acc[inv], axis=1, keepdims=True), 1e-30)
+    d = t.reshape(-1, 3) - t.reshape(-1, 3).mean(axis=0)
+    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-30)
+    u = (0.5 + np.arctan2(d[:, 0], -d[:, 1]) / (2 * math.pi)).reshape(-1, 3)
+    u = np.where(u - u[:, :1] > 0.5, u - 1.0, np.where(u - u[:, :1] < -0.5, u + 1.0, u))
+    v = (0.5 - 0.5 * d[:, 2]).reshape(-1, 3)
+    return np.stack([u, v], axis=2).astype(np.float32), vn.reshape(-1, 3, 3).astype(np.float32)
+
+
+def smooth_mesh_scene(res=(1920, 1080), ssaa=1, sample=256, bounce=8, n_tris=967, vn=True, uv=True, inline=False):
+    """mesh_scene with the mesh shaded smooth (vn) and textured through a spherical UV (uv + a checker `tex`): the scene of
+    DESIGN.md section 14.  vn / uv = False leaves that attribute (and the texture) out."""
+    from .scene import attr_to_inline
+    d = mesh_scene(res, ssaa, sample, bounce, n_tris)
+    m = d["scene"]["renderer"][0]
+    tris = bumpy_mesh(n_tris) if n_tris <= 1280 else big_mesh(n_tris)
+    tuv, tvn = smooth_attrs(tris)
+    if vn:
+        m["vn"] = attr_to_inline(tvn) if inline else tvn.tolist()
+    if uv:
+        m["uv"] = attr_to_inline(tuv) if inline else tuv.tolist()
+        m["mat"]["tex"] = checker_texture(32, 16, 2, a=(1.0, 217 / 255.0, 153 / 255.0), b=(80 / 255.0, 120 / 255.0, 200 / 255.0))
+    return d
+
+
 def _atlas_texture(w=64, h=48, seed=0, base=(0.6, 0.45, 0.3)):
     """Procedural 4x3 box cross atlas with k/255 texels."""
     rng = np.random.default_rng(seed)
