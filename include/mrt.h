@@ -310,7 +310,8 @@ int mrt_adapt_half(mrt_ctx *ctx, float *rgb);
  * use and kept on the device (mrt_reset keeps them: they depend on scene and camera only).  Any output may be NULL:
  *   depth[nh][nw]        distance along the unit ray (+inf: miss)
  *   normal[nh][nw][3]    world-space normal as the path tracer uses it (0: miss)
- *   albedo[nh][nw][3]    material albedo x texture at the hit (0: miss)
+ *   albedo[nh][nw][3]    material albedo x texture at the hit (miss: 0, or, on a context with an environment texture
+ *                        (mrt_env), the sky E(d) the centre ray sees: sky.color x texel)
  *   renderer[nh][nw]     index into mrt_scene.renderer (-1: miss)
  *   instance[nh][nw]     index into that renderer's inst list (-1: miss)
  * Sharded and multi-device contexts return the whole frame too.  Not an observation: booked samples stay booked. */
@@ -374,13 +375,34 @@ typedef struct mrt_tri_attrs {
     const float *vn;
 } mrt_tri_attrs;
 
+/* ---- environment texture of the sky (not in the reference) -------------------------------------
+ * The texel the direction d of an escaping ray maps to multiplies sky.color, as a material's tex multiplies its albedo:
+ * E(d) = sky.color x texel.  A primary miss contributes E(d), a later miss L + T x (E(d) * sky.pwr); a path that runs out of
+ * bounces takes the texture's solid-angle-weighted mean in the texel's place.  Nearest texel, no filtering, no importance
+ * sampling.  Mappings (u is then shifted by rot and wrapped into [0, 1) like a plane's):
+ *   MRT_ENV_SPHERE   the sphere renderer's UV of the direction: u = 0.5 + atan2(d.x, -d.y) / 2pi, v = 0.5 - 0.5 d.z
+ *   MRT_ENV_LATLONG  equirectangular: the same u, v = acos(d.z) / pi
+ * Rejected with MRT_ERR_SCENE: w == 0, h == 0, dat == NULL, a non-finite or negative texel, an unknown mapping, a non-finite rot;
+ * with MRT_ERR_LIMIT: more than 2^25 texels. */
+#define MRT_ENV_SPHERE  0u
+#define MRT_ENV_LATLONG 1u
+typedef struct mrt_env {
+    mrt_texture tex;        /* w x h f32 RGB texels, row 0 = +z; values finite and >= 0, may exceed 1 (HDR) */
+    uint32_t mapping;       /* MRT_ENV_* */
+    float rot;              /* turns about +z added to u; finite */
+    uint32_t reserved[4];
+} mrt_env;
+
+/* attrs == NULL: no attributes, whatever n_renderer says (an ext that only carries env); env == NULL: no environment. */
 typedef struct mrt_desc_ext {
     uint32_t n_renderer;
     const mrt_tri_attrs *attrs;
-    uint32_t reserved[4];
+    const mrt_env *env;
+    uint32_t reserved[2];
 } mrt_desc_ext;
 
-/* mrt_create / mrt_plan_launch of a scene with attributes; ext == NULL (or no attribute in it): exactly mrt_create / mrt_plan_launch. */
+/* mrt_create / mrt_plan_launch of a scene with attributes or an environment; ext == NULL (or neither in it): exactly mrt_create /
+ * mrt_plan_launch. */
 mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext);
 int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mrt_plan *out);
 

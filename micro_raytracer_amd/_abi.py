@@ -90,8 +90,16 @@ class TriAttrs(C.Structure):
     _fields_ = [("uv", C.POINTER(C.c_float)), ("vn", C.POINTER(C.c_float))]
 
 
+ENV_SPHERE, ENV_LATLONG = 0, 1
+ENV_MAPPINGS = {"sphere": ENV_SPHERE, "latlong": ENV_LATLONG}
+
+
+class Env(C.Structure):
+    _fields_ = [("tex", Texture), ("mapping", C.c_uint32), ("rot", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
 class DescExt(C.Structure):
-    _fields_ = [("n_renderer", C.c_uint32), ("attrs", C.POINTER(TriAttrs)), ("reserved", C.c_uint32 * 4)]
+    _fields_ = [("n_renderer", C.c_uint32), ("attrs", C.POINTER(TriAttrs)), ("env", C.POINTER(Env)), ("reserved", C.c_uint32 * 2)]
 
 
 class Adapt(C.Structure):
@@ -147,7 +155,7 @@ class DescHolder:
 
     def __init__(self):
         self.desc = RenderDesc()
-        self.ext = None        # mrt_desc_ext when a triangle / mesh renderer carries per-corner uv / vn, else None
+        self.ext = None        # mrt_desc_ext when a triangle / mesh renderer carries per-corner uv / vn or the sky a texture, else None
         self.keep = []
 
     def ptr(self):
@@ -259,6 +267,25 @@ def build_desc(render) -> DescHolder:
 
     _f3(d.scene.sky.color, sc.sky.color)
     d.scene.sky.pwr = float(np.float32(sc.sky.pwr))
+    sky_tex = getattr(sc.sky, "tex", None)
+    if sky_tex is not None:               # the environment texture (mrt_env)
+        mapping = getattr(sc.sky, "mapping", "sphere")
+        if mapping not in ENV_MAPPINGS:
+            raise ValueError(f"sky map `{mapping}`: expected one of {sorted(ENV_MAPPINGS)}")
+        env = Env()
+        env.tex.w, env.tex.h = int(sky_tex.w), int(sky_tex.h)
+        if sky_tex.dat is not None:
+            arr = np.ascontiguousarray(np.asarray(sky_tex.dat, np.float32).reshape(-1, 3))
+            if arr.shape[0] != env.tex.w * env.tex.h:
+                raise ValueError(f"sky tex: {arr.shape[0]} texels for {env.tex.w} x {env.tex.h}")
+            h.keep.append(arr)
+            env.tex.dat = arr.ctypes.data_as(C.POINTER(C.c_float))
+        env.mapping = ENV_MAPPINGS[mapping]
+        env.rot = float(np.float32(getattr(sc.sky, "rot", 0.0)))
+        h.keep.append(env)
+        if h.ext is None:
+            h.ext = DescExt()
+        h.ext.env = C.pointer(env)
 
     texs = (Texture * max(1, len(tex_list)))()
     for i, t in enumerate(tex_list):

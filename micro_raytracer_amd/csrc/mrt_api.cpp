@@ -445,7 +445,7 @@ void plan_launch(const mrt_render_desc *desc, const mrt_desc_ext *ext, Packed &p
         const u32 f = (u32)atoi(force);
         if ((f == 64u && !cold) || f == 256u || f == 512u || f == 1024u) { if (fits(f, cold)) { want = f; marker = cold; pl.small_plain_grid = false; } }
     }
-    pk.features = (pk.features & (31u | F_VATTR)) | marker | (pk.all_ident ? (u32)F_IDENT : 0u);      // (pt_instantiation: which shapes have F_IDENT builds)
+    pk.features = (pk.features & (31u | F_VATTR | F_ENV)) | marker | (pk.all_ident ? (u32)F_IDENT : 0u);      // (pt_instantiation: which shapes have F_IDENT builds)
     // the leaf queue of the warm mesh kernels takes what the LDS has left while the workgroups per CU stay the same (967-triangle
     // bench scene: 13 entries, +2 % over 8: fewer walks need a second round)
     if (in_lds && marker == kWarm && mesh_walk && has_walk_area(pk.features)) {
@@ -1489,7 +1489,7 @@ static int denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *
     float *e0 = a.dn.p, *e1 = e0 + 4u * np, *dst = e1 + 4u * np;
     const u32 *tc = c->adaptive ? c->ad->counts() : nullptr;     // per-tile counts of the last adaptive call
     HIP_TRY(hipEventRecord(a.ev[0].get(), c->stream.get()));
-    HIP_TRY(launch_denoise(f.rgb, 1.0f / (float)f.count, tc, a.guide.p, a.albedo.p, nw, nh, passes, sc, sn, sp, e0, e1, dst, c->stream.get()));
+    HIP_TRY(launch_denoise(f.rgb, 1.0f / (float)f.count, tc, a.guide.p, a.albedo.p, nw, nh, passes, sc, sn, sp, e0, e1, dst, c->stream.get(), c->pk.P.off_env != 0u));
     HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     float ms = 0.0f;

@@ -4,6 +4,7 @@
 //
 // Filter (Dammertz et al. 2010), f32 in exactly this order (-ffp-contract=off; IEEE division; max = fmaxf):
 //   c_p = A_p * rc_p (the mean the tone map forms);  D_p = hit_p ? fmaxf(albedo_p, 1/256) : 1 per channel;  e_p = c_p / D_p
+//   (a context with an environment texture, DESIGN.md §15: D_p = fmaxf(albedo_p, 1/256) for miss pixels too -- their albedo is E(d))
 //   pass i, step s = 2^i, sc_i = sc * 4^i: for the 5x5 taps q = p + s * (dx, dy) inside the frame, dy outer, dx inner:
 //     w = 0 if hit_p != hit_q, else ((k5[dx] * k5[dy] * wc) * wn) * wp  (dn_tap_weight)
 //     num += w * e_q, den += w for taps with w > 0;  e'_p = den > 0 ? num / den : e_p
@@ -40,6 +41,7 @@ MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
         a.g.nx = 0.0f; a.g.ny = 0.0f; a.g.nz = 0.0f; a.g.t = __builtin_inff();
         a.g.px = 0.0f; a.g.py = 0.0f; a.g.pz = 0.0f; a.g.hit = 0.0f;
         a.albedo = v3(0.0f, 0.0f, 0.0f);
+        if constexpr (FEAT & F_ENV) { float sky_pwr; a.albedo = env_color<FEAT>(S, d, sky_pwr); }      // the backdrop the centre ray sees
         a.rend = -1; a.inst = -1;
         return a;
     }
@@ -57,8 +59,8 @@ MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
 // B3 spline taps, k5[dx + 2]
 MRT_HD float dn_k5(int i) { return i == 0 ? 0.375f : ((i == 1 || i == -1) ? 0.25f : 0.0625f); }
 
-// demodulation divisor of one channel
-MRT_HD float dn_demod(float albedo, float hit) { return hit != 0.0f ? __builtin_fmaxf(albedo, kDnAlbedoFloor) : 1.0f; }
+// demodulation divisor of one channel (env: the context has an environment texture, a miss pixel's albedo is its backdrop)
+MRT_HD float dn_demod(float albedo, float hit, bool env = false) { return (hit != 0.0f || env) ? __builtin_fmaxf(albedo, kDnAlbedoFloor) : 1.0f; }
 
 // weight of tap q for pixel p: k = k5[dx] * k5[dy]; sc = sc_i of the pass, sn, sp as formed on the host
 MRT_HD float dn_tap_weight(float k, const float *ep, const float *eq, const DnGuide &gp, const DnGuide &gq, float sc, float sn, float sp)

@@ -171,7 +171,8 @@ size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 f
 // four feature sets per shape -- plain primitives without / with lights (sphere and plane crowds), everything but
 // triangles and meshes, everything -- of which the smallest covering one runs (a Minecraft-shaped scene without the
 // triangle / mesh code: 113 VGPRs and no scratch instead of 128 + 72 B, +15 %).  Scenes with per-corner attributes (F_VATTR)
-// always take the full set.  Reported in mrt_stats.kernel_features.
+// always take the full set, and so do scenes with an environment texture (F_ENV, which comes with F_VATTR).  Reported in
+// mrt_stats.kernel_features.
 u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features)
 {
     constexpr u32 FN = F_ALL & ~F_TRI;
@@ -181,7 +182,7 @@ u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features)
     if (cold && (features & F_DEEP) && (need & F_TRI)) cold |= F_DEEP;               // ... and the deep ones with the mesh code only
     const u32 nostash = (scene_in_lds && block_threads == 1024u && (features & F_NOSTASH) && !cold) ? (u32)F_NOSTASH : 0u;
     // per-corner attributes (the scene has a triangle or a mesh): the full feature set in every shape and staging level
-    if (features & F_VATTR) return F_ALL | F_VATTR | (features & F_BVH) | (scene_in_lds ? cold | nostash : 0u);
+    if (features & F_VATTR) return F_ALL | F_VATTR | (features & (F_BVH | F_ENV)) | (scene_in_lds ? cold | nostash : 0u);
     if (features & F_BVH) {
         if (!scene_in_lds) return big | F_BVH;
         const u32 pick = (need & (F_BOX | F_TRI | F_MAPS)) == 0 ? (need & F_LIGHTS) : big;

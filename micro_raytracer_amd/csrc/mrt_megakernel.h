@@ -69,13 +69,17 @@ constexpr int waves_for(u32 feat_, int block_threads)
 // kernel without and one with the instance BVH.
 #define MRT_VATTR2(T, X) MRT_CASE(T, F_ALL | F_VATTR | (X)) MRT_CASE(T, F_ALL | F_BVH | F_VATTR | (X))
 #define MRT_VATTR6(T) MRT_VATTR2(T, 0u) MRT_VATTR2(T, F_COLD) MRT_VATTR2(T, F_COLD | F_DEEP)
-#define MRT_SHAPES_64 MRT_PLAIN16(64) MRT_BVH4(64, 0u) MRT_VATTR2(64, 0u)
+// Scenes with an environment texture (F_ENV) likewise, on top of F_VATTR: the same family once more.
+#define MRT_ENV2(T, X) MRT_VATTR2(T, F_ENV | (X))
+#define MRT_ENV6(T) MRT_ENV2(T, 0u) MRT_ENV2(T, F_COLD) MRT_ENV2(T, F_COLD | F_DEEP)
+#define MRT_SHAPES_64 MRT_PLAIN16(64) MRT_BVH4(64, 0u) MRT_VATTR2(64, 0u) MRT_ENV2(64, 0u)
 #define MRT_SHAPES_256 MRT_PLAIN16(256) MRT_IDENT4(256) MRT_BVH4(256, 0u) MRT_IDENT_BVH2(256) MRT_BIG2(256, F_COLD) MRT_BVH4(256, F_COLD) MRT_DEEP2(256) \
-    MRT_VATTR6(256)
-#define MRT_SHAPES_512 MRT_BIG2(512, 0u) MRT_BVH4(512, 0u) MRT_IDENT_BVH2(512) MRT_BIG2(512, F_COLD) MRT_BVH4(512, F_COLD) MRT_DEEP2(512) MRT_VATTR6(512)
+    MRT_VATTR6(256) MRT_ENV6(256)
+#define MRT_SHAPES_512 MRT_BIG2(512, 0u) MRT_BVH4(512, 0u) MRT_IDENT_BVH2(512) MRT_BIG2(512, F_COLD) MRT_BVH4(512, F_COLD) MRT_DEEP2(512) MRT_VATTR6(512) MRT_ENV6(512)
 #define MRT_SHAPES_1024 MRT_BIG2(1024, 0u) MRT_BVH4(1024, 0u) MRT_IDENT_BVH2(1024) MRT_BIG2(1024, F_NOSTASH) MRT_BVH4(1024, F_NOSTASH) \
-    MRT_BIG2(1024, F_COLD) MRT_BVH4(1024, F_COLD) MRT_DEEP2(1024) MRT_VATTR6(1024) MRT_VATTR2(1024, F_NOSTASH)
+    MRT_BIG2(1024, F_COLD) MRT_BVH4(1024, F_COLD) MRT_DEEP2(1024) MRT_VATTR6(1024) MRT_VATTR2(1024, F_NOSTASH) MRT_ENV6(1024) MRT_ENV2(1024, F_NOSTASH)
 #define MRT_SHAPES_L2 MRT_CASE_L2(F_ALL & ~F_TRI) MRT_CASE_L2(F_ALL) MRT_CASE_L2((F_ALL & ~F_TRI) | F_BVH) MRT_CASE_L2(F_ALL | F_BVH) \
-    MRT_CASE_L2(F_ALL | F_VATTR) MRT_CASE_L2(F_ALL | F_BVH | F_VATTR)
+    MRT_CASE_L2(F_ALL | F_VATTR) MRT_CASE_L2(F_ALL | F_BVH | F_VATTR) \
+    MRT_CASE_L2(F_ALL | F_VATTR | F_ENV) MRT_CASE_L2(F_ALL | F_BVH | F_VATTR | F_ENV)
 
 }  // namespace mrt

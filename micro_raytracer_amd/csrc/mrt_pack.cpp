@@ -377,12 +377,13 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     if ((sc.n_renderer && !sc.renderer) || (sc.n_light && !sc.light) || (sc.n_textures && !sc.textures)) {
         err = "null array with non-zero count"; return MRT_ERR_ARG;
     }
-    if (ext && ext->n_renderer != sc.n_renderer) {
+    const mrt_tri_attrs *attrs = ext ? ext->attrs : nullptr;      // NULL: no attributes, whatever n_renderer says
+    const mrt_env *env = ext ? ext->env : nullptr;
+    if (attrs && ext->n_renderer != sc.n_renderer) {
         snprintf(msg, sizeof msg, "attributes for %u renderers, the scene has %u", ext->n_renderer, sc.n_renderer); err = msg; return MRT_ERR_SCENE;
     }
-    if (ext && ext->n_renderer && !ext->attrs) { err = "null attribute array"; return MRT_ERR_ARG; }
-    auto uv_of = [&](u32 r) { return ext ? ext->attrs[r].uv : nullptr; };
-    auto vn_of = [&](u32 r) { return ext ? ext->attrs[r].vn : nullptr; };
+    auto uv_of = [&](u32 r) { return attrs ? attrs[r].uv : nullptr; };
+    auto vn_of = [&](u32 r) { return attrs ? attrs[r].vn : nullptr; };
     out = Packed();
     Params &P = out.P;
     memset(&P, 0, sizeof P);
@@ -410,6 +411,35 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     if (P.bounce > 0x0fffffffu) { err = "bounce too large"; return MRT_ERR_LIMIT; }
     P.q = 1.0f - min_num(d->rt.loss, 1.0f);
     for (int k = 0; k < 3; ++k) { P.sky[k] = sc.sky.color[k]; P.sky_init[k] = sc.sky.color[k] * sc.sky.pwr; }
+    if (env) {
+        // the sky's environment texture (mrt.h mrt_env): validated here; a path that runs out of bounces did not
+        // escape in any direction and takes the texture's solid-angle-weighted mean m in the texel's place:
+        // sky_init = (sky.color x m) * sky.pwr, m summed in float64 in row-major order and rounded once
+        const mrt_texture &tx = env->tex;
+        if (tx.w == 0 || tx.h == 0) { snprintf(msg, sizeof msg, "env.tex: %ux%u texels", tx.w, tx.h); err = msg; return MRT_ERR_SCENE; }
+        if (!tx.dat) { err = "env.tex.dat is null"; return MRT_ERR_SCENE; }
+        if (env->mapping > MRT_ENV_LATLONG) { snprintf(msg, sizeof msg, "env.mapping %u unknown", env->mapping); err = msg; return MRT_ERR_SCENE; }
+        if (!std::isfinite(env->rot)) { err = "env.rot is not finite"; return MRT_ERR_SCENE; }
+        if ((unsigned long long)tx.w * tx.h > (1ull << 25)) { snprintf(msg, sizeof msg, "env.tex: %ux%u is more than 2^25 texels", tx.w, tx.h); err = msg; return MRT_ERR_LIMIT; }
+        double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
+        const double pi = 3.14159265358979323846;
+        for (u32 y = 0; y < tx.h; ++y) {
+            const double wy = env->mapping == MRT_ENV_LATLONG ? cos(pi * y / tx.h) - cos(pi * (y + 1.0) / tx.h) : 1.0;
+            const float *row = tx.dat + (size_t)y * tx.w * 3;
+            for (u32 x = 0; x < tx.w; ++x) {
+                for (int k = 0; k < 3; ++k) {
+                    const float v = row[(size_t)x * 3 + k];
+                    if (!(std::isfinite(v) && v >= 0.0f)) {
+                        snprintf(msg, sizeof msg, "env.tex: texel (%u, %u) is negative or not finite", x, y); err = msg; return MRT_ERR_SCENE;
+                    }
+                    num[k] += wy * (double)v;
+                }
+                den += wy;
+            }
+        }
+        for (int k = 0; k < 3; ++k) P.sky_init[k] = (sc.sky.color[k] * (float)(num[k] / den)) * sc.sky.pwr;
+        out.features |= 512u | 1024u;                                                // F_VATTR | F_ENV: the full feature set
+    }
 
     // ---- validation: everything the reference would panic on is refused here ----
     for (u32 t = 0; t < sc.n_textures; ++t) {
@@ -845,6 +875,32 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         out.off_vattr = B.align4(); for (float v : vattr_tab) B.f(v);
         out.n_vattr_rows = (u32)(vattr_tab.size() / VATTR_WORDS);
         for (const auto &rf : vattr_first) B.w[P.off_rend + (size_t)rf.first * REND_WORDS + REND_VATTR] = out.off_vattr + rf.second * VATTR_WORDS;
+    }
+    if (env) {
+        // the environment's texels and its ENV record: behind everything a kernel may stage, like the attribute table; the texel
+        // formats of the material textures above (RGB8 when every texel is exactly k/255, else f32), written in bulk
+        const mrt_texture &tx = env->tex;
+        const size_t n = (size_t)tx.w * tx.h * 3;
+        bool exact = true;
+        for (size_t i = 0; i < n && exact; ++i) {
+            const float v = tx.dat[i];
+            const float kf = rintf(v * 255.0f);
+            exact = kf >= 0.0f && kf <= 255.0f && bits(kf / 255.0f) == bits(v);
+        }
+        const size_t at = B.align4();
+        // TEX_OFF is a 32-bit offset: bytes for RGB8 texels, words for f32 ones
+        if ((exact ? at * 4 + n : at + n) > 0xfffffff0ull) { err = "env.tex: the packed scene is too large for 32-bit texel offsets"; return MRT_ERR_LIMIT; }
+        if (exact) {
+            B.w.resize(at + (n + 3) / 4, 0);
+            unsigned char *bytes = reinterpret_cast<unsigned char *>(B.w.data() + at);
+            for (size_t i = 0; i < n; ++i) bytes[i] = (unsigned char)rintf(tx.dat[i] * 255.0f);
+        } else {
+            B.w.resize(at + n);
+            memcpy(B.w.data() + at, tx.dat, n * sizeof(float));
+        }
+        P.off_env = B.align4();
+        B.u(tx.w); B.u(tx.h); B.u(exact ? (u32)(at * 4) : (u32)at); B.u(exact ? (u32)TEXFMT_U8 : (u32)TEXFMT_F32);
+        B.u(env->mapping); B.f(env->rot); B.f(sc.sky.pwr); B.u(0u);
     }
     B.align4();
     P.blob_words = (u32)B.w.size();

@@ -13,6 +13,8 @@
 //   instance   R = rotate_y(-dir), L = lookat(-dir, up)  src/rt.rs:726-727
 //   light      norm(-(norm(dir))) for directional lights src/rt.rs:1031-1034
 #pragma once
+#include <stddef.h>
+
 #include "mrt_math.h"
 
 namespace mrt {
@@ -67,6 +69,13 @@ enum : u32 { LIGHT_KIND = 0, LIGHT_V = 1, LIGHT_PWR = 4, LIGHT_COLOR = 5 };
 // TEX: [0] w [1] h [2] offset (words for f32 texels, bytes for u8 texels, from blob start) [3] format
 enum : u32 { TEX_W = 0, TEX_H = 1, TEX_OFF = 2, TEX_FMT = 3 };
 enum : u32 { TEXFMT_NONE = 0, TEXFMT_F32 = 1, TEXFMT_U8 = 2 };
+
+// ENV (the sky's environment texture, mrt.h mrt_env): one record of ENV_WORDS words at Params.off_env, behind the
+// octree leaf lists and the attribute table like the texels it describes -- never staged, read from global memory at a miss:
+//   [0] w [1] h [2] texel offset (as TEX_OFF) [3] format (TEXFMT_F32 | TEXFMT_U8) [4] mapping (MRT_ENV_*) [5] rot (f32) [6] sky.pwr (f32) [7] 0
+enum : u32 { ENV_W = 0, ENV_H = 1, ENV_OFF = 2, ENV_FMT = 3, ENV_MAP = 4, ENV_ROT = 5, ENV_PWR = 6 };
+constexpr u32 ENV_WORDS = 8;
+enum : u32 { ENVMAP_SPHERE = 0, ENVMAP_LATLONG = 1 };
 
 // MESH: [0] first triangle [1] triangle count [2] root node (0xffffffff: no octree) [3] leaf-id base
 //       [4] root of the mesh's triangle BVH: node index in the TBVH table, binary or 4-wide (0xffffffff: none)  [5] number of ids in the mesh's octree leaf lists
@@ -141,7 +150,7 @@ struct Params {
     float cam_L[9], cam_R[9];   // lookat(cam.dir, up), rotate_y(cam.dir), src/rt.rs:925-927
     u32 cam_ident;              // both equal the identity as values
     float sky[3];
-    float sky_init[3];       // sky.color * sky.pwr, src/rt.rs:964
+    float sky_init[3];       // sky.color * sky.pwr, src/rt.rs:964 (with an environment texture: (sky.color x its mean) * sky.pwr)
     // scene tables
     u32 n_rend, n_light, n_inst;
     u32 n_lin, n_bvh_nodes;   // instance BVH: linear-list length, node count (0: every instance is scanned linearly)
@@ -176,7 +185,10 @@ struct Params {
     unsigned long long *segments;
     u32 *tile_counter;       // persistent launches: next (tile, sample-split lane) index, zeroed before the launch
     u32 persist_grid;        // workgroups of a persistent launch (0: one workgroup per tile block, blockIdx addresses the tiles)
+    u32 off_env;             // the ENV record of the sky's environment texture (F_ENV kernels; 0: none).  The last word of the block:
+                             // it takes what was the struct's tail padding, so the argument block keeps its size and every offset
 };
+static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, off_env) + 4 == sizeof(Params), "off_env fills the tail of Params");
 
 // Tile-list launches (adaptive sampling, mrt_execute_adaptive): only the n 8x8 wave tiles tiles[i] = ty * n_tx + tx are traced.
 // A kernel argument of its own (pt_megakernel_list), not a Params field: the ordinary launches keep their argument block.

@@ -36,6 +36,9 @@ enum : u32 {
                       // ~30 of ~220 cycles per instance on the Cornell box (8236 -> 8700 Msamples/s).  Exists for the plain
                       // 256-thread kernels of planes / spheres / boxes with and without lights; rays whose shifted origin has a
                       // zero, infinite or NaN component still take the reference's two mat-vecs (xf_vec)
+    F_ENV = 1024u,    // the sky has an environment texture (mrt.h mrt_env): env_uv / env_color at the two miss sites of
+                      // render_pixel.  Like F_VATTR it exists with the full feature set only, and always together with F_VATTR
+                      // (F_ALL | F_VATTR | F_ENV plus the shape markers and F_BVH)
     F_VATTR = 512u    // some triangle / mesh renderer carries per-corner normals or UVs (mrt.h mrt_desc_ext):
                       // the interpolation of hit_normal / hit_uv.  Exists with the full feature set only (F_ALL | F_VATTR plus the
                       // shape markers and F_BVH)
@@ -357,6 +360,52 @@ MRT_HD V3 tex_fetch(const Scn &S, i32 id, UV uv)
         return v3(L[B[0]], L[B[1]], L[B[2]]);
     }
     return ld3(X, off + i * 3u);
+}
+
+// The sky's environment texture (F_ENV kernels).  env_uv: the texture coordinate of direction d -- the
+// sphere's UV of hit_uv (src/rt.rs:468-476) or the equirectangular one, u shifted by rot turns and wrapped like the plane's; d is
+// the ray direction as the kernel holds it, not normalised again.
+MRT_HD UV env_uv(u32 mapping, float rot, V3 d)
+{
+    UV r;
+    const float u0 = 0.5f + div_(0.5f * atan2_(d.x, -d.y), kPi);
+    float u = u0 + rot;
+    u = u - trunc_(u);
+    if (u < 0.0f) u = 1.0f + u;
+    r.x = u;
+    if (mapping == ENVMAP_LATLONG) r.y = div_(acos_(fmin_(fmax_(d.z, -1.0f), 1.0f)), kPi);
+    else r.y = 0.5f - 0.5f * d.z;
+    return r;
+}
+// flat texel index of a coordinate: tex_fetch's rule
+MRT_HD u32 env_index(UV uv, u32 w, u32 h)
+{
+    const uint64_t x = to_index(uv.x * (float)w);
+    const uint64_t y = to_index(uv.y * (float)h);
+    uint64_t idx = x + y * (uint64_t)w;
+    const uint64_t last = (uint64_t)w * h - 1;
+    if (idx > last) idx = last;
+    return (u32)idx;
+}
+// E(d) = sky.color x texel, read from global memory at every staging level; pwr_out = sky.pwr (word 6 of the ENV record)
+template <u32 FEAT>
+MRT_HD V3 env_color(const Scn &S, V3 d, float &pwr_out)
+{
+    const Params &P = *S.P;
+    const float *E = S.G + P.off_env;
+    const u32 w = ldu(E, ENV_W), h = ldu(E, ENV_H), fmt = ldu(E, ENV_FMT), off = ldu(E, ENV_OFF);
+    pwr_out = E[ENV_PWR];
+    const size_t i = (size_t)env_index(env_uv(ldu(E, ENV_MAP), E[ENV_ROT], d), w, h) * 3u;
+    V3 t;
+    if (fmt == TEXFMT_U8) {
+        const unsigned char *B = reinterpret_cast<const unsigned char *>(S.G) + ((size_t)off + i);
+        const float *L = S.F + P.off_lut;
+        t = v3(L[B[0]], L[B[1]], L[B[2]]);
+    } else {
+        const float *X = S.G + ((size_t)off + i);
+        t = v3(X[0], X[1], X[2]);
+    }
+    return hadam(v3(P.sky[0], P.sky[1], P.sky[2]), t);
 }
 
 // ---- one closest-hit candidate ----
@@ -1481,7 +1530,14 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
         MRT_TICK(0);                                                   // the closest-hit query
         if (!hit_any) {
             // primary miss: raw sky colour (src/rt.rs:957-959); otherwise the fold starts from sky*pwr (:964)
-            contrib = (b == 0) ? v3(P.sky[0], P.sky[1], P.sky[2]) : add(getL(), hadam(getT(), sky_init));
+            if constexpr (FEAT & F_ENV) {
+                // environment texture: E(d) in the sky colour's place; a later miss scales it by sky.pwr
+                float sky_pwr;
+                const V3 e = env_color<FEAT>(S, d, sky_pwr);
+                contrib = (b == 0) ? e : add(getL(), hadam(getT(), muls(e, sky_pwr)));
+            } else {
+                contrib = (b == 0) ? v3(P.sky[0], P.sky[1], P.sky[2]) : add(getL(), hadam(getT(), sky_init));
+            }
             ended = true;
         } else {
             MRT_PROBE(PH_SHADE);

@@ -35,9 +35,11 @@ public:
     // The context is created on the first call (scene and frame only arrive here) and rebuilt when a later call passes
     // a description with other contents; sums accumulated so far are carried over when the supersampled frame keeps its
     // size (the reference's map keeps adding whatever the scene, src/sampler.rs:60-70).
-    double execute(const mrt_render_desc &render, uint32_t n_samples = 1)
+    // ext (optional): per-corner attributes / the sky's environment texture (mrt_desc_ext); the context is then created through
+    // mrt_create_ext, and the environment is part of the fingerprint.
+    double execute(const mrt_render_desc &render, uint32_t n_samples = 1, const mrt_desc_ext *ext = nullptr)
     {
-        const uint64_t print = fingerprint(render);
+        const uint64_t print = fingerprint(render, ext);
         if (!ctx_ || print != print_ || stale_) {
             stale_ = false;
             mrt_opts o{};
@@ -45,7 +47,7 @@ public:
             o.seed = seed_;
             o.device = device_;
             o.flags = flags_;
-            mrt_ctx *fresh = mrt_create(&render, &o);
+            mrt_ctx *fresh = ext ? mrt_create_ext(&render, &o, ext) : mrt_create(&render, &o);
             if (!fresh) throw std::runtime_error(mrt_last_error());
             uint32_t nw = 0, nh = 0;
             mrt_dims(fresh, &nw, &nh, nullptr);
@@ -112,7 +114,7 @@ private:
         template <class T> void pod(const T &v) { bytes(&v, sizeof v); }
         void bulk(const float *p, size_t n) { pod(p); pod(n); if (!p) return; const size_t step = 1 + n / 1024; for (size_t i = 0; i < n; i += step) pod(p[i]); }
     };
-    uint64_t fingerprint(const mrt_render_desc &d)
+    uint64_t fingerprint(const mrt_render_desc &d, const mrt_desc_ext *ext = nullptr)
     {
         Fnv f;
         f.pod(d.rt.bounce); f.pod(d.rt.loss);
@@ -130,6 +132,10 @@ private:
         }
         for (uint32_t i = 0; i < d.scene.n_light; ++i) { const mrt_light &l = d.scene.light[i]; f.pod(l.kind); f.pod(l.v); f.pod(l.pwr); f.pod(l.color); }
         for (uint32_t i = 0; i < d.scene.n_textures; ++i) { const mrt_texture &t = d.scene.textures[i]; f.pod(t.w); f.pod(t.h); f.bulk(t.dat, t.dat ? (size_t)t.w * t.h * 3 : 0); }
+        if (ext && ext->env) {      // the environment texture: texels hashed like other bulk data
+            const mrt_env &e = *ext->env;
+            f.pod(e.tex.w); f.pod(e.tex.h); f.pod(e.mapping); f.pod(e.rot); f.bulk(e.tex.dat, e.tex.dat ? (size_t)e.tex.w * e.tex.h * 3 : 0);
+        }
         return f.h;
     }
 

@@ -62,6 +62,8 @@ class Texture:
             arr = None if dat is None else np.asarray(dat, dtype=np.float64).astype(np.float32).reshape(-1, 3)
             return Texture(int(obj.get("w", 0)), int(obj.get("h", 0)), arr)
         if isinstance(obj, str):
+            if obj.lower().endswith(".hdr"):  # Radiance RGBE (not in the reference): float texels, may exceed 1
+                return read_hdr(os.path.join(base_dir, obj))
             if "." in obj:  # file name (src/parser.rs:688-689)
                 from PIL import Image
                 im = Image.open(os.path.join(base_dir, obj))
@@ -78,6 +80,68 @@ class Texture:
         """TextureWrapper::to_inline, src/parser.rs:698-710."""
         obj = {"w": self.w, "h": self.h, "dat": None if self.dat is None else [[float(x) for x in t] for t in self.dat]}
         return base64.b64encode(gzip.compress(json.dumps(obj).encode(), 9)).decode()
+
+
+def read_hdr(path) -> "Texture":
+    """A Radiance picture (header `#?RADIANCE` / `#?RGBE`, FORMAT=32-bit_rle_rgbe, resolution `-Y h +X w`; flat and new-style
+    run-length scanlines) as a Texture: a pixel (r, g, b, e) is 0 for e == 0, else m * 2^(e - 136) per mantissa byte m --
+    exact in f32.  Other orientations, a malformed header and truncated pixel data: ValueError."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    lines, pos = [], 0
+    while True:
+        end = buf.find(b"\n", pos)
+        if end < 0:
+            raise ValueError(f"{path}: truncated Radiance header")
+        line, pos = buf[pos:end], end + 1
+        if not line:
+            break
+        lines.append(line)
+    if not lines or lines[0] not in (b"#?RADIANCE", b"#?RGBE"):
+        raise ValueError(f"{path}: not a Radiance picture (#?RADIANCE / #?RGBE)")
+    fmt = [ln.split(b"=", 1)[1].strip() for ln in lines if ln.startswith(b"FORMAT=")]
+    if fmt != [b"32-bit_rle_rgbe"]:
+        raise ValueError(f"{path}: FORMAT must be 32-bit_rle_rgbe")
+    end = buf.find(b"\n", pos)
+    if end < 0:
+        raise ValueError(f"{path}: truncated Radiance header (no resolution line)")
+    res = buf[pos:end].split()
+    if len(res) != 4 or res[0] != b"-Y" or res[2] != b"+X" or not (res[1].isdigit() and res[3].isdigit()):
+        raise ValueError(f"{path}: resolution line must be `-Y h +X w`")
+    h, w, pos = int(res[1]), int(res[3]), end + 1
+    if w <= 0 or h <= 0:
+        raise ValueError(f"{path}: empty picture")
+    px = np.zeros((h, w, 4), np.uint8)
+    for y in range(h):
+        if 8 <= w < 32768 and len(buf) >= pos + 4 and buf[pos:pos + 2] == b"\x02\x02" and (buf[pos + 2] << 8 | buf[pos + 3]) == w:
+            pos += 4                                     # new-style run-length scanline: the four channels one after another
+            for ch in range(4):
+                x = 0
+                while x < w:
+                    if pos + 2 > len(buf):              # a run is at least its count and one byte
+                        raise ValueError(f"{path}: truncated pixel data in scanline {y}")
+                    n = buf[pos]
+                    if n > 128:
+                        n -= 128
+                        if n == 0 or x + n > w:
+                            raise ValueError(f"{path}: bad run in scanline {y}")
+                        px[y, x:x + n, ch] = buf[pos + 1]
+                        pos += 2
+                    else:
+                        if n == 0 or x + n > w or pos + 1 + n > len(buf):
+                            raise ValueError(f"{path}: bad run in scanline {y}")
+                        px[y, x:x + n, ch] = np.frombuffer(buf, np.uint8, n, pos + 1)
+                        pos += 1 + n
+                    x += n
+        else:                                            # flat scanline
+            if pos + 4 * w > len(buf):
+                raise ValueError(f"{path}: truncated pixel data")
+            px[y] = np.frombuffer(buf, np.uint8, 4 * w, pos).reshape(w, 4)
+            pos += 4 * w
+    e = px[..., 3].astype(np.int32)
+    scale = np.where(e == 0, f32(0.0), np.ldexp(f32(1.0), e - 136)).astype(np.float32)
+    dat = (px[..., :3].astype(np.float32) + f32(0.0)) * scale[..., None]
+    return Texture(w, h, dat.reshape(-1, 3).astype(np.float32))
 
 
 @dataclass
@@ -303,8 +367,13 @@ class Light:
 
 @dataclass
 class Sky:
+    """rt::Sky, src/rt.rs:178-181, plus the optional environment texture (not in the reference; DESIGN.md section 15): `tex`
+    multiplies `color` per direction; mapping "sphere" | "latlong"; rot in turns about +z."""
     color: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
     pwr: float = 0.5
+    tex: Optional[Texture] = None
+    mapping: str = "sphere"
+    rot: float = 0.0
 
 
 @dataclass
@@ -388,6 +457,13 @@ def load_render(src, base_dir=".") -> Render:
     sky = sc.get("sky", {})
     out.scene.sky = Sky(parse_color(sky["color"]) if "color" in sky else np.zeros(3, np.float32),
                         float(f32(sky.get("pwr", 0.5))))
+    if sky.get("tex") is not None:
+        src_tex = sky["tex"]
+        out.scene.sky.tex = src_tex if isinstance(src_tex, Texture) else Texture.from_json(src_tex, base_dir)
+        out.scene.sky.mapping = str(sky.get("map", "sphere"))
+        if out.scene.sky.mapping not in ("sphere", "latlong"):
+            raise ValueError(f"sky map `{out.scene.sky.mapping}` is unexpected (sphere | latlong)")
+        out.scene.sky.rot = float(f32(sky.get("rot", 0.0)))
     return out
 
 
@@ -428,11 +504,14 @@ def dump_render(r: Render) -> dict:
     for l in r.scene.light:
         lights.append({"type": l.kind, ("pos" if l.kind == "point" else "dir"): fl(l.v), "pwr": l.pwr, "color": fl(l.color)})
     cam = r.frame.cam
+    sky = {"color": fl(r.scene.sky.color), "pwr": r.scene.sky.pwr}
+    if r.scene.sky.tex is not None:       # the three keys of the environment only when there is one
+        sky.update({"tex": tex(r.scene.sky.tex), "map": r.scene.sky.mapping, "rot": r.scene.sky.rot})
     return {
         "rt": {"bounce": r.rt.bounce, "sample": r.rt.sample, "loss": r.rt.loss},
         "frame": {"res": list(r.frame.res), "ssaa": r.frame.ssaa,
                   "cam": {"pos": fl(cam.pos), "dir": fl(cam.dir), "fov": cam.fov, "gamma": cam.gamma,
                           "exp": cam.exp, "aprt": cam.aprt, "foc": cam.foc}},
         "scene": {"renderer": rend or None, "light": lights or None,
-                  "sky": {"color": fl(r.scene.sky.color), "pwr": r.scene.sky.pwr}},
+                  "sky": sky},
     }

@@ -189,6 +189,45 @@ def smooth_mesh_scene(res=(1920, 1080), ssaa=1, sample=256, bounce=8, n_tris=967
     return d
 
 
+def sky_texture(w=256, h=128, mapping="sphere", sun=(0.31, 0.55), sun_radiance=50.0):
+    """A procedural HDR sky as a texture buffer (`dat` an (w*h, 3) float32 array, row 0 = up): a vertical gradient from a pale
+    horizon to a deep zenith, a dim ground below a bright horizon band, and a sun disc of radiance ~sun_radiance a few texels
+    wide at u = sun[0], height z = sun[1].  Laid out for `mapping` ("sphere": rows equal in z; "latlong": rows equal in angle),
+    so that both mappings show the same sky."""
+    v = (np.arange(h) + 0.5) / h
+    z = (1.0 - 2.0 * v) if mapping == "sphere" else np.cos(math.pi * v)
+    a = 2.0 * math.pi * ((np.arange(w) + 0.5) / w - 0.5)
+    zz, aa = np.meshgrid(z, a, indexing="ij")
+    r = np.sqrt(np.maximum(1.0 - zz * zz, 0.0))
+    d = np.stack([np.sin(aa) * r, -np.cos(aa) * r, zz], -1)
+    up = np.clip(zz, 0.0, 1.0)[..., None]
+    sky = (1.0 - up) * np.array([0.95, 0.85, 0.75]) + up * np.array([0.25, 0.45, 0.9])
+    ground = np.array([0.18, 0.16, 0.14]) * (1.0 + 0.5 * np.clip(zz, -1.0, 0.0))[..., None]
+    img = np.where(zz[..., None] >= 0.0, sky, ground)
+    img = img + np.exp(-(zz / 0.06) ** 2)[..., None] * np.array([0.9, 0.8, 0.6])           # the horizon band
+    sa, sz = 2.0 * math.pi * (sun[0] - 0.5), sun[1]
+    sr = math.sqrt(1.0 - sz * sz)
+    sd = np.array([math.sin(sa) * sr, -math.cos(sa) * sr, sz])
+    disc = np.sum(d * sd, -1) > math.cos(max(2.5 * math.pi / h, 0.03))
+    img = np.where(disc[..., None], np.array([1.0, 0.92, 0.8]) * sun_radiance, img)
+    return {"w": int(w), "h": int(h), "dat": img.reshape(-1, 3).astype(np.float32)}
+
+
+def env_scene(res=(1280, 720), sample=64, bounce=8, mapping="sphere", tex_res=(256, 128)):
+    """A chrome sphere, a glass sphere and the smooth textured mesh of smooth_mesh_scene on a rough plane, lit by nothing but a
+    procedural HDR environment (sky_texture): the scene of DESIGN.md section 15.  No lights."""
+    d = smooth_mesh_scene(res, 1, sample, bounce)
+    d["scene"]["light"] = []
+    d["scene"]["renderer"][1]["mat"] = {"rough": 1, "albedo": [0.7, 0.7, 0.7]}
+    d["scene"]["renderer"] += [
+        {"type": "sphere", "r": 0.22, "pos": [-0.62, 0.25, -0.28], "mat": {"metal": 1, "rough": 0, "albedo": [0.9, 0.9, 0.9]}},
+        {"type": "sphere", "r": 0.2, "pos": [0.6, 0.1, -0.3], "mat": {"glass": 0.08, "opacity": 0}},
+    ]
+    d["scene"]["sky"] = {"color": [1.0, 1.0, 1.0], "pwr": 0.6, "tex": sky_texture(tex_res[0], tex_res[1], mapping),
+                         "map": mapping, "rot": 0.0}
+    return d
+
+
 def _atlas_texture(w=64, h=48, seed=0, base=(0.6, 0.45, 0.3)):
     """Procedural 4x3 box cross atlas with k/255 texels."""
     rng = np.random.default_rng(seed)
