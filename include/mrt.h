@@ -365,7 +365,7 @@ int mrt_plan_launch(const mrt_render_desc *desc, mrt_plan *out);
  * Optional smooth shading normals and texture coordinates, one entry per corner in the order of the renderer's vertices
  * (a MRT_KIND_TRIANGLE renderer counts as n_tris = 1).  Either pointer may be NULL:
  *   uv[n_tris][3][2]   texture coordinates (finite); the hit's UV is interpolated, wrapped into [0, 1) like a plane's and looked up
- *                      nearest-texel.  Only a renderer WITH uv may carry texture maps (mrt_material.tex ... emap).
+ *                      like a plane's (nearest texel, or the scene's filter).  Only a renderer WITH uv may carry texture maps (mrt_material.tex ... emap).
  *   vn[n_tris][3][3]   object-space normals, any length; the shading normal is interpolated and replaces the face normal
  *                      wherever the path tracer uses one (a degenerate triangle or a zero / non-finite result: the face normal).
  * attrs[r] belongs to scene.renderer[r]; n_renderer must equal scene.n_renderer.  Attributes on a sphere, plane or box, or a
@@ -378,22 +378,33 @@ typedef struct mrt_tri_attrs {
 /* ---- environment texture of the sky (not in the reference) -------------------------------------
  * The texel the direction d of an escaping ray maps to multiplies sky.color, as a material's tex multiplies its albedo:
  * E(d) = sky.color x texel.  A primary miss contributes E(d), a later miss L + T x (E(d) * sky.pwr); a path that runs out of
- * bounces takes the texture's solid-angle-weighted mean in the texel's place.  Nearest texel, no filtering, no importance
- * sampling.  Mappings (u is then shifted by rot and wrapped into [0, 1) like a plane's):
+ * bounces takes the texture's solid-angle-weighted mean in the texel's place.  Nearest texel unless filter asks for the bilinear
+ * filter (below); no importance sampling.  Mappings (u is then shifted by rot and wrapped into [0, 1) like a plane's):
  *   MRT_ENV_SPHERE   the sphere renderer's UV of the direction: u = 0.5 + atan2(d.x, -d.y) / 2pi, v = 0.5 - 0.5 d.z
  *   MRT_ENV_LATLONG  equirectangular: the same u, v = acos(d.z) / pi
- * Rejected with MRT_ERR_SCENE: w == 0, h == 0, dat == NULL, a non-finite or negative texel, an unknown mapping, a non-finite rot;
- * with MRT_ERR_LIMIT: more than 2^25 texels. */
+ * Rejected with MRT_ERR_SCENE: w == 0, h == 0, dat == NULL, a non-finite or negative texel, an unknown mapping, a non-finite rot,
+ * an unknown filter; with MRT_ERR_LIMIT: more than 2^25 texels.
+ *
+ * Texture filters: MRT_FILTER_NEAREST is the lookup described above.  MRT_FILTER_BILINEAR blends the four texels
+ * around the coordinate (texel centres at i + 0.5, f32, unfused): u repeats; v repeats too for a material texture on a plane,
+ * box, triangle or mesh, and is clamped to the first / last row for the environment (the poles) and for a material texture on
+ * a sphere.  A path that runs out of bounces keeps the unfiltered mean.  Selected separately for the environment
+ * (mrt_env.filter) and, with one scene-wide switch, for the material textures (mrt_desc_ext.reserved[0]). */
 #define MRT_ENV_SPHERE  0u
 #define MRT_ENV_LATLONG 1u
+#define MRT_FILTER_NEAREST  0u
+#define MRT_FILTER_BILINEAR 1u
 typedef struct mrt_env {
     mrt_texture tex;        /* w x h f32 RGB texels, row 0 = +z; values finite and >= 0, may exceed 1 (HDR) */
     uint32_t mapping;       /* MRT_ENV_* */
     float rot;              /* turns about +z added to u; finite */
-    uint32_t reserved[4];
+    uint32_t filter;        /* MRT_FILTER_* (the first word of what was reserved[4]: a caller that zeroed it asks for nearest) */
+    uint32_t reserved[3];
 } mrt_env;
 
-/* attrs == NULL: no attributes, whatever n_renderer says (an ext that only carries env); env == NULL: no environment. */
+/* attrs == NULL: no attributes, whatever n_renderer says (an ext that only carries env); env == NULL: no environment.
+ * reserved[0] is the MRT_FILTER_* of the scene's material textures (mrt_material.tex ... emap of every renderer; another value:
+ * MRT_ERR_SCENE); on a scene in which no material has a texture map it changes nothing.  reserved[1] must be 0 (MRT_ERR_ARG). */
 typedef struct mrt_desc_ext {
     uint32_t n_renderer;
     const mrt_tri_attrs *attrs;
@@ -401,8 +412,8 @@ typedef struct mrt_desc_ext {
     uint32_t reserved[2];
 } mrt_desc_ext;
 
-/* mrt_create / mrt_plan_launch of a scene with attributes or an environment; ext == NULL (or neither in it): exactly mrt_create /
- * mrt_plan_launch. */
+/* mrt_create / mrt_plan_launch of a scene with attributes, an environment or filtered textures; ext == NULL (or none of them in
+ * it): exactly mrt_create / mrt_plan_launch. */
 mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext);
 int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mrt_plan *out);
 

@@ -3,14 +3,16 @@
     python -m micro_raytracer_amd scene.json -o out.png [--sample N] [--bounce N] [--seed S] [--update]
                                   [--adaptive THRESHOLD [--min-sample N] [--step N]]
                                   [--denoise [--denoise-passes N]] [--aov PREFIX]
-                                  [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS]
+                                  [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS] [--sky-filter nearest|bilinear]
+                                  [--tex-filter nearest|bilinear]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
 --adaptive renders with a per-tile noise threshold instead (Sampler.execute_adaptive), --sample being the cap.
 --denoise saves the image of the AOV-guided a-trous filter (Sampler.img_denoised) instead of the raw means; --aov writes the
 first-hit normal, albedo and depth as PREFIX.normal.png, PREFIX.albedo.png and PREFIX.depth.png.
 --sky-tex / --sky-map / --sky-rot override the description's environment texture (an image file or a Radiance .hdr), its
-mapping and its rotation about +z.
+mapping and its rotation about +z; --sky-filter / --tex-filter choose the filter of the environment texture and of the material
+textures (nearest texel, or bilinear).
 """
 import argparse
 import sys
@@ -65,6 +67,8 @@ def main(argv=None):
     ap.add_argument("--sky-tex", metavar="FILE", help="environment texture of the sky: an image file or a Radiance .hdr")
     ap.add_argument("--sky-map", choices=("sphere", "latlong"), help="mapping of the environment texture")
     ap.add_argument("--sky-rot", type=float, metavar="TURNS", help="rotation of the environment about +z, in turns")
+    ap.add_argument("--sky-filter", choices=("nearest", "bilinear"), help="filter of the environment texture")
+    ap.add_argument("--tex-filter", choices=("nearest", "bilinear"), help="filter of the material textures")
     a = ap.parse_args(argv)
     if not 0 <= a.denoise_passes <= 8:
         ap.error(f"--denoise-passes {a.denoise_passes} is not in 0..8")
@@ -82,12 +86,16 @@ def main(argv=None):
         render.rt.bounce = a.bounce
     if a.sky_tex is not None:
         render.scene.sky.tex = Texture.from_json(a.sky_tex)
-    if render.scene.sky.tex is None and (a.sky_map is not None or a.sky_rot is not None):
-        ap.error("--sky-map / --sky-rot need an environment texture: \"tex\" on the description's \"sky\", or --sky-tex")
+    if render.scene.sky.tex is None and (a.sky_map is not None or a.sky_rot is not None or a.sky_filter is not None):
+        ap.error("--sky-map / --sky-rot / --sky-filter need an environment texture: \"tex\" on the description's \"sky\", or --sky-tex")
     if a.sky_map is not None:
         render.scene.sky.mapping = a.sky_map
     if a.sky_rot is not None:
         render.scene.sky.rot = float(np.float32(a.sky_rot))
+    if a.sky_filter is not None:
+        render.scene.sky.filter = a.sky_filter
+    if a.tex_filter is not None:
+        render.scene.tex_filter = a.tex_filter
     s = Sampler(seed=a.seed)
     t0 = time.perf_counter()
     if a.adaptive is not None:

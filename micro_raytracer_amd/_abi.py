@@ -94,12 +94,25 @@ ENV_SPHERE, ENV_LATLONG = 0, 1
 ENV_MAPPINGS = {"sphere": ENV_SPHERE, "latlong": ENV_LATLONG}
 
 
+FILTER_NEAREST, FILTER_BILINEAR = 0, 1
+FILTERS = {"nearest": FILTER_NEAREST, "bilinear": FILTER_BILINEAR}
+
+
 class Env(C.Structure):
-    _fields_ = [("tex", Texture), ("mapping", C.c_uint32), ("rot", C.c_float), ("reserved", C.c_uint32 * 4)]
+    _fields_ = [("tex", Texture), ("mapping", C.c_uint32), ("rot", C.c_float), ("filter", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class DescExt(C.Structure):
     _fields_ = [("n_renderer", C.c_uint32), ("attrs", C.POINTER(TriAttrs)), ("env", C.POINTER(Env)), ("reserved", C.c_uint32 * 2)]
+
+    @property
+    def tex_filter(self):
+        """MRT_FILTER_* of the scene's material textures: word 0 of `reserved` (word 1 must stay 0)."""
+        return int(self.reserved[0])
+
+    @tex_filter.setter
+    def tex_filter(self, value):
+        self.reserved[0] = int(value)
 
 
 class Adapt(C.Structure):
@@ -150,12 +163,19 @@ def _f4(dst, src):
         dst[i] = float(np.float32(src[i]))
 
 
+def _filter_id(name, what):
+    if name not in FILTERS:
+        raise ValueError(f"{what} `{name}`: expected one of {sorted(FILTERS)}")
+    return FILTERS[name]
+
+
 class DescHolder:
     """Owns a RenderDesc together with every array it points into."""
 
     def __init__(self):
         self.desc = RenderDesc()
-        self.ext = None        # mrt_desc_ext when a triangle / mesh renderer carries per-corner uv / vn or the sky a texture, else None
+        self.ext = None        # mrt_desc_ext when a triangle / mesh renderer carries per-corner uv / vn, the sky a texture or the
+                               # material textures a filter, else None
         self.keep = []
 
     def ptr(self):
@@ -282,6 +302,7 @@ def build_desc(render) -> DescHolder:
             env.tex.dat = arr.ctypes.data_as(C.POINTER(C.c_float))
         env.mapping = ENV_MAPPINGS[mapping]
         env.rot = float(np.float32(getattr(sc.sky, "rot", 0.0)))
+        env.filter = _filter_id(getattr(sc.sky, "filter", "nearest"), "sky filter")
         h.keep.append(env)
         if h.ext is None:
             h.ext = DescExt()
@@ -297,4 +318,10 @@ def build_desc(render) -> DescHolder:
     h.keep.append(texs)
     d.scene.textures = C.cast(texs, C.POINTER(Texture))
     d.scene.n_textures = len(tex_list)
+    # the filter of the material textures: carried by the ext only when some material has a texture for it to act on
+    tex_filter = _filter_id(getattr(sc, "tex_filter", "nearest"), "scene filter")
+    if tex_filter != FILTER_NEAREST and tex_list:
+        if h.ext is None:
+            h.ext = DescExt()
+        h.ext.tex_filter = tex_filter
     return h

@@ -41,7 +41,7 @@ MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
         a.g.nx = 0.0f; a.g.ny = 0.0f; a.g.nz = 0.0f; a.g.t = __builtin_inff();
         a.g.px = 0.0f; a.g.py = 0.0f; a.g.pz = 0.0f; a.g.hit = 0.0f;
         a.albedo = v3(0.0f, 0.0f, 0.0f);
-        if constexpr (FEAT & F_ENV) { float sky_pwr; a.albedo = env_color<FEAT>(S, d, sky_pwr); }      // the backdrop the centre ray sees
+        if constexpr (FEAT & F_ENV) { if (P.off_env != 0u) { float sky_pwr; a.albedo = env_color<FEAT>(S, d, sky_pwr); } }      // the backdrop the centre ray sees
         a.rend = -1; a.inst = -1;
         return a;
     }

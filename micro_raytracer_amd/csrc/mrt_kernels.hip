@@ -171,8 +171,8 @@ size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 f
 // four feature sets per shape -- plain primitives without / with lights (sphere and plane crowds), everything but
 // triangles and meshes, everything -- of which the smallest covering one runs (a Minecraft-shaped scene without the
 // triangle / mesh code: 113 VGPRs and no scratch instead of 128 + 72 B, +15 %).  Scenes with per-corner attributes (F_VATTR)
-// always take the full set, and so do scenes with an environment texture (F_ENV, which comes with F_VATTR).  Reported in
-// mrt_stats.kernel_features.
+// always take the full set, and so do scenes with an environment texture or a filtered texture (F_ENV, which comes with
+// F_VATTR).  Reported in mrt_stats.kernel_features.
 u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features)
 {
     constexpr u32 FN = F_ALL & ~F_TRI;

@@ -382,6 +382,12 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     if (attrs && ext->n_renderer != sc.n_renderer) {
         snprintf(msg, sizeof msg, "attributes for %u renderers, the scene has %u", ext->n_renderer, sc.n_renderer); err = msg; return MRT_ERR_SCENE;
     }
+    // texture filters (mrt.h MRT_FILTER_*): one switch for the material textures, one for the environment
+    if (ext && ext->reserved[1] != 0u) { snprintf(msg, sizeof msg, "ext.reserved[1] is %u, not 0", ext->reserved[1]); err = msg; return MRT_ERR_ARG; }
+    if (ext && ext->reserved[0] > MRT_FILTER_BILINEAR) {
+        snprintf(msg, sizeof msg, "ext.reserved[0] (tex_filter) %u unknown", ext->reserved[0]); err = msg; return MRT_ERR_SCENE;
+    }
+    const bool tex_bilinear = ext && ext->reserved[0] == MRT_FILTER_BILINEAR;
     auto uv_of = [&](u32 r) { return attrs ? attrs[r].uv : nullptr; };
     auto vn_of = [&](u32 r) { return attrs ? attrs[r].vn : nullptr; };
     out = Packed();
@@ -420,6 +426,7 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         if (!tx.dat) { err = "env.tex.dat is null"; return MRT_ERR_SCENE; }
         if (env->mapping > MRT_ENV_LATLONG) { snprintf(msg, sizeof msg, "env.mapping %u unknown", env->mapping); err = msg; return MRT_ERR_SCENE; }
         if (!std::isfinite(env->rot)) { err = "env.rot is not finite"; return MRT_ERR_SCENE; }
+        if (env->filter > MRT_FILTER_BILINEAR) { snprintf(msg, sizeof msg, "env.filter %u unknown", env->filter); err = msg; return MRT_ERR_SCENE; }
         if ((unsigned long long)tx.w * tx.h > (1ull << 25)) { snprintf(msg, sizeof msg, "env.tex: %ux%u is more than 2^25 texels", tx.w, tx.h); err = msg; return MRT_ERR_LIMIT; }
         double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
         const double pi = 3.14159265358979323846;
@@ -727,6 +734,11 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         mr[MAT_ROUGH] = bits(o.mat.rough); mr[MAT_METAL] = bits(o.mat.metal); mr[MAT_GLASS] = bits(o.mat.glass);
         mr[MAT_OPACITY] = bits(o.mat.opacity); mr[MAT_EMIT] = bits(o.mat.emit);
         for (int k = 0; k < 6; ++k) mr[MAT_MAP + k] = (u32)maps[k];
+        if (tex_bilinear && any_map) {
+            // the scene-wide filter switch, stored per material; the filtered lookups live in the full-feature F_ENV kernels only
+            mr[MAT_FLAGS] = MATF_BILINEAR | (o.kind == MRT_KIND_SPHERE ? (u32)MATF_CLAMP_V : 0u);    // a sphere's v runs pole to pole
+            out.features |= 512u | 1024u;                                            // F_VATTR | F_ENV
+        }
         mat_tab.insert(mat_tab.end(), mr, mr + MAT_WORDS);
     }
     if (xf_tab.empty()) { const float dflt[4] = {-0.0f, -0.0f, -1.0f, -0.0f}; xf_of(dflt); }
@@ -900,7 +912,7 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         }
         P.off_env = B.align4();
         B.u(tx.w); B.u(tx.h); B.u(exact ? (u32)(at * 4) : (u32)at); B.u(exact ? (u32)TEXFMT_U8 : (u32)TEXFMT_F32);
-        B.u(env->mapping); B.f(env->rot); B.f(sc.sky.pwr); B.u(0u);
+        B.u(env->mapping); B.f(env->rot); B.f(sc.sky.pwr); B.u(env->filter == MRT_FILTER_BILINEAR ? (u32)ENVF_BILINEAR : 0u);
     }
     B.align4();
     P.blob_words = (u32)B.w.size();

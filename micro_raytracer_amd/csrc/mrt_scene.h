@@ -60,7 +60,11 @@ constexpr u32 TAG_KIND_MASK = 7u, TAG_IDENT = 8u, TAG_XF_SHIFT = 4u;
 enum : u32 { XF_L = 0, XF_R = 9, XF_IDENT = 18 };
 
 // MAT: [0..2] albedo [3] rough [4] metal [5] glass [6] opacity [7] emit [8..13] map ids (tex rmap mmap gmap omap emap, -1 none)
-enum : u32 { MAT_ALBEDO = 0, MAT_ROUGH = 3, MAT_METAL = 4, MAT_GLASS = 5, MAT_OPACITY = 6, MAT_EMIT = 7, MAT_MAP = 8 };
+//      [14] flags: MATF_BILINEAR = the maps of this material are looked up with the bilinear filter of DESIGN.md §16 (set from the
+//           scene-wide switch of mrt_desc_ext on every material that has a map; 0 otherwise), with it MATF_CLAMP_V when the
+//           renderer is a sphere (its v runs pole to pole: the filter clamps v instead of repeating it)  [15] 0
+enum : u32 { MAT_ALBEDO = 0, MAT_ROUGH = 3, MAT_METAL = 4, MAT_GLASS = 5, MAT_OPACITY = 6, MAT_EMIT = 7, MAT_MAP = 8, MAT_FLAGS = 14 };
+enum : u32 { MATF_BILINEAR = 1u, MATF_CLAMP_V = 2u };
 enum : u32 { MAP_TEX = 0, MAP_ROUGH = 1, MAP_METAL = 2, MAP_GLASS = 3, MAP_OPACITY = 4, MAP_EMIT = 5 };
 
 // LIGHT: [0] kind [1..3] point: pos / dir: norm(-(norm(dir)))  [4] pwr  [5..7] color
@@ -72,8 +76,10 @@ enum : u32 { TEXFMT_NONE = 0, TEXFMT_F32 = 1, TEXFMT_U8 = 2 };
 
 // ENV (the sky's environment texture, mrt.h mrt_env): one record of ENV_WORDS words at Params.off_env, behind the
 // octree leaf lists and the attribute table like the texels it describes -- never staged, read from global memory at a miss:
-//   [0] w [1] h [2] texel offset (as TEX_OFF) [3] format (TEXFMT_F32 | TEXFMT_U8) [4] mapping (MRT_ENV_*) [5] rot (f32) [6] sky.pwr (f32) [7] 0
-enum : u32 { ENV_W = 0, ENV_H = 1, ENV_OFF = 2, ENV_FMT = 3, ENV_MAP = 4, ENV_ROT = 5, ENV_PWR = 6 };
+//   [0] w [1] h [2] texel offset (as TEX_OFF) [3] format (TEXFMT_F32 | TEXFMT_U8) [4] mapping (MRT_ENV_*) [5] rot (f32) [6] sky.pwr (f32)
+//   [7] flags: ENVF_BILINEAR = the bilinear filter of DESIGN.md §16 (mrt_env.filter); 0: nearest texel
+enum : u32 { ENV_W = 0, ENV_H = 1, ENV_OFF = 2, ENV_FMT = 3, ENV_MAP = 4, ENV_ROT = 5, ENV_PWR = 6, ENV_FLAGS = 7 };
+enum : u32 { ENVF_BILINEAR = 1u };
 constexpr u32 ENV_WORDS = 8;
 enum : u32 { ENVMAP_SPHERE = 0, ENVMAP_LATLONG = 1 };
 
@@ -185,7 +191,8 @@ struct Params {
     unsigned long long *segments;
     u32 *tile_counter;       // persistent launches: next (tile, sample-split lane) index, zeroed before the launch
     u32 persist_grid;        // workgroups of a persistent launch (0: one workgroup per tile block, blockIdx addresses the tiles)
-    u32 off_env;             // the ENV record of the sky's environment texture (F_ENV kernels; 0: none).  The last word of the block:
+    u32 off_env;             // the ENV record of the sky's environment texture (F_ENV kernels; 0: none -- also in an F_ENV kernel, which
+                             // a scene that only filters its material textures runs: tested at run time).  The last word of the block:
                              // it takes what was the struct's tail padding, so the argument block keeps its size and every offset
 };
 static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, off_env) + 4 == sizeof(Params), "off_env fills the tail of Params");

@@ -37,7 +37,8 @@ enum : u32 {
                       // 256-thread kernels of planes / spheres / boxes with and without lights; rays whose shifted origin has a
                       // zero, infinite or NaN component still take the reference's two mat-vecs (xf_vec)
     F_ENV = 1024u,    // the sky has an environment texture (mrt.h mrt_env): env_uv / env_color at the two miss sites of
-                      // render_pixel.  Like F_VATTR it exists with the full feature set only, and always together with F_VATTR
+                      // render_pixel -- or the scene filters its textures: the bilinear lookups live in this
+                      // family only, and a scene without an environment (Params.off_env == 0) takes the constant sky.  Like F_VATTR it exists with the full feature set only, and always together with F_VATTR
                       // (F_ALL | F_VATTR | F_ENV plus the shape markers and F_BVH)
     F_VATTR = 512u    // some triangle / mesh renderer carries per-corner normals or UVs (mrt.h mrt_desc_ext):
                       // the interpolation of hit_normal / hit_uv.  Exists with the full feature set only (F_ALL | F_VATTR plus the
@@ -362,6 +363,82 @@ MRT_HD V3 tex_fetch(const Scn &S, i32 id, UV uv)
     return ld3(X, off + i * 3u);
 }
 
+// The bilinear filter of DESIGN.md section 16 (F_ENV kernels only).  T: a TEX record, or the ENV record, whose first four words
+// have the same layout (w, h, texel offset, format); X: the blob the texels are read from; L: the k/255 LUT.  The four texels
+// around (u, v) are blended per channel as top = t00 + fx (t10 - t00), bot likewise, out = top + fy (bot - top); u always
+// repeats, v repeats or (clamp_v) replicates the first and last row.  A texel-space coordinate that is not finite (or beyond
+// 2^30: never for u, v in [0, 1]) takes the nearest rule's texel.  Texel addresses are formed in 64 bits; every index is clamped
+// into the texture whatever u and v are.
+// ONE out-of-line body per code object: the kernels that can call it sit at their 128-VGPR bound, and the unfiltered path of
+// those kernels keeps a flag test and a call in a branch instead of nine inlined four-texel bodies.
+MRT_HD u32 env_index(UV uv, u32 w, u32 h);
+#if defined(__HIPCC__) || defined(__HIP__)
+#define MRT_HD_OUTLINE __host__ __device__ inline __attribute__((noinline))
+#else
+#define MRT_HD_OUTLINE inline __attribute__((noinline))
+#endif
+constexpr float kBilinearMax = 1073741824.0f;      // 2^30
+MRT_HD_OUTLINE V3 tex_bilinear(const float *T, const float *X, const float *L, float u, float v, u32 clamp_v)
+{
+    const u32 w = ldu(T, TEX_W), h = ldu(T, TEX_H), off = ldu(T, TEX_OFF), fmt = ldu(T, TEX_FMT);
+    if (fmt == TEXFMT_NONE) return v3(0.0f, 0.0f, 0.0f);
+    const unsigned char *B = reinterpret_cast<const unsigned char *>(X) + (size_t)off;      // RGB8 texels
+    const float *Q = X + (size_t)off;                                                       // f32 texels
+    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;       // texel centres at i + 0.5
+    if (!(fabs_(x) < kBilinearMax) || !(fabs_(y) < kBilinearMax)) {
+        UV uv; uv.x = u; uv.y = v;
+        const size_t i = (size_t)env_index(uv, w, h) * 3u;              // the nearest rule (tex_fetch, env_color)
+        if (fmt == TEXFMT_U8) return v3(L[B[i]], L[B[i + 1]], L[B[i + 2]]);
+        return v3(Q[i], Q[i + 1], Q[i + 2]);
+    }
+    float xf = trunc_(x), yf = trunc_(y);                               // floor
+    if (xf > x) xf = xf - 1.0f;
+    if (yf > y) yf = yf - 1.0f;
+    const float fx = x - xf, fy = y - yf;                               // exact, in [0, 1)
+    const i32 iw = (i32)w, ih = (i32)h;
+    // ix mod w for |ix| <= w (u in [0, 1]); beyond that the index is clamped, never out of the texture
+    i32 x0 = (i32)xf;
+    if (x0 < 0) x0 += iw;
+    if (x0 >= iw) x0 -= iw;
+    x0 = x0 < 0 ? 0 : (x0 > iw - 1 ? iw - 1 : x0);
+    const i32 x1 = x0 + 1 >= iw ? 0 : x0 + 1;
+    i32 y0 = (i32)yf, y1;
+    if (clamp_v) {
+        y1 = y0 + 1;
+        y0 = y0 < 0 ? 0 : (y0 > ih - 1 ? ih - 1 : y0);
+        y1 = y1 < 0 ? 0 : (y1 > ih - 1 ? ih - 1 : y1);
+    } else {
+        if (y0 < 0) y0 += ih;
+        if (y0 >= ih) y0 -= ih;
+        y0 = y0 < 0 ? 0 : (y0 > ih - 1 ? ih - 1 : y0);
+        y1 = y0 + 1 >= ih ? 0 : y0 + 1;
+    }
+    const size_t r0 = (size_t)y0 * w, r1 = (size_t)y1 * w;
+    const size_t i00 = (r0 + (size_t)x0) * 3u, i10 = (r0 + (size_t)x1) * 3u, i01 = (r1 + (size_t)x0) * 3u, i11 = (r1 + (size_t)x1) * 3u;
+    V3 t00, t10, t01, t11;
+    if (fmt == TEXFMT_U8) {
+        t00 = v3(L[B[i00]], L[B[i00 + 1]], L[B[i00 + 2]]);
+        t10 = v3(L[B[i10]], L[B[i10 + 1]], L[B[i10 + 2]]);
+        t01 = v3(L[B[i01]], L[B[i01 + 1]], L[B[i01 + 2]]);
+        t11 = v3(L[B[i11]], L[B[i11 + 1]], L[B[i11 + 2]]);
+    } else {
+        t00 = v3(Q[i00], Q[i00 + 1], Q[i00 + 2]);
+        t10 = v3(Q[i10], Q[i10 + 1], Q[i10 + 2]);
+        t01 = v3(Q[i01], Q[i01 + 1], Q[i01 + 2]);
+        t11 = v3(Q[i11], Q[i11 + 1], Q[i11 + 2]);
+    }
+    const V3 top = add(t00, muls(sub(t10, t00), fx));
+    const V3 bot = add(t01, muls(sub(t11, t01), fx));
+    return add(top, muls(sub(bot, top), fy));
+}
+
+// tex_fetch under the bilinear filter: material flags has MATF_BILINEAR, and MATF_CLAMP_V when the renderer is a sphere
+template <u32 FEAT>
+MRT_HD V3 tex_fetch_bilinear(const Scn &S, i32 id, UV uv, u32 flags)
+{
+    return tex_bilinear(S.F + S.P->off_tex + (u32)id * TEX_WORDS, (FEAT & F_COLD) ? S.G : S.F, S.F + S.P->off_lut, uv.x, uv.y, flags & MATF_CLAMP_V);
+}
+
 // The sky's environment texture (F_ENV kernels).  env_uv: the texture coordinate of direction d -- the
 // sphere's UV of hit_uv (src/rt.rs:468-476) or the equirectangular one, u shifted by rot turns and wrapped like the plane's; d is
 // the ray direction as the kernel holds it, not normalised again.
@@ -387,7 +464,8 @@ MRT_HD u32 env_index(UV uv, u32 w, u32 h)
     if (idx > last) idx = last;
     return (u32)idx;
 }
-// E(d) = sky.color x texel, read from global memory at every staging level; pwr_out = sky.pwr (word 6 of the ENV record)
+// E(d) = sky.color x texel, read from global memory at every staging level; pwr_out = sky.pwr (word 6 of the ENV record).
+// Only for P.off_env != 0: an F_ENV kernel also serves scenes that filter their material textures and have no environment.
 template <u32 FEAT>
 MRT_HD V3 env_color(const Scn &S, V3 d, float &pwr_out)
 {
@@ -395,7 +473,10 @@ MRT_HD V3 env_color(const Scn &S, V3 d, float &pwr_out)
     const float *E = S.G + P.off_env;
     const u32 w = ldu(E, ENV_W), h = ldu(E, ENV_H), fmt = ldu(E, ENV_FMT), off = ldu(E, ENV_OFF);
     pwr_out = E[ENV_PWR];
-    const size_t i = (size_t)env_index(env_uv(ldu(E, ENV_MAP), E[ENV_ROT], d), w, h) * 3u;
+    const UV uv = env_uv(ldu(E, ENV_MAP), E[ENV_ROT], d);
+    if (ldu(E, ENV_FLAGS) & ENVF_BILINEAR)               // (wave-uniform) DESIGN.md section 16: the poles replicate, the seam wraps
+        return hadam(v3(P.sky[0], P.sky[1], P.sky[2]), tex_bilinear(E, S.G, S.F + P.off_lut, uv.x, uv.y, 1u));
+    const size_t i = (size_t)env_index(uv, w, h) * 3u;
     V3 t;
     if (fmt == TEXFMT_U8) {
         const unsigned char *B = reinterpret_cast<const unsigned char *>(S.G) + ((size_t)off + i);
@@ -1316,7 +1397,10 @@ MRT_HD float surf_scalar(const Scn &S, const Surf &s, u32 slot, u32 field)
 {
     if (s.maps) {
         const i32 id = (i32)ldu(s.M, MAT_MAP + slot);
-        if (id >= 0) return tex_fetch<FEAT>(S, id, s.uv).x;
+        if (id >= 0) {
+            if constexpr (FEAT & F_ENV) { const u32 fl = ldu(s.M, MAT_FLAGS); if (fl & MATF_BILINEAR) return tex_fetch_bilinear<FEAT>(S, id, s.uv, fl).x; }
+            return tex_fetch<FEAT>(S, id, s.uv).x;
+        }
     }
     return s.M[field];
 }
@@ -1326,7 +1410,10 @@ MRT_HD V3 surf_color(const Scn &S, const Surf &s)
     const V3 albedo = ld3(s.M, MAT_ALBEDO);
     if (s.maps) {
         const i32 id = (i32)ldu(s.M, MAT_MAP + MAP_TEX);
-        if (id >= 0) return hadam(albedo, tex_fetch<FEAT>(S, id, s.uv));
+        if (id >= 0) {
+            if constexpr (FEAT & F_ENV) { const u32 fl = ldu(s.M, MAT_FLAGS); if (fl & MATF_BILINEAR) return hadam(albedo, tex_fetch_bilinear<FEAT>(S, id, s.uv, fl)); }
+            return hadam(albedo, tex_fetch<FEAT>(S, id, s.uv));
+        }
     }
     return albedo;
 }
@@ -1530,14 +1617,18 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
         MRT_TICK(0);                                                   // the closest-hit query
         if (!hit_any) {
             // primary miss: raw sky colour (src/rt.rs:957-959); otherwise the fold starts from sky*pwr (:964)
+            bool env = false;
             if constexpr (FEAT & F_ENV) {
-                // environment texture: E(d) in the sky colour's place; a later miss scales it by sky.pwr
-                float sky_pwr;
-                const V3 e = env_color<FEAT>(S, d, sky_pwr);
-                contrib = (b == 0) ? e : add(getL(), hadam(getT(), muls(e, sky_pwr)));
-            } else {
-                contrib = (b == 0) ? v3(P.sky[0], P.sky[1], P.sky[2]) : add(getL(), hadam(getT(), sky_init));
+                // environment texture: E(d) in the sky colour's place; a later miss scales it by sky.pwr.  (wave-uniform) A scene
+                // that runs this family for its filtered material textures alone has none and takes the constant sky below
+                if (P.off_env != 0u) {
+                    float sky_pwr;
+                    const V3 e = env_color<FEAT>(S, d, sky_pwr);
+                    contrib = (b == 0) ? e : add(getL(), hadam(getT(), muls(e, sky_pwr)));
+                    env = true;
+                }
             }
+            if (!env) contrib = (b == 0) ? v3(P.sky[0], P.sky[1], P.sky[2]) : add(getL(), hadam(getT(), sky_init));
             ended = true;
         } else {
             MRT_PROBE(PH_SHADE);

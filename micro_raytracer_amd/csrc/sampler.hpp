@@ -35,7 +35,7 @@ public:
     // The context is created on the first call (scene and frame only arrive here) and rebuilt when a later call passes
     // a description with other contents; sums accumulated so far are carried over when the supersampled frame keeps its
     // size (the reference's map keeps adding whatever the scene, src/sampler.rs:60-70).
-    // ext (optional): per-corner attributes / the sky's environment texture (mrt_desc_ext); the context is then created through
+    // ext (optional): per-corner attributes / the sky's environment texture / the texture filters (mrt_desc_ext); the context is then created through
     // mrt_create_ext, and the environment is part of the fingerprint.
     double execute(const mrt_render_desc &render, uint32_t n_samples = 1, const mrt_desc_ext *ext = nullptr)
     {
@@ -134,8 +134,9 @@ private:
         for (uint32_t i = 0; i < d.scene.n_textures; ++i) { const mrt_texture &t = d.scene.textures[i]; f.pod(t.w); f.pod(t.h); f.bulk(t.dat, t.dat ? (size_t)t.w * t.h * 3 : 0); }
         if (ext && ext->env) {      // the environment texture: texels hashed like other bulk data
             const mrt_env &e = *ext->env;
-            f.pod(e.tex.w); f.pod(e.tex.h); f.pod(e.mapping); f.pod(e.rot); f.bulk(e.tex.dat, e.tex.dat ? (size_t)e.tex.w * e.tex.h * 3 : 0);
+            f.pod(e.tex.w); f.pod(e.tex.h); f.pod(e.mapping); f.pod(e.rot); f.pod(e.filter); f.bulk(e.tex.dat, e.tex.dat ? (size_t)e.tex.w * e.tex.h * 3 : 0);
         }
+        if (ext && ext->reserved[0]) f.pod(ext->reserved[0]);      // MRT_FILTER_* of the material textures
         return f.h;
     }
 

@@ -55,7 +55,8 @@ def _fingerprint(render: Render):
            arr(render.scene.sky.color), render.scene.sky.pwr]
     sky = render.scene.sky
     if getattr(sky, "tex", None) is not None:
-        out.append(("env", tex(sky.tex), sky.mapping, sky.rot))
+        out.append(("env", tex(sky.tex), sky.mapping, sky.rot, getattr(sky, "filter", "nearest")))
+    out.append(("tex_filter", getattr(render.scene, "tex_filter", "nearest")))
     for l in render.scene.light:
         out.append((l.kind, arr(l.v), l.pwr, arr(l.color)))
     for o in render.scene.renderer:
@@ -116,7 +117,7 @@ class Sampler:
         opts.flags = self.flags
         if self._holder.ext is None:
             ctx = L.mrt_create(C.cast(self._holder.ptr(), C.c_void_p), C.byref(opts))
-        else:                   # per-corner uv / vn on a triangle or mesh, or an environment texture on the sky
+        else:                   # per-corner uv / vn on a triangle or mesh, an environment texture on the sky, or filtered textures
             ctx = L.mrt_create_ext(C.cast(self._holder.ptr(), C.c_void_p), C.byref(opts), self._holder.ext_ptr())
         if not ctx:
             raise _lib.MrtError(L.mrt_last_status(), L.mrt_last_error().decode())

@@ -368,12 +368,14 @@ class Light:
 @dataclass
 class Sky:
     """rt::Sky, src/rt.rs:178-181, plus the optional environment texture (not in the reference; DESIGN.md section 15): `tex`
-    multiplies `color` per direction; mapping "sphere" | "latlong"; rot in turns about +z."""
+    multiplies `color` per direction; mapping "sphere" | "latlong"; rot in turns about +z; filter "nearest" | "bilinear"
+    (DESIGN.md section 16)."""
     color: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
     pwr: float = 0.5
     tex: Optional[Texture] = None
     mapping: str = "sphere"
     rot: float = 0.0
+    filter: str = "nearest"
 
 
 @dataclass
@@ -415,6 +417,7 @@ class Scene:
     renderer: List[Renderer] = field(default_factory=list)
     light: List[Light] = field(default_factory=list)
     sky: Sky = field(default_factory=Sky)
+    tex_filter: str = "nearest"         # filter of every material texture: "nearest" | "bilinear" (not in the reference)
 
 
 @dataclass
@@ -423,6 +426,16 @@ class Render:
     rt: RayTracer = field(default_factory=RayTracer)
     frame: Frame = field(default_factory=Frame)
     scene: Scene = field(default_factory=Scene)
+
+
+FILTERS = ("nearest", "bilinear")
+
+
+def _filter_from_json(obj, where):
+    val = obj.get("filter", "nearest")
+    if val not in FILTERS:
+        raise ValueError(f"\"filter\" on \"{where}\": `{val}` is unexpected (nearest | bilinear)")
+    return val
 
 
 def load_render(src, base_dir=".") -> Render:
@@ -464,6 +477,9 @@ def load_render(src, base_dir=".") -> Render:
         if out.scene.sky.mapping not in ("sphere", "latlong"):
             raise ValueError(f"sky map `{out.scene.sky.mapping}` is unexpected (sphere | latlong)")
         out.scene.sky.rot = float(f32(sky.get("rot", 0.0)))
+    # texture filters: "filter" on "sky" (the environment texture) and on "scene" (every material texture)
+    out.scene.sky.filter = _filter_from_json(sky, "sky")
+    out.scene.tex_filter = _filter_from_json(sc, "scene")
     return out
 
 
@@ -507,11 +523,14 @@ def dump_render(r: Render) -> dict:
     sky = {"color": fl(r.scene.sky.color), "pwr": r.scene.sky.pwr}
     if r.scene.sky.tex is not None:       # the three keys of the environment only when there is one
         sky.update({"tex": tex(r.scene.sky.tex), "map": r.scene.sky.mapping, "rot": r.scene.sky.rot})
+    if getattr(r.scene.sky, "filter", "nearest") != "nearest":      # the filters only when they are not the default
+        sky["filter"] = r.scene.sky.filter
+    scene_filter = {} if getattr(r.scene, "tex_filter", "nearest") == "nearest" else {"filter": r.scene.tex_filter}
     return {
         "rt": {"bounce": r.rt.bounce, "sample": r.rt.sample, "loss": r.rt.loss},
         "frame": {"res": list(r.frame.res), "ssaa": r.frame.ssaa,
                   "cam": {"pos": fl(cam.pos), "dir": fl(cam.dir), "fov": cam.fov, "gamma": cam.gamma,
                           "exp": cam.exp, "aprt": cam.aprt, "foc": cam.foc}},
         "scene": {"renderer": rend or None, "light": lights or None,
-                  "sky": sky},
+                  "sky": sky, **scene_filter},
     }

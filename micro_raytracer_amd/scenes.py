@@ -213,9 +213,10 @@ def sky_texture(w=256, h=128, mapping="sphere", sun=(0.31, 0.55), sun_radiance=5
     return {"w": int(w), "h": int(h), "dat": img.reshape(-1, 3).astype(np.float32)}
 
 
-def env_scene(res=(1280, 720), sample=64, bounce=8, mapping="sphere", tex_res=(256, 128)):
+def env_scene(res=(1280, 720), sample=64, bounce=8, mapping="sphere", tex_res=(256, 128), filter="nearest"):
     """A chrome sphere, a glass sphere and the smooth textured mesh of smooth_mesh_scene on a rough plane, lit by nothing but a
-    procedural HDR environment (sky_texture): the scene of DESIGN.md section 15.  No lights."""
+    procedural HDR environment (sky_texture): the scene of DESIGN.md section 15.  No lights.  filter: "nearest" | "bilinear" for
+    the environment texture."""
     d = smooth_mesh_scene(res, 1, sample, bounce)
     d["scene"]["light"] = []
     d["scene"]["renderer"][1]["mat"] = {"rough": 1, "albedo": [0.7, 0.7, 0.7]}
@@ -225,6 +226,8 @@ def env_scene(res=(1280, 720), sample=64, bounce=8, mapping="sphere", tex_res=(2
     ]
     d["scene"]["sky"] = {"color": [1.0, 1.0, 1.0], "pwr": 0.6, "tex": sky_texture(tex_res[0], tex_res[1], mapping),
                          "map": mapping, "rot": 0.0}
+    if filter != "nearest":
+        d["scene"]["sky"]["filter"] = filter
     return d
 
 

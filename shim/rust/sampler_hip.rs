@@ -45,8 +45,8 @@ struct MrtMaterial { albedo: [f32; 3], rough: f32, metal: f32, glass: f32, opaci
 #[repr(C)] struct MrtCtx { _private: [u8; 0] }
 
 extern "C" {
-    // (mrt_create_ext adds per-corner attributes and the sky's environment texture -- mrt_desc_ext.attrs / .env of mrt.h; the
-    // reference's scenes have neither, so the shim creates through mrt_create)
+    // (mrt_create_ext adds per-corner attributes, the sky's environment texture and the bilinear texture filter -- mrt_desc_ext.attrs /
+    // .env / .reserved[0] and mrt_env.filter of mrt.h; the reference's scenes have none of them, so the shim creates through mrt_create)
     fn mrt_create(desc: *const MrtRenderDesc, opts: *const MrtOpts) -> *mut MrtCtx;
     fn mrt_destroy(ctx: *mut MrtCtx);
     fn mrt_execute(ctx: *mut MrtCtx, n_samples: u32, seconds: *mut f64) -> c_int;
