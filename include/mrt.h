@@ -318,20 +318,36 @@ int mrt_adapt_half(mrt_ctx *ctx, float *rgb);
 int mrt_aov(mrt_ctx *ctx, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance);
 
 /* Edge-avoiding a-trous filter (Dammertz et al. 2010) on the mean radiance, guided by the AOVs.  passes 0..8 (0: the means
- * unchanged); sigmas > 0 or +inf (+inf switches that term off); NaN or <= 0: MRT_ERR_ARG.  NULL options = the defaults. */
+ * unchanged); sigmas > 0 or +inf (+inf switches that term off); NaN or <= 0: MRT_ERR_ARG.  NULL options = the defaults.
+ *
+ * mode MRT_DN_VARIANCE: the colour term is driven by a per-pixel variance estimate instead of sigma_color (which
+ * must still be valid, and is not used).  The estimate comes from the accumulator and the half buffer of an adaptive render, so
+ * the mode needs what mrt_adapt_half needs: an mrt_execute_adaptive on this context since its last mrt_reset / mrt_set_accum*,
+ * else MRT_ERR_STATE.  A uniform budget of n samples with a half buffer: mrt_execute_adaptive with threshold 0 and
+ * min_samples = max_samples = n (the accumulator bytes of an n-sample mrt_execute).
+ *   sigma_var   the colour term's width in standard deviations of the pixel's mean; 0: MRT_DN_SIGMA_VAR; > 0 or +inf (off)
+ *   firefly     a pixel brighter than firefly x its brightest same-surface neighbour is scaled down to that before the filter;
+ *               0: MRT_DN_FIREFLY; > 0; +inf: off
+ * NaN or < 0: MRT_ERR_ARG.  In mode MRT_DN_ATROUS both must be 0 (MRT_ERR_ARG); any other mode: MRT_ERR_ARG. */
 #define MRT_DENOISE_PASSES 5u
 #define MRT_DENOISE_SIGMA_COLOR 0.5f
 #define MRT_DENOISE_SIGMA_NORMAL 0.25f
 #define MRT_DENOISE_SIGMA_PLANE 0.05f
+#define MRT_DN_ATROUS 0u
+#define MRT_DN_VARIANCE 1u
+#define MRT_DN_SIGMA_VAR 4.5f
+#define MRT_DN_FIREFLY 1.0f
 typedef struct mrt_denoise_opts {
     uint32_t passes;
     float sigma_color, sigma_normal, sigma_plane;
-    uint32_t reserved[4];
+    uint32_t mode;                 /* MRT_DN_ATROUS (0, the filter as it always was) or MRT_DN_VARIANCE */
+    float sigma_var, firefly;      /* MRT_DN_VARIANCE only; 0: the default */
+    uint32_t reserved[1];
 } mrt_denoise_opts;
 typedef struct mrt_denoise_info {
     double aov_ms, filter_ms;      /* HIP-event times of this call's AOV pass (0: the AOVs were cached) and of the filter */
     uint32_t passes, aov_cached;
-    uint32_t reserved[2];
+    uint32_t reserved[2];          /* reserved[0]: the mode that ran (MRT_DN_*) */
 } mrt_denoise_info;
 
 /* The filtered means rgb[nh][nw][3].  An observation like mrt_img: booked samples are traced first; needs the whole frame

@@ -2,7 +2,8 @@
 
     python -m micro_raytracer_amd scene.json -o out.png [--sample N] [--bounce N] [--seed S] [--update]
                                   [--adaptive THRESHOLD [--min-sample N] [--step N]]
-                                  [--denoise [--denoise-passes N]] [--aov PREFIX]
+                                  [--denoise [--denoise-passes N] [--denoise-mode atrous|variance] [--denoise-sigma-var S]
+                                   [--denoise-firefly F]] [--aov PREFIX]
                                   [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS] [--sky-filter nearest|bilinear]
                                   [--tex-filter nearest|bilinear]
 
@@ -10,6 +11,9 @@ Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --upda
 --adaptive renders with a per-tile noise threshold instead (Sampler.execute_adaptive), --sample being the cap.
 --denoise saves the image of the AOV-guided a-trous filter (Sampler.img_denoised) instead of the raw means; --aov writes the
 first-hit normal, albedo and depth as PREFIX.normal.png, PREFIX.albedo.png and PREFIX.depth.png.
+--denoise-mode variance drives the filter's colour term by a per-pixel variance estimate from the adaptive half buffer; without
+--adaptive the render then goes through execute_adaptive(threshold=0, min = max = --sample, step 16), the bytes of the uniform
+render, so --sample must be a multiple of 32.  --denoise-sigma-var and --denoise-firefly (inf: off) tune that mode.
 --sky-tex / --sky-map / --sky-rot override the description's environment texture (an image file or a Radiance .hdr), its
 mapping and its rotation about +z; --sky-filter / --tex-filter choose the filter of the environment texture and of the material
 textures (nearest texel, or bilinear).
@@ -26,7 +30,9 @@ from .scene import Texture
 
 
 def image(s, a):
-    return s.img_denoised(passes=a.denoise_passes) if a.denoise else s.img()
+    if not a.denoise:
+        return s.img()
+    return s.img_denoised(passes=a.denoise_passes, mode=a.denoise_mode, sigma_var=a.denoise_sigma_var, firefly=a.denoise_firefly)
 
 
 def aov_images(aov):
@@ -63,6 +69,12 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true", help="save the denoised image (AOV-guided a-trous filter)")
     ap.add_argument("--denoise-passes", type=int, default=_abi.DENOISE_PASSES,
                     help=f"--denoise: filter passes, 0..8 (default {_abi.DENOISE_PASSES})")
+    ap.add_argument("--denoise-mode", choices=sorted(_abi.DN_MODES), default="atrous",
+                    help="--denoise: atrous (fixed colour sigma) or variance (colour term from the adaptive half buffer)")
+    ap.add_argument("--denoise-sigma-var", type=float, metavar="S",
+                    help=f"--denoise-mode variance: colour width in standard deviations (default {_abi.DN_SIGMA_VAR})")
+    ap.add_argument("--denoise-firefly", type=float, metavar="F",
+                    help=f"--denoise-mode variance: firefly clamp factor, inf: off (default {_abi.DN_FIREFLY})")
     ap.add_argument("--aov", metavar="PREFIX", help="also write PREFIX.normal.png, PREFIX.albedo.png and PREFIX.depth.png")
     ap.add_argument("--sky-tex", metavar="FILE", help="environment texture of the sky: an image file or a Radiance .hdr")
     ap.add_argument("--sky-map", choices=("sphere", "latlong"), help="mapping of the environment texture")
@@ -72,6 +84,18 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not 0 <= a.denoise_passes <= 8:
         ap.error(f"--denoise-passes {a.denoise_passes} is not in 0..8")
+    variance = a.denoise and a.denoise_mode == "variance"
+    if not variance and (a.denoise_sigma_var is not None or a.denoise_firefly is not None):
+        ap.error("--denoise-sigma-var / --denoise-firefly need --denoise --denoise-mode variance")
+    for name, v in (("--denoise-sigma-var", a.denoise_sigma_var), ("--denoise-firefly", a.denoise_firefly)):
+        if v is not None and not v > 0.0:
+            ap.error(f"{name} {v} is not > 0")
+    if variance and a.adaptive is None:
+        if a.update:
+            ap.error("--update cannot be combined with --denoise-mode variance")
+        if a.sample is not None and (a.sample <= 0 or a.sample % 32):
+            ap.error(f"--sample {a.sample} is not a positive multiple of 32: --denoise-mode variance renders through "
+                     "execute_adaptive(threshold=0, min = max = --sample, step=16), whose rounds come in pairs of 16 samples")
     if a.adaptive is not None:
         if a.update:
             ap.error("--update cannot be combined with --adaptive")
@@ -103,6 +127,11 @@ def main(argv=None):
         uniform = s.nw * s.nh * render.rt.sample
         print(f"adaptive: {info['samples']} samples traced of {uniform} uniform ({info['samples'] / uniform:.1%}), "
               f"{info['tiles_converged']} of {info['tiles']} tiles converged, per-pixel counts {info['min_count']}..{info['max_count']}")
+    elif variance:
+        if render.rt.sample <= 0 or render.rt.sample % 32:
+            ap.error(f"the description's sample count {render.rt.sample} is not a positive multiple of 32, which --denoise-mode variance "
+                     "needs (execute_adaptive with min = max = the sample count, step 16); pass --sample")
+        s.execute_adaptive(render, 0.0, min_samples=render.rt.sample, max_samples=render.rt.sample, step=16)
     elif a.update:
         for _ in range(render.rt.sample):
             s.execute(render)

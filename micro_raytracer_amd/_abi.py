@@ -127,7 +127,7 @@ class AdaptInfo(C.Structure):
 
 class DenoiseOpts(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
-                ("reserved", C.c_uint32 * 4)]
+                ("mode", C.c_uint32), ("sigma_var", C.c_float), ("firefly", C.c_float), ("reserved", C.c_uint32 * 1)]
 
 
 class DenoiseInfo(C.Structure):
@@ -139,13 +139,26 @@ class DenoiseInfo(C.Structure):
 DENOISE_PASSES, DENOISE_SIGMA_COLOR, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_PLANE = 5, 0.5, 0.25, 0.05
 
 
-def denoise_opts(passes=DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None) -> DenoiseOpts:
-    """mrt_denoise_opts; a sigma of None takes its default, float("inf") switches that term off."""
+# modes of mrt_denoise_opts (MRT_DN_*) and the variance mode's defaults (MRT_DN_SIGMA_VAR, MRT_DN_FIREFLY), which a 0 word selects
+DN_MODES = {"atrous": 0, "variance": 1}
+DN_SIGMA_VAR, DN_FIREFLY = 4.5, 1.0
+
+
+def denoise_opts(passes=DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, mode="atrous", sigma_var=None,
+                 firefly=None) -> DenoiseOpts:
+    """mrt_denoise_opts; a sigma of None takes its default, float("inf") switches that term off.  mode "variance" (an adaptive
+    render's half buffer drives the colour term): sigma_var / firefly of None are the struct's 0 word, the library's default;
+    firefly float("inf") switches the firefly clamp off."""
+    if mode not in DN_MODES:
+        raise ValueError(f"denoise mode `{mode}`: expected one of {sorted(DN_MODES)}")
     o = DenoiseOpts()
     o.passes = int(passes)
     o.sigma_color = DENOISE_SIGMA_COLOR if sigma_color is None else float(sigma_color)
     o.sigma_normal = DENOISE_SIGMA_NORMAL if sigma_normal is None else float(sigma_normal)
     o.sigma_plane = DENOISE_SIGMA_PLANE if sigma_plane is None else float(sigma_plane)
+    o.mode = DN_MODES[mode]
+    o.sigma_var = 0.0 if sigma_var is None else float(sigma_var)
+    o.firefly = 0.0 if firefly is None else float(firefly)
     return o
 
 

@@ -1454,8 +1454,10 @@ int mrt_aov(mrt_ctx *c, float *depth, float *normal, float *albedo, int32_t *ren
     return MRT_OK;
 }
 
-// Filter options -> passes and the three 1/sigma^2, formed in f32 (sigma = +inf: 0, the term is off)
-static int denoise_opts(const mrt_denoise_opts *o, const char *fn, u32 &passes, float &sc, float &sn, float &sp)
+// Filter options -> passes, the 1/sigma^2 formed in f32 (sigma = +inf: 0, the term is off), the mode and its firefly factor
+struct DnOpts { u32 passes, mode; float sc, sn, sp, sv, firefly; };
+
+static int denoise_opts(const mrt_denoise_opts *o, const char *fn, DnOpts &r)
 {
     mrt_denoise_opts d;
     memset(&d, 0, sizeof d);
@@ -1465,38 +1467,54 @@ static int denoise_opts(const mrt_denoise_opts *o, const char *fn, u32 &passes, 
     if (o->passes > kDnMaxPasses) return fail(MRT_ERR_ARG, "%s: passes %u > %u", fn, o->passes, kDnMaxPasses);
     const float sg[3] = {o->sigma_color, o->sigma_normal, o->sigma_plane};
     for (float s : sg) if (!(s > 0.0f)) return fail(MRT_ERR_ARG, "%s: sigma %g is not > 0", fn, (double)s);
-    passes = o->passes;
-    sc = 1.0f / (sg[0] * sg[0]);
-    sn = 1.0f / (sg[1] * sg[1]);
-    sp = 1.0f / (sg[2] * sg[2]);
+    if (o->mode != MRT_DN_ATROUS && o->mode != MRT_DN_VARIANCE) return fail(MRT_ERR_ARG, "%s: unknown mode %u", fn, o->mode);
+    if (!(o->sigma_var >= 0.0f)) return fail(MRT_ERR_ARG, "%s: sigma_var %g is not >= 0", fn, (double)o->sigma_var);
+    if (!(o->firefly >= 0.0f)) return fail(MRT_ERR_ARG, "%s: firefly %g is not >= 0", fn, (double)o->firefly);
+    if (o->mode == MRT_DN_ATROUS && (o->sigma_var != 0.0f || o->firefly != 0.0f))
+        return fail(MRT_ERR_ARG, "%s: sigma_var and firefly belong to MRT_DN_VARIANCE and must be 0 in MRT_DN_ATROUS", fn);
+    r.passes = o->passes; r.mode = o->mode;
+    r.sc = 1.0f / (sg[0] * sg[0]);
+    r.sn = 1.0f / (sg[1] * sg[1]);
+    r.sp = 1.0f / (sg[2] * sg[2]);
+    const float sv = o->sigma_var != 0.0f ? o->sigma_var : MRT_DN_SIGMA_VAR;
+    r.sv = 1.0f / (sv * sv);
+    r.firefly = o->firefly != 0.0f ? o->firefly : MRT_DN_FIREFLY;
     return MRT_OK;
 }
 
 // The filtered means of the accumulator into the context's output plane (*out, on the device); an observation like mrt_img
 static int denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *info, const char *fn, const float **out)
 {
-    u32 passes;
-    float sc, sn, sp;
+    DnOpts d;
     Frame f;
     bool cached;
     double aov_ms;
     int rc;
-    if ((rc = denoise_opts(o, fn, passes, sc, sn, sp)) || (rc = enter(c)) || (rc = whole_frame(c, fn, "", f)) || (rc = aov_compute(c, cached, aov_ms))) return rc;
+    if ((rc = denoise_opts(o, fn, d)) || (rc = enter(c))) return rc;
+    if (d.mode == MRT_DN_VARIANCE && !c->adaptive)
+        return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE needs the half buffer of an adaptive render on this context since its last reset or "
+                    "mrt_set_accum; for a uniform budget of n samples call mrt_execute_adaptive with threshold 0 and min_samples = max_samples = n", fn);
+    if ((rc = whole_frame(c, fn, "", f)) || (rc = aov_compute(c, cached, aov_ms))) return rc;
     Aov &a = *c->aov;
     const u32 nw = c->pk.nw, nh = c->pk.nh;
     const size_t np = (size_t)nw * nh;
     if (!a.dn.p) HIP_TRY(a.dn.alloc(np * 11u));
     float *e0 = a.dn.p, *e1 = e0 + 4u * np, *dst = e1 + 4u * np;
     const u32 *tc = c->adaptive ? c->ad->counts() : nullptr;     // per-tile counts of the last adaptive call
+    const bool env = c->pk.P.off_env != 0u;
     HIP_TRY(hipEventRecord(a.ev[0].get(), c->stream.get()));
-    HIP_TRY(launch_denoise(f.rgb, 1.0f / (float)f.count, tc, a.guide.p, a.albedo.p, nw, nh, passes, sc, sn, sp, e0, e1, dst, c->stream.get(), c->pk.P.off_env != 0u));
+    if (d.mode == MRT_DN_VARIANCE && d.passes != 0u)
+        HIP_TRY(launch_denoise_var(f.rgb, c->ad->half.p, tc, a.guide.p, a.albedo.p, nw, nh, d.passes, d.sv, d.sn, d.sp, d.firefly, e0, e1, dst, c->stream.get(), env));
+    else
+        HIP_TRY(launch_denoise(f.rgb, 1.0f / (float)f.count, tc, a.guide.p, a.albedo.p, nw, nh, d.passes, d.sc, d.sn, d.sp, e0, e1, dst, c->stream.get(), env));
     HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, a.ev[0].get(), a.ev[1].get()));
     if (info) {
         memset(info, 0, sizeof *info);
-        info->aov_ms = aov_ms; info->filter_ms = ms; info->passes = passes; info->aov_cached = cached ? 1u : 0u;
+        info->aov_ms = aov_ms; info->filter_ms = ms; info->passes = d.passes; info->aov_cached = cached ? 1u : 0u;
+        info->reserved[0] = d.mode;
     }
     *out = dst;
     return MRT_OK;

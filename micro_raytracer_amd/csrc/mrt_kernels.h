@@ -23,6 +23,9 @@ hipError_t launch_tonemap_tiles(const float *accum, unsigned char *out, const u3
 hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo, i32 *ids, hipStream_t stream);
 hipError_t launch_denoise(const float *accum, float rc, const u32 *tile_count, const float *guide, const float *albedo, u32 nw, u32 nh, u32 passes,
                           float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env = false);   // env: the context has an environment texture
+// mrt_denoise_var.hip: the variance-guided mode, passes >= 1; half: the adaptive half buffer, tile_count not null
+hipError_t launch_denoise_var(const float *accum, const float *half, const u32 *tile_count, const float *guide, const float *albedo, u32 nw, u32 nh,
+                              u32 passes, float sv, float sn, float sp, float firefly, float *e0, float *e1, float *out, hipStream_t stream, bool env);
 hipError_t launch_scatter_rows(float *frame, const float *gathered, const u32 *rowmap, u32 n_rows, u32 row_words, hipStream_t stream);
 hipError_t launch_tonemap(const float *accum, unsigned char *out, u32 n_px, float rc, float gamma, float wexp, hipStream_t stream);
 hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,

@@ -224,27 +224,33 @@ class Sampler:
                                       out["instance"].ctypes.data_as(ip)))
         return out
 
-    def denoise(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None) -> np.ndarray:
+    def denoise(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None, mode="atrous",
+                sigma_var=None, firefly=None) -> np.ndarray:
         """The accumulated means filtered by the AOV-guided a-trous filter (mrt_denoise), f32 [nh][nw][3].  info: a dict that
-        receives mrt_denoise_info."""
+        receives mrt_denoise_info (and "mode").  mode "variance": the colour term follows a per-pixel variance estimate from the
+        half buffer, so it needs an execute_adaptive() on this context (threshold=0, min_samples=max_samples=n for a uniform
+        budget); sigma_var / firefly of None take the library's defaults, firefly=float("inf") switches the clamp off."""
         self._need()
-        o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane)
+        o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane, mode, sigma_var, firefly)
         out = np.empty((self.nh, self.nw, 3), np.float32)
         di = _abi.DenoiseInfo()
         _lib.check(_lib.lib().mrt_denoise(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(di)))
         if info is not None:
             info.update({k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"})
+            info["mode"] = int(di.reserved[0])
         return out
 
-    def img_denoised(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None) -> np.ndarray:
-        """img() of the denoised means (mrt_img_denoised), uint8 [res_h][res_w][3]."""
+    def img_denoised(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None, mode="atrous",
+                     sigma_var=None, firefly=None) -> np.ndarray:
+        """img() of the denoised means (mrt_img_denoised), uint8 [res_h][res_w][3]; the options of denoise()."""
         self._need()
-        o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane)
+        o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane, mode, sigma_var, firefly)
         out = np.empty((self.res[1], self.res[0], 3), np.uint8)
         di = _abi.DenoiseInfo()
         _lib.check(_lib.lib().mrt_img_denoised(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(di)))
         if info is not None:
             info.update({k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"})
+            info["mode"] = int(di.reserved[0])
         return out
 
     # -- extras of the C ABI -----------------------------------------------------------------
