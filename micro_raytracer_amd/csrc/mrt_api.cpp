@@ -361,7 +361,7 @@ void plan_launch(const mrt_render_desc *desc, const mrt_desc_ext *ext, Packed &p
     // entries, deep: the scene is packed again with 4-wide triangle BVHs).
     // Environment (experiments, tests; read here, once): MRT_COLD=0/1 forbids / forces the warm level, MRT_DEEP_NODES=n forces
     // the deep level with n staged nodes, MRT_SCENE_IN_L2 forces none, MRT_BLOCK_THREADS forces a workgroup size, MRT_WALK_CAP
-    // the entries of the deep level's walk area.
+    // the entries of the deep level's walk area, MRT_AXIS_SCAN=0 switches the axis scan of mrt_trace.h off.
     const bool no_lds = getenv("MRT_SCENE_IN_L2") != nullptr;
     const char *force = getenv("MRT_BLOCK_THREADS");
     const bool mesh_walk = pk.n_tbvh_nodes != 0u && (pk.features & 3u) == 3u;
@@ -446,6 +446,8 @@ void plan_launch(const mrt_render_desc *desc, const mrt_desc_ext *ext, Packed &p
         if ((f == 64u && !cold) || f == 256u || f == 512u || f == 1024u) { if (fits(f, cold)) { want = f; marker = cold; pl.small_plain_grid = false; } }
     }
     pk.features = (pk.features & (31u | F_VATTR | F_ENV)) | marker | (pk.all_ident ? (u32)F_IDENT : 0u);      // (pt_instantiation: which shapes have F_IDENT builds)
+    // MRT_AXIS_SCAN=0 (tests, A/B runs): the closest-hit scan of the plain F_IDENT kernel keeps its generic body for every query
+    if (const char *fa = getenv("MRT_AXIS_SCAN")) { if (!atoi(fa)) pk.P.axis_scan = 0u; }
     // the leaf queue of the warm mesh kernels takes what the LDS has left while the workgroups per CU stay the same (967-triangle
     // bench scene: 13 entries, +2 % over 8: fewer walks need a second round)
     if (in_lds && marker == kWarm && mesh_walk && has_walk_area(pk.features)) {

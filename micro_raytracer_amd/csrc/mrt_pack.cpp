@@ -775,6 +775,30 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
         const u32 tag = inst_tab[(size_t)i * INST_WORDS + INST_TAG];
         out.all_ident = (tag & TAG_IDENT) != 0u && memcmp(&xf_tab[tag >> TAG_XF_SHIFT], &xf_tab[xf0], XF_IDENT * sizeof(float)) == 0;
     }
+    // The AXIS table (mrt_scene.h): for scenes of untransformed planes and spheres whose planes all lie along an axis, the
+    // closest-hit scan of the plain F_IDENT kernel tests a plane with the one component of ray and position that its normal
+    // selects (mrt_trace.h trace; DESIGN.md section 7 has the argument that no bit changes).  The bound on the magnitudes keeps
+    // every shifted origin finite and every numerator inside the window of the division core.
+    std::vector<u32> axis_tab;
+    out.axis_scan = out.all_ident && out.features == 0u;
+    for (u32 i = 0; i < n_inst_total && out.axis_scan; ++i) {
+        const u32 *ir = &inst_tab[(size_t)i * INST_WORDS];
+        const u32 kind = ir[INST_TAG] & TAG_KIND_MASK;
+        auto bounded = [](u32 w) { return fabsf(fbits(w)) <= kAxisMax; };      // false for NaN and inf
+        u32 code = 0u, sd = 0u;
+        bool ok = bounded(ir[INST_POS]) && bounded(ir[INST_POS + 1]) && bounded(ir[INST_POS + 2]) && bounded(ir[INST_P3]);
+        if (kind == KIND_PLANE) {
+            u32 ones = 0u, zeros = 0u;
+            for (u32 k = 0; k < 3u; ++k) {
+                const u32 w = ir[INST_P5 + k], mag = w & 0x7fffffffu;
+                if (mag == 0x3f800000u) { ++ones; code = k + 1u; sd = ir[INST_P3] ^ (w & 0x80000000u); }      // s * d: d, or d with its sign flipped
+                else if (mag == 0u) ++zeros;
+            }
+            ok = ok && ones == 1u && zeros == 2u;
+        } else if (kind != KIND_SPHERE) ok = false;
+        axis_tab.push_back(code); axis_tab.push_back(sd);
+        out.axis_scan = ok;
+    }
     {
         // the culling margin of the instance BVH (mrt_trace.h), one per ray from the root box: 1e-4 of the origin distance (boxes,
         // triangles, mesh root boxes: rounding proportional to the distance) + 4e-6 / r_min of its SQUARE when spheres are bounded
@@ -797,6 +821,8 @@ int pack_scene(const mrt_render_desc *d, Packed &out, std::string &err, const Pa
     P.off_bvhinst = B.align4(); B.w.insert(B.w.end(), bvh_inst.begin(), bvh_inst.end());
     P.off_inst = B.align4(); B.w.insert(B.w.end(), inst_tab.begin(), inst_tab.end());
     P.off_instx = B.align4(); B.w.insert(B.w.end(), instx_tab.begin(), instx_tab.end());
+    P.off_axis = 0u; P.axis_scan = out.axis_scan ? 1u : 0u;
+    if (out.axis_scan) { P.off_axis = B.align4(); B.w.insert(B.w.end(), axis_tab.begin(), axis_tab.end()); }
     P.off_xf = B.align4(); for (float v : xf_tab) B.f(v);
     P.off_mat = B.align4(); B.w.insert(B.w.end(), mat_tab.begin(), mat_tab.end());
     P.off_light = B.align4();

@@ -17,6 +17,8 @@ struct Packed {
     float gamma = 0, exp = 0;
     u32 features = 0;            // F_* bits of mrt_trace.h the scene needs
     bool all_ident = false;      // every instance untransformed (TAG_IDENT): mrt_create adds F_IDENT to the features
+    bool axis_scan = false;      // the scene has the AXIS table of mrt_scene.h (P.off_axis, P.axis_scan): all_ident, planes and spheres
+                                 // only, every plane axis-aligned, every coordinate bounded
     bool tbvh_wide = false;      // the triangle-BVH table is the 4-wide one (PackOpts)
     u32 n_tex_u8 = 0, n_tex_f32 = 0, n_nodes = 0, n_leaf_ids = 0, n_tris = 0, n_xf = 0, n_bvh_nodes = 0, n_lin = 0, n_tbvh_nodes = 0;
     u32 off_vattr = 0, n_vattr_rows = 0;   // the per-corner attribute table (mrt_scene.h REND_VATTR): first word, rows (0: no renderer has any)

@@ -54,6 +54,15 @@ enum : u32 { VATTR_VN = 0, VATTR_UV = 9 };
 enum : u32 { INST_POS = 0, INST_P3 = 3, INST_TAG = 4, INST_P5 = 5 };
 enum : u32 { INSTX_REND = 0, INSTX_PLANE_NW = 1 };
 constexpr u32 INSTX_WORDS = 4;
+// AXIS (only for scenes the axis scan serves, Params.axis_scan: every instance untransformed, planes and spheres only, every
+// plane's unit normal n^ along an axis -- one component exactly +-1, the others +-0 --, every position, plane offset and r*r
+// finite and at most kAxisMax in magnitude; behind INSTX, one record per instance, in the order of INST):
+//   [0] code: 0 sphere | 1, 2, 3 plane along x, y, z   [1] plane: s * d, with s = the normal's +-1 and d = INST word 3 (exact)
+// The INST records are what they are without it; the closest-hit scan of the plain F_IDENT kernel reads this table instead of
+// tag and normal (mrt_trace.h trace).
+enum : u32 { AXIS_CODE = 0, AXIS_SD = 1 };
+constexpr u32 AXIS_WORDS = 2;
+constexpr float kAxisMax = 0x1p38f;
 constexpr u32 TAG_KIND_MASK = 7u, TAG_IDENT = 8u, TAG_XF_SHIFT = 4u;
 
 // XF: [0..8] L (lookat)  [9..17] R (rotate_y)  [18] 1 if both equal the identity as values
@@ -193,9 +202,12 @@ struct Params {
     u32 persist_grid;        // workgroups of a persistent launch (0: one workgroup per tile block, blockIdx addresses the tiles)
     u32 off_env;             // the ENV record of the sky's environment texture (F_ENV kernels; 0: none -- also in an F_ENV kernel, which
                              // a scene that only filters its material textures runs: tested at run time).  The last word of the block:
-                             // it takes what was the struct's tail padding, so the argument block keeps its size and every offset
+                             // it takes what was the struct's tail padding, so the argument block keeps every offset
+    u32 off_axis;            // the AXIS table (0: the scene has none)
+    u32 axis_scan;           // 1: the plain F_IDENT kernel's closest-hit scan may take the axis body (pack_scene: the scene has an AXIS
+                             // table; mrt_create clears it under MRT_AXIS_SCAN=0); wave-uniform, tested once per query
 };
-static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, off_env) + 4 == sizeof(Params), "off_env fills the tail of Params");
+static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, axis_scan) + 4 == sizeof(Params), "Params has no tail padding");
 
 // Tile-list launches (adaptive sampling, mrt_execute_adaptive): only the n 8x8 wave tiles tiles[i] = ty * n_tx + tx are traced.
 // A kernel argument of its own (pt_megakernel_list), not a Params field: the ordinary launches keep their argument block.

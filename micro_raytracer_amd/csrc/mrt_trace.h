@@ -36,6 +36,12 @@ enum : u32 {
                       // ~30 of ~220 cycles per instance on the Cornell box (8236 -> 8700 Msamples/s).  Exists for the plain
                       // 256-thread kernels of planes / spheres / boxes with and without lights; rays whose shifted origin has a
                       // zero, infinite or NaN component still take the reference's two mat-vecs (xf_vec)
+                      // AXIS SCAN (F_IDENT alone: planes and spheres, no lights, closest hit): a scene whose planes all lie along an
+                      // axis carries the AXIS table of mrt_scene.h (Params.axis_scan), and a query whose whole wavefront has every
+                      // direction component inside the division window and every origin component within kAxisMax scans it with
+                      // a second body (trace, "axis scan"): the three refined reciprocals of the direction once per ray, a plane
+                      // from the ONE component its normal selects.  Same bits; any other query, the shadow
+                      // query and every other kernel take the generic body
     F_ENV = 1024u,    // the sky has an environment texture (mrt.h mrt_env): env_uv / env_color at the two miss sites of
                       // render_pixel -- or the scene filters its textures: the bilinear lookups live in this
                       // family only, and a scene without an environment (Params.off_env == 0) takes the constant sky.  Like F_VATTR it exists with the full feature set only, and always together with F_VATTR
@@ -96,7 +102,7 @@ constexpr u32 kLeafQueue = MRT_LEAF_QUEUE;
 #ifndef MRT_PROBE_ROUND                // one round of a lane's triangle-BVH walk: box steps taken, triangles tested, membership boxes
 #define MRT_PROBE_ROUND(steps, tris, membs)
 #endif
-enum : u32 { CT_TRACE = 0, CT_LIN_TEST, CT_BVH_NODE, CT_BVH_TEST, CT_MESH_CALL, CT_MESH_ROOT_HIT, CT_TBVH_NODE, CT_TBVH_TRI, CT_TBVH_TRI_HIT, CT_MEMB_BOX, CT_TRACE_ANY, CT_WALK_OVERFLOW, CT_WALK_ROUND, CT_REF_TRI, CT_REF_BOX, CT_COUNT };
+enum : u32 { CT_TRACE = 0, CT_LIN_TEST, CT_BVH_NODE, CT_BVH_TEST, CT_MESH_CALL, CT_MESH_ROOT_HIT, CT_TBVH_NODE, CT_TBVH_TRI, CT_TBVH_TRI_HIT, CT_MEMB_BOX, CT_TRACE_ANY, CT_WALK_OVERFLOW, CT_WALK_ROUND, CT_REF_TRI, CT_REF_BOX, CT_AXIS_SCAN, CT_COUNT };
 enum : u32 { PH_ITER = 0, PH_REGEN, PH_SPHERE_MATH, PH_PLANE_HIT, PH_SHADE, PH_NORMAL_NONPLANE, PH_SCATTER1, PH_SCATTER2, PH_REFRACT, PH_EMIT_END, PH_LIGHTS, PH_COUNT };
 
 constexpr float kE = 0.0001f;                 // src/rt.rs:7
@@ -122,6 +128,8 @@ MRT_HD V3 ld3(const float *F, u32 i) { return v3(F[i], F[i + 1], F[i + 2]); }
 struct alignas(16) F4 { float x, y, z, w; };
 MRT_HD F4 ld4(const float *F, u32 i) { return *reinterpret_cast<const F4 *>(F + i); }   // i % 4 == 0 (records are 16-byte aligned)
 MRT_HD u32 ldu(const float *F, u32 i) { return f2u(F[i]); }
+struct alignas(8) F2 { float x, y; };
+MRT_HD F2 ld2(const float *F, u32 i) { return *reinterpret_cast<const F2 *>(F + i); }   // i % 2 == 0, F 8-byte aligned
 
 // true when x is neither zero, infinite nor NaN
 MRT_HD bool nzfin(float x)
@@ -1140,7 +1148,80 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
     // ---- linear scan: every instance, or (BVH scenes) the ones that cannot be bounded: planes, odd transforms ----
     const bool bvh = (FEAT & F_BVH) != 0;
     const u32 n = bvh ? P.n_lin : P.n_inst;
-    if (!bvh && !(FEAT & F_TRI) && n) {          // (with triangle / mesh code the test is too large to have twice)
+    // ---- axis scan (see F_IDENT): the same scan over a scene of spheres and axis-aligned planes, for a wavefront of tame rays ----
+    // Every direction component is inside the division window (so d_ok holds and ray_i is ray_), every origin component and
+    // every packed coordinate at most kAxisMax.  A plane along axis k with normal component s = +-1:
+    //   rd.n^ = s rd_k and ro.n^ = s ro_k exactly (the other products are zeros added to a non-zero term; a zero ro_k leaves
+    //   dot + d == d, or a zero numerator and a miss on both routes), so -(ro.n^ + d) / rd.n^ == -(ro_k + s d) / rd_k as real
+    //   numbers, and both divisions round correctly: the same tt.  Here tt is finite, a hit is tt > 0, and for a positive float
+    //   total_key is its bit pattern: `0 < bits < best_key` is the miss test and the key comparison at once.
+    // Spheres: the generic arithmetic.  Order, strict comparison, prefetch and the t0-from-key recovery are the generic scan's.
+    bool scanned = false;
+    if constexpr (!ANY && FEAT == F_IDENT && MRT_T0_FROM_KEY) {
+        const V3 o = ray_.o, d = ray_.d;
+        // (one predicate, no short-circuit branches: the test runs once per query with all lanes on)
+        const bool tame = (int)in_window(d.x) & (int)in_window(d.y) & (int)in_window(d.z) & (int)(fabs_(o.x) <= kAxisMax) & (int)(fabs_(o.y) <= kAxisMax) &
+                          (int)(fabs_(o.z) <= kAxisMax);
+        if (P.axis_scan && n && wave_all(tame)) {
+            scanned = true;
+            MRT_COUNT(CT_AXIS_SCAN);
+            const float *A = F + P.off_axis;
+#if defined(MRT_FAST_IEEE)
+            const V3 r = v3(rcp_refined_(d.x), rcp_refined_(d.y), rcp_refined_(d.z));
+#else
+            const V3 r = v3(0.0f, 0.0f, 0.0f);      // (unused: the x86 build divides)
+#endif
+            // one plane: ok, dk, rk = the ray's components along the plane's axis, pk the position's, sd = s * d.  Each axis has
+            // its own copy of this body behind a scalar branch (the components are named, never indexed: an index would put
+            // them into scratch)
+            auto plane = [&](u32 i, float ok, float dk, float rk, float pk, float sd) {
+                const float ro = pk + (ok - pk);
+                const float num = -(ro + sd);
+                float tt;
+#if defined(MRT_FAST_IEEE)
+                if (wave_all(fabs_(num) >= kWinLo)) tt = div_core_(num, dk, rk);      // (|num| <= 2^40 by the bounds)
+                else
+#endif
+                    tt = num / dk;
+                (void)rk;
+                const i32 kb = (i32)f2u(tt);
+                if (kb > 0 && kb < best_key) { best_key = kb; best.inst = i; best.t1 = tt; }
+            };
+            auto test = [&](u32 i, const F4 &ia, const F2 &ax) {
+                MRT_COUNT(CT_LIN_TEST);
+                MRT_PROBE_INST(i);
+                const u32 code = wave_uniform(f2u(ax.x));
+                if (code == 1u) plane(i, o.x, d.x, r.x, ia.x, ax.y);
+                else if (code == 2u) plane(i, o.y, d.y, r.y, ia.y, ax.y);
+                else if (code == 3u) plane(i, o.z, d.z, r.z, ia.z, ax.y);
+                else {
+                    const V3 pos = v3(ia.x, ia.y, ia.z);
+                    const V3 ro = add(pos, xf_vec(X0, true, sub(o, pos)));
+                    float t0 = 0.0f, t1 = 0.0f;
+                    if (sphere_isect(ia.w, sub(ro, pos), d, ray_.dd, t0, t1)) {
+                        const i32 key = total_key(t0);
+                        if (key < best_key) { best_key = key; best.inst = i; best.t1 = t1; }
+                    }
+                }
+            };
+            u32 j = 0;
+            F4 a0 = ld4(I, 0), b0 = a0;
+            F2 c0 = ld2(A, 0), e0 = c0;
+            for (;;) {
+                if (j + 1u < n) { b0 = ld4(I, (j + 1u) * INST_WORDS); e0 = ld2(A, (j + 1u) * AXIS_WORDS); }
+                test(j, a0, c0);
+                if (++j >= n) break;
+                if (j + 1u < n) { a0 = ld4(I, (j + 1u) * INST_WORDS); c0 = ld2(A, (j + 1u) * AXIS_WORDS); }
+                test(j, b0, e0);
+                if (++j >= n) break;
+            }
+            // no candidate ever carries the initial key (a NaN distance maps to 0x80000000), and an equal key never wins
+            best.rend = best_key != 0x7fffffff ? 0 : -1;
+        }
+    }
+    if (scanned) {
+        // (the axis scan has answered)
+    } else if (!bvh && !(FEAT & F_TRI) && n) {          // (with triangle / mesh code the test is too large to have twice)
         // two record buffers used in turn, each loaded one instance ahead of its use: the next record is in flight
         // while the current one is tested, and no register copies are needed to keep it (one buffer + a copy per
         // instance cost 8 v_mov each)
