@@ -20,6 +20,11 @@
  *       <= 3e-7 from the literal om_acosf -> om_sincosf composition, <= 6e-8 from the f64 truth.
  *       RULE: the restatement of reference arithmetic changes only together with a committed
  *       bound of this kind and a re-run of all five doc/out*.png pins.
+ *
+ * Beyond the reference (orc_create_ext): per-corner normals and UVs, the environment texture and the bilinear filter are
+ * restated from the contract text of DESIGN.md sections 14, 15 and 16 and of include/mrt.h (mrt_tri_attrs, mrt_env,
+ * mrt_desc_ext), each function citing its section.  They share no code with the kernel headers and know nothing of the packed
+ * layout: attributes are indexed by the description-order triangle id (hit_t.idx), texels are the description's f32 values.
  */
 #define _GNU_SOURCE
 #include "mrt_oracle.h"
@@ -175,6 +180,7 @@ typedef struct {
     uint32_t kind;
     float r; v3 n; v3 sizes; tri_t tri;
     tri_t *mesh; uint32_t n_mesh; bvh_t *bvh; uint32_t leaf_ids_total;
+    float *vn, *uv;   /* [n_tris][3][3] / [n_tris][3][2] in description order, NULL = none */
     mat_t mat;
     inst_t *inst; uint32_t n_inst;
 } rend_t;
@@ -186,6 +192,10 @@ struct orc_ctx {
     rend_t *rend; uint32_t n_rend;
     light_t *light; uint32_t n_light;
     v3 sky_color; float sky_pwr;
+    /* DESIGN.md sections 15, 16 (orc_create_ext) */
+    int has_env; tex_t env_tex; uint32_t env_map; float env_rot; int env_bilinear;
+    v3 sky_exhaust;       /* (sky.color x m) * sky.pwr: what an exhausted path starts its fold from */
+    int mat_bilinear;     /* mrt_desc_ext.reserved[0]: the scene-wide filter of the material maps */
     tex_t *tex; uint32_t n_tex;
     uint64_t seed;
     uint32_t nw, nh;
@@ -346,6 +356,119 @@ static v3 tex_get_color(const tex_t *t, v2 uv)
     return V3(t->dat[idx * 3], t->dat[idx * 3 + 1], t->dat[idx * 3 + 2]);
 }
 
+/* ------------------------------------------------------------------ beyond the reference: DESIGN.md sections 14-16 */
+/* The bilinear() block of DESIGN.md section 16.  clamp_v: v replicates the first / last row (environment, material maps on
+ * spheres); otherwise v repeats like u.  A coordinate beyond 2^30 texels or not finite takes the nearest rule's texel. */
+static inline int32_t wrap_index(int32_t i, int32_t n)   /* "one conditional + w, one conditional - w and a final clamp" */
+{
+    if (i < 0) i += n;
+    if (i >= n) i -= n;
+    if (i < 0) i = 0;
+    if (i > n - 1) i = n - 1;
+    return i;
+}
+static inline int32_t clamp_index(int32_t i, int32_t n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
+static inline v3 tex_texel(const tex_t *t, int32_t x, int32_t y)
+{
+    const float *q = t->dat + ((size_t)y * t->w + (size_t)x) * 3;
+    return V3(q[0], q[1], q[2]);
+}
+static inline float f_lerp(float a, float b, float f) { return a + f * (b - a); }
+static v3 tex_bilinear(const tex_t *t, v2 uv, int clamp_v)
+{
+    if (!t->dat) return V3(0.0f, 0.0f, 0.0f);
+    float x = uv.x * (float)t->w - 0.5f;
+    float y = uv.y * (float)t->h - 0.5f;
+    if (!(fabsf(x) < 1073741824.0f) || !(fabsf(y) < 1073741824.0f)) return tex_get_color(t, uv);
+    float xf = truncf(x); if (xf > x) xf = xf - 1.0f;
+    float yf = truncf(y); if (yf > y) yf = yf - 1.0f;
+    float fx = x - xf, fy = y - yf;
+    int32_t ix = (int32_t)xf, iy = (int32_t)yf, w = (int32_t)t->w, h = (int32_t)t->h;
+    int32_t x0 = wrap_index(ix, w);
+    int32_t x1 = (x0 + 1) % w;
+    int32_t y0, y1;
+    if (clamp_v) { y0 = clamp_index(iy, h); y1 = clamp_index(iy + 1, h); }
+    else { y0 = wrap_index(iy, h); y1 = (y0 + 1) % h; }
+    v3 t00 = tex_texel(t, x0, y0), t10 = tex_texel(t, x1, y0), t01 = tex_texel(t, x0, y1), t11 = tex_texel(t, x1, y1);
+    v3 top = V3(f_lerp(t00.x, t10.x, fx), f_lerp(t00.y, t10.y, fx), f_lerp(t00.z, t10.z, fx));
+    v3 bot = V3(f_lerp(t01.x, t11.x, fx), f_lerp(t01.y, t11.y, fx), f_lerp(t01.z, t11.z, fx));
+    return V3(f_lerp(top.x, bot.x, fy), f_lerp(top.y, bot.y, fy), f_lerp(top.z, bot.z, fy));
+}
+
+/* texture coordinate of the direction d of an escaping ray (d is not normalised again) */
+static v2 env_coord(uint32_t mapping, float rot, v3 d)
+{
+    v2 r;
+    float u = (0.5f + 0.5f * om_atan2f(d.x, -d.y) / OM_PI) + rot;
+    u = u - truncf(u);
+    if (u < 0.0f) u = 1.0f + u;
+    r.x = u;
+    if (mapping == MRT_ENV_LATLONG) r.y = om_acosf(f_min(f_max(d.z, -1.0f), 1.0f)) / OM_PI;
+    else r.y = 0.5f - 0.5f * d.z;
+    return r;
+}
+/* the texel a direction sees: nearest (tex_fetch's rule) or, section 16, bilinear with clamp_v = true */
+static v3 env_texel(const tex_t *t, uint32_t mapping, float rot, int bilinear, v3 d, v2 *uv_out)
+{
+    v2 uv = env_coord(mapping, rot, d);
+    if (uv_out) *uv_out = uv;
+    return bilinear ? tex_bilinear(t, uv, 1) : tex_get_color(t, uv);
+}
+/* DESIGN.md section 15, "exhausted path": the solid-angle-weighted mean m per channel, both sums in float64 in row-major
+ * order, the quotient rounded once to f32 */
+static v3 env_mean(const tex_t *t, uint32_t mapping)
+{
+    const double pi = 3.14159265358979323846;
+    double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
+    for (uint32_t y = 0; y < t->h; y++) {
+        double wy = 1.0;
+        if (mapping == MRT_ENV_LATLONG) wy = cos(pi * (double)y / (double)t->h) - cos(pi * ((double)y + 1.0) / (double)t->h);
+        for (uint32_t x = 0; x < t->w; x++) {
+            const float *q = t->dat + ((size_t)y * t->w + x) * 3;
+            for (int k = 0; k < 3; k++) num[k] += wy * (double)q[k];
+            den += wy;
+        }
+    }
+    return V3((float)(num[0] / den), (float)(num[1] / den), (float)(num[2] / den));
+}
+
+/* DESIGN.md section 14, the shading contract.  p = n_hit - pos; v0, e1 = v1 - v0, e2 = v2 - v0 */
+typedef struct { float b1, b2; int ok; } bary_t;
+static inline int f_finite(float x) { return !(x != x) && !isinf(x); }
+static bary_t attr_bary(v3 p, v3 v0, v3 e1, v3 e2)
+{
+    v3 q = v3_sub(p, v0);
+    float d00 = v3_dot(e1, e1), d01 = v3_dot(e1, e2), d11 = v3_dot(e2, e2), d20 = v3_dot(q, e1), d21 = v3_dot(q, e2);
+    float den = d00 * d11 - d01 * d01;
+    bary_t b;
+    b.b1 = (d11 * d20 - d01 * d21) / den;
+    b.b2 = (d00 * d21 - d01 * d20) / den;
+    b.ok = den != 0.0f && f_finite(den) && f_finite(b.b1) && f_finite(b.b2);
+    return b;
+}
+static inline float attr_mix(const bary_t *b, float a0, float a1, float a2) { return a0 + (b->b1 * (a1 - a0) + b->b2 * (a2 - a0)); }
+/* vn[3][3]: the interpolated normal (not normalised); cross(e1, e2) when the triangle is degenerate or the result is
+ * zero or not finite */
+static v3 attr_normal(v3 p, v3 v0, v3 e1, v3 e2, const float *vn)
+{
+    bary_t b = attr_bary(p, v0, e1, e2);
+    v3 n = V3(attr_mix(&b, vn[0], vn[3], vn[6]), attr_mix(&b, vn[1], vn[4], vn[7]), attr_mix(&b, vn[2], vn[5], vn[8]));
+    if (!b.ok || !f_finite(n.x) || !f_finite(n.y) || !f_finite(n.z) || (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f))
+        return v3_cross(e1, e2);
+    return n;
+}
+/* uv[3][2]: the interpolated coordinate (corner 0's for a degenerate triangle), wrapped like the plane's */
+static v2 attr_uv(v3 p, v3 v0, v3 e1, v3 e2, const float *uv)
+{
+    bary_t b = attr_bary(p, v0, e1, e2);
+    v2 r;
+    r.x = f_fract(b.ok ? attr_mix(&b, uv[0], uv[2], uv[4]) : uv[0]);
+    if (r.x < 0.0f) r.x = 1.0f + r.x;
+    r.y = f_fract(b.ok ? attr_mix(&b, uv[1], uv[3], uv[5]) : uv[1]);
+    if (r.y < 0.0f) r.y = 1.0f + r.y;
+    return r;
+}
+
 /* ------------------------------------------------------------------ BVH (src/rt.rs:630-703) */
 /* Triangle::check_in_aabb, src/rt.rs:227-248 */
 static int tri_in_aabb(const tri_t *t, v3 aabb, v3 rel_pos)
@@ -493,6 +616,10 @@ static int renderer_intersect(const rend_t *o, const inst_t *inst, const ray_t *
     return 0;
 }
 
+/* the triangle a hit names and its attribute row: a MRT_KIND_TRIANGLE renderer counts as n_tris = 1 (hit_t.idx is -1 there) */
+static inline const tri_t *tri_of(const rend_t *o, int32_t idx) { return o->kind == MRT_KIND_MESH ? &o->mesh[idx] : &o->tri; }
+static inline uint32_t tri_row(const rend_t *o, int32_t idx) { return o->kind == MRT_KIND_MESH ? (uint32_t)idx : 0u; }
+
 /* Renderer::normal, src/rt.rs:776-793 */
 static v3 renderer_normal(const rend_t *o, const inst_t *inst, const hit_t *hit)
 {
@@ -507,11 +634,15 @@ static v3 renderer_normal(const rend_t *o, const inst_t *inst, const hit_t *hit)
     case MRT_KIND_TRIANGLE: n = v3_cross(v3_sub(o->tri.b, o->tri.a), v3_sub(o->tri.c, o->tri.a)); break; /* :459-466 */
     default: { const tri_t *t = &o->mesh[hit->idx]; n = v3_cross(v3_sub(t->b, t->a), v3_sub(t->c, t->a)); break; }
     }
+    if (o->vn) {   /* the shading normal replaces the face normal, at the entry and the exit hit alike */
+        const tri_t *t = tri_of(o, hit->idx);
+        n = attr_normal(v3_sub(n_hit, inst->pos), t->a, v3_sub(t->b, t->a), v3_sub(t->c, t->a), o->vn + (size_t)tri_row(o, hit->idx) * 9);
+    }
     return v3_norm(xf_apply(&xf, n));
 }
 
 /* Renderer::to_uv, src/rt.rs:795-809 (triangle / mesh: todo!() => rejected at create, D7) */
-static v2 renderer_to_uv(const rend_t *o, const inst_t *inst, v3 hit)
+static v2 renderer_to_uv(const rend_t *o, const inst_t *inst, v3 hit, int32_t idx)
 {
     xf_t xf = inst_xf(inst);
     v3 n_hit = v3_add(inst->pos, xf_apply(&xf, v3_sub(hit, inst->pos)));
@@ -519,21 +650,36 @@ static v2 renderer_to_uv(const rend_t *o, const inst_t *inst, v3 hit)
     case MRT_KIND_SPHERE: return sphere_uv(n_hit, inst->pos);
     case MRT_KIND_PLANE: return plane_uv(n_hit);
     case MRT_KIND_BOX: return box_uv(o->sizes, n_hit, inst->pos);
-    default: { v2 z = {0.0f, 0.0f}; return z; }
+    default: {
+        if (o->uv) {   /* the UV of the triangle this hit names (entry: i0, exit: i1) at this hit's point */
+            const tri_t *t = tri_of(o, idx);
+            return attr_uv(v3_sub(n_hit, inst->pos), t->a, v3_sub(t->b, t->a), v3_sub(t->c, t->a), o->uv + (size_t)tri_row(o, idx) * 6);
+        }
+        v2 z = {0.0f, 0.0f}; return z;
     }
+    }
+}
+
+/* a material map's texel at a hit: nearest, or under the scene-wide switch the filter of DESIGN.md section 16, where v is
+ * clamped on a sphere (its v runs pole to pole) and repeats on every other kind */
+static v3 hit_texel(const orc_ctx *c, const hit_t *h, int32_t map)
+{
+    v2 uv = renderer_to_uv(h->obj, h->inst, ray_point(&h->ray), h->idx);
+    if (c->mat_bilinear) return tex_bilinear(&c->tex[map], uv, h->obj->kind == MRT_KIND_SPHERE);
+    return tex_get_color(&c->tex[map], uv);
 }
 
 /* Renderer::get_color .. get_emit, src/rt.rs:811-863, through RayHit::get_*, src/rt.rs:592-616 */
 static v3 hit_get_color(const orc_ctx *c, const hit_t *h)
 {
     const mat_t *m = &h->obj->mat;
-    if (m->map[0] >= 0) return v3_hadam(m->albedo, tex_get_color(&c->tex[m->map[0]], renderer_to_uv(h->obj, h->inst, ray_point(&h->ray))));
+    if (m->map[0] >= 0) return v3_hadam(m->albedo, hit_texel(c, h, m->map[0]));
     return m->albedo;
 }
 static float hit_get_scalar(const orc_ctx *c, const hit_t *h, int slot, float constant)
 {
     const mat_t *m = &h->obj->mat;
-    if (m->map[slot] >= 0) return tex_get_color(&c->tex[m->map[slot]], renderer_to_uv(h->obj, h->inst, ray_point(&h->ray))).x;
+    if (m->map[slot] >= 0) return hit_texel(c, h, m->map[slot]).x;
     return constant;
 }
 #define hit_get_rough(c, h)   hit_get_scalar(c, h, 1, (h)->obj->mat.rough)
@@ -688,11 +834,12 @@ static v3 trace_sample(const orc_ctx *c, scratch_t *s, const pixel_cam_t *pc, ui
     uint32_t pk = orc_path_key(c->seed, pixel, sample);
     ray_t next_ray = camera_ray(c, pc, pk);
     uint32_t n = 0;
+    int escaped = 0;      /* the path left the scene (in direction next_ray.dir) instead of running out of bounces */
     /* RaytraceIterator::next, collected (src/rt.rs:961) */
     while (next_ray.bounce <= c->bounce) {
         hit_t h0, h1;
         s->segments++;
-        if (!closest_hit(c, &next_ray, &s->ids, 1, &h0, &h1)) break;
+        if (!closest_hit(c, &next_ray, &s->ids, 1, &h0, &h1)) { escaped = 1; break; }
         uint8_t *vis = s->vis + (size_t)n * (c->n_light ? c->n_light : 1);
         v3 p0 = ray_point(&h0.ray);
         for (uint32_t li = 0; li < c->n_light; li++) {           /* src/rt.rs:1027-1046 */
@@ -710,9 +857,21 @@ static v3 trace_sample(const orc_ctx *c, scratch_t *s, const pixel_cam_t *pc, ui
         }
         s->path[n++] = n_hit;
     }
-    if (n == 0) return c->sky_color;                              /* src/rt.rs:957-959 */
-
-    v3 col = v3_muls(c->sky_color, c->sky_pwr);                   /* src/rt.rs:964 */
+    v3 col;
+    if (c->has_env) {
+        /* E(d) = sky.color x texel; primary miss E(d), later miss the fold from E(d) * sky.pwr, an
+         * exhausted path from (sky.color x m) * sky.pwr (section 16: the unfiltered mean under either filter) */
+        if (escaped) {
+            v3 e = v3_hadam(c->sky_color, env_texel(&c->env_tex, c->env_map, c->env_rot, c->env_bilinear, next_ray.dir, NULL));
+            if (n == 0) return e;
+            col = v3_muls(e, c->sky_pwr);
+        } else {
+            col = c->sky_exhaust;
+        }
+    } else {
+        if (n == 0) return c->sky_color;                          /* src/rt.rs:957-959 */
+        col = v3_muls(c->sky_color, c->sky_pwr);                  /* src/rt.rs:964 */
+    }
     for (uint32_t k = n; k-- > 0;) {
         const hit_t *hit = &s->path[k];
         const uint8_t *vis = s->vis + (size_t)k * (c->n_light ? c->n_light : 1);
@@ -950,7 +1109,7 @@ static int validate_material(const orc_ctx *c, const rend_t *o)
     const mat_t *m = &o->mat;
     for (int k = 0; k < 6; k++) {
         if (m->map[k] >= (int32_t)c->n_tex) return fail("material map index out of range");
-        if (m->map[k] >= 0 && (o->kind == MRT_KIND_TRIANGLE || o->kind == MRT_KIND_MESH))
+        if (m->map[k] >= 0 && (o->kind == MRT_KIND_TRIANGLE || o->kind == MRT_KIND_MESH) && !o->uv)   /* with uv: DESIGN.md section 14 */
             return fail("textured triangle/mesh: reference hits todo!() (src/rt.rs:546,806)");
         if (m->map[k] >= 0 && c->tex[m->map[k]].dat && (c->tex[m->map[k]].w == 0 || c->tex[m->map[k]].h == 0))
             return fail("empty texture: reference would panic on index (src/rt.rs:624)");
@@ -968,11 +1127,40 @@ static int validate_material(const orc_ctx *c, const rend_t *o)
     return 1;
 }
 
-orc_ctx *orc_create(const mrt_render_desc *d, uint64_t seed)
+static float *copy_floats(const float *src, size_t n)
+{
+    float *q = (float *)malloc(sizeof(float) * (n ? n : 1));
+    memcpy(q, src, sizeof(float) * n);
+    return q;
+}
+
+/* the environment of an ext (include/mrt.h mrt_env: what mrt_create_ext rejects is rejected here) */
+static int take_env(orc_ctx *c, const mrt_env *e)
+{
+    if (e->tex.w == 0 || e->tex.h == 0) return fail("env.tex: no texels");
+    if (!e->tex.dat) return fail("env.tex.dat is null");
+    if ((uint64_t)e->tex.w * e->tex.h > (1ull << 25)) return fail("env.tex: more than 2^25 texels");
+    if (e->mapping != MRT_ENV_SPHERE && e->mapping != MRT_ENV_LATLONG) return fail("env.mapping unknown");
+    if (!f_finite(e->rot)) return fail("env.rot is not finite");
+    if (e->filter != MRT_FILTER_NEAREST && e->filter != MRT_FILTER_BILINEAR) return fail("env.filter unknown");
+    size_t n = (size_t)e->tex.w * e->tex.h * 3;
+    for (size_t i = 0; i < n; i++) if (!f_finite(e->tex.dat[i]) || e->tex.dat[i] < 0.0f) return fail("env.tex: texel negative or not finite");
+    c->has_env = 1;
+    c->env_tex.w = e->tex.w; c->env_tex.h = e->tex.h; c->env_tex.dat = copy_floats(e->tex.dat, n);
+    c->env_map = e->mapping; c->env_rot = e->rot; c->env_bilinear = e->filter == MRT_FILTER_BILINEAR;
+    c->sky_exhaust = v3_muls(v3_hadam(c->sky_color, env_mean(&c->env_tex, c->env_map)), c->sky_pwr);
+    return 1;
+}
+
+static orc_ctx *create_impl(const mrt_render_desc *d, const mrt_desc_ext *ext, uint64_t seed)
 {
     g_err[0] = 0;
     if (!d) { fail("null desc"); return NULL; }
+    if (ext && ext->attrs && ext->n_renderer != d->scene.n_renderer) { fail("ext.n_renderer != scene.n_renderer"); return NULL; }
+    if (ext && ext->reserved[0] != MRT_FILTER_NEAREST && ext->reserved[0] != MRT_FILTER_BILINEAR) { fail("ext.reserved[0]: unknown filter"); return NULL; }
+    if (ext && ext->reserved[1] != 0) { fail("ext.reserved[1] must be 0"); return NULL; }
     orc_ctx *c = (orc_ctx *)calloc(1, sizeof(orc_ctx));
+    c->mat_bilinear = ext && ext->reserved[0] == MRT_FILTER_BILINEAR;
     c->bounce = d->rt.bounce; c->loss = d->rt.loss;
     c->res_w = d->frame.res_w; c->res_h = d->frame.res_h; c->ssaa = d->frame.ssaa; c->cam = d->frame.cam;
     c->seed = seed;
@@ -1040,19 +1228,34 @@ orc_ctx *orc_create(const mrt_render_desc *d, uint64_t seed)
             }
             if (o->n_mesh > c->max_ids) c->max_ids = o->n_mesh;
         }
+        if (ext && ext->attrs && (ext->attrs[i].uv || ext->attrs[i].vn)) {          /* DESIGN.md section 14 */
+            if (r->kind != MRT_KIND_TRIANGLE && r->kind != MRT_KIND_MESH) { ok = fail("attributes on a sphere, plane or box"); break; }
+            size_t nt = r->kind == MRT_KIND_MESH ? r->n_tris : 1;
+            if (ext->attrs[i].vn) o->vn = copy_floats(ext->attrs[i].vn, nt * 9);
+            if (ext->attrs[i].uv) {
+                o->uv = copy_floats(ext->attrs[i].uv, nt * 6);
+                for (size_t k = 0; k < nt * 6; k++) if (!f_finite(o->uv[k])) { ok = fail("uv is not finite"); break; }
+                if (!ok) break;
+            }
+        }
         if (!validate_material(c, o)) ok = 0;
     }
+    if (ok && ext && ext->env && !take_env(c, ext->env)) ok = 0;
     if (ok && (c->nw == 0 || c->nh == 0)) ok = fail("empty frame");
     if (!ok) { orc_destroy(c); return NULL; }
     c->colors = (float *)calloc((size_t)c->nw * c->nh * 3, sizeof(float));
     return c;
 }
 
+orc_ctx *orc_create(const mrt_render_desc *d, uint64_t seed) { return create_impl(d, NULL, seed); }
+orc_ctx *orc_create_ext(const mrt_render_desc *d, const mrt_desc_ext *ext, uint64_t seed) { return create_impl(d, ext, seed); }
+
 void orc_destroy(orc_ctx *c)
 {
     if (!c) return;
-    for (uint32_t i = 0; i < c->n_rend; i++) { free(c->rend[i].inst); free(c->rend[i].mesh); bvh_free(c->rend[i].bvh); }
+    for (uint32_t i = 0; i < c->n_rend; i++) { free(c->rend[i].inst); free(c->rend[i].mesh); bvh_free(c->rend[i].bvh); free(c->rend[i].vn); free(c->rend[i].uv); }
     for (uint32_t i = 0; i < c->n_tex; i++) free(c->tex[i].dat);
+    free(c->env_tex.dat);
     free(c->rend); free(c->tex); free(c->light); free(c->colors); free(c);
 }
 
@@ -1113,4 +1316,38 @@ void orc_math(int op, const float *a, const float *b, float *out, size_t n)
         default: out[i] = 0.0f;
         }
     }
+}
+
+/* ------------------------------------------------------------------ elementwise pieces of DESIGN.md sections 14-16, for anchoring */
+/* n cases of p[3], v0[3], e1[3], e2[3], vn[9], uv[6]: the un-normalised shading normal (or its fall-back) and the wrapped UV */
+void orc_vattr(size_t n, const float *p, const float *v0, const float *e1, const float *e2, const float *vn, const float *uv,
+               float *normal_out, float *uv_out)
+{
+    for (size_t i = 0; i < n; i++) {
+        v3 P = V3(p[i * 3], p[i * 3 + 1], p[i * 3 + 2]), A = V3(v0[i * 3], v0[i * 3 + 1], v0[i * 3 + 2]);
+        v3 E1 = V3(e1[i * 3], e1[i * 3 + 1], e1[i * 3 + 2]), E2 = V3(e2[i * 3], e2[i * 3 + 1], e2[i * 3 + 2]);
+        if (normal_out) { v3 r = attr_normal(P, A, E1, E2, vn + i * 9); normal_out[i * 3] = r.x; normal_out[i * 3 + 1] = r.y; normal_out[i * 3 + 2] = r.z; }
+        if (uv_out) { v2 r = attr_uv(P, A, E1, E2, uv + i * 6); uv_out[i * 2] = r.x; uv_out[i * 2 + 1] = r.y; }
+    }
+}
+
+/* n directions d[3] on the w x h f32 texture dat: the texel each one sees (without sky.color) and its coordinate */
+void orc_env_lookup(uint32_t w, uint32_t h, const float *dat, uint32_t mapping, float rot, uint32_t filter, size_t n, const float *d,
+                    float *rgb_out, float *uv_out)
+{
+    tex_t t; t.w = w; t.h = h; t.dat = (float *)dat;
+    for (size_t i = 0; i < n; i++) {
+        v2 uv;
+        v3 r = env_texel(&t, mapping, rot, filter == MRT_FILTER_BILINEAR, V3(d[i * 3], d[i * 3 + 1], d[i * 3 + 2]), &uv);
+        if (rgb_out) { rgb_out[i * 3] = r.x; rgb_out[i * 3 + 1] = r.y; rgb_out[i * 3 + 2] = r.z; }
+        if (uv_out) { uv_out[i * 2] = uv.x; uv_out[i * 2 + 1] = uv.y; }
+    }
+}
+
+/* the mean m an exhausted path takes in the texel's place */
+void orc_env_mean(uint32_t w, uint32_t h, const float *dat, uint32_t mapping, float m_out[3])
+{
+    tex_t t; t.w = w; t.h = h; t.dat = (float *)dat;
+    v3 m = env_mean(&t, mapping);
+    m_out[0] = m.x; m_out[1] = m.y; m_out[2] = m.z;
 }

@@ -14,6 +14,14 @@
  * `image` crate's Lanczos3 are third-party code absent from the reference tree: the
  * seeded counter RNG is build-defined => sample-level parity with the Rust
  * binary is UNPINNED (statistical only); Lanczos3 follows image 0.24's published algorithm.
+ *
+ * BEYOND THE REFERENCE: orc_create_ext also restates what mrt_create_ext adds to the path -- per-corner normals and UVs
+ * (DESIGN.md section 14), the environment texture (section 15) and the bilinear filter (section 16) -- from the contract text
+ * of those sections and of include/mrt.h, not from the kernel headers.  It indexes attributes by the description-order
+ * triangle id and reads the description's f32 texels, so the packer's leaf order and texel formats are checked too.  There is
+ * nothing in the reference to pin these against: they are held to the x86 build of the kernel headers and to the GPU
+ * (tests/test_oracle_ext.py, tests/test_gpu_oracle_ext.py), and their elementwise pieces to the float32 numpy restatements of
+ * tests/vattr_ref.py, tests/env_ref.py and tests/filter_ref.py.
  */
 #ifndef MRT_ORACLE_H
 #define MRT_ORACLE_H
@@ -30,6 +38,10 @@ typedef struct orc_ctx orc_ctx;
 
 /* Deep-copies the description; builds mesh octrees (src/parser.rs:815-816). NULL + orc_error() on reject. */
 orc_ctx *orc_create(const mrt_render_desc *desc, uint64_t seed);
+/* The same for a scene with attributes, an environment or filtered textures (mrt_create_ext).  ext == NULL, or an ext that
+ * requests nothing: exactly orc_create.  Rejects what mrt_create_ext rejects (texture maps on a triangle / mesh without uv
+ * included). */
+orc_ctx *orc_create_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, uint64_t seed);
 void orc_destroy(orc_ctx *c);
 const char *orc_error(void);
 
@@ -73,6 +85,18 @@ float    orc_draw_f32(uint32_t path_key, uint32_t dim);
 
 /* math contract (elementwise) : op as in mrt_selftest_math */
 void orc_math(int op, const float *a, const float *b, float *out, size_t n);
+
+/* DESIGN.md sections 14-16, elementwise (tests/test_oracle_ext.py anchors them to the numpy restatements):
+ * orc_vattr      n cases p[3], v0[3], e1[3], e2[3], vn[9], uv[6] -> the shading normal before xf_vec / norm (the face normal
+ *                where the contract falls back) and the wrapped UV; either output may be NULL (then its input may be too)
+ * orc_env_lookup n directions d[3] -> the texel of the w x h f32 texture each one sees (E(d) without sky.color) under
+ *                mapping (MRT_ENV_*), rot and filter (MRT_FILTER_*), and its coordinate; either output may be NULL
+ * orc_env_mean   the solid-angle-weighted mean m of the texture */
+void orc_vattr(size_t n, const float *p, const float *v0, const float *e1, const float *e2, const float *vn, const float *uv,
+               float *normal_out, float *uv_out);
+void orc_env_lookup(uint32_t w, uint32_t h, const float *dat, uint32_t mapping, float rot, uint32_t filter, size_t n, const float *d,
+                    float *rgb_out, float *uv_out);
+void orc_env_mean(uint32_t w, uint32_t h, const float *dat, uint32_t mapping, float m_out[3]);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,8 @@ def lib():
     vp, u32, u64, f32p, u8p, u32p = C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
     L.orc_create.restype = vp
     L.orc_create.argtypes = [vp, u64]
+    L.orc_create_ext.restype = vp
+    L.orc_create_ext.argtypes = [vp, vp, u64]
     L.orc_destroy.argtypes = [vp]
     L.orc_error.restype = C.c_char_p
     L.orc_dims.argtypes = [vp, u32p, u32p]
@@ -60,6 +62,12 @@ def lib():
     L.orc_draw_f32.restype = C.c_float
     L.orc_draw_f32.argtypes = [u32, u32]
     L.orc_math.argtypes = [C.c_int, f32p, f32p, f32p, C.c_size_t]
+    L.orc_vattr.argtypes = [C.c_size_t, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p]
+    L.orc_vattr.restype = None
+    L.orc_env_lookup.argtypes = [u32, u32, f32p, u32, C.c_float, u32, C.c_size_t, f32p, f32p, f32p]
+    L.orc_env_lookup.restype = None
+    L.orc_env_mean.argtypes = [u32, u32, f32p, u32, f32p]
+    L.orc_env_mean.restype = None
     _LIB = L
     return L
 
@@ -78,7 +86,11 @@ class Oracle:
     def __init__(self, desc_holder, seed=1):
         L = lib()
         self._h = desc_holder
-        self._c = L.orc_create(C.cast(desc_holder.ptr(), C.c_void_p), C.c_uint64(seed))
+        ext = desc_holder.ext_ptr()      # attributes, environment, filters (mrt_desc_ext): never silently dropped
+        if ext is not None:
+            self._c = L.orc_create_ext(C.cast(desc_holder.ptr(), C.c_void_p), ext, C.c_uint64(seed))
+        else:
+            self._c = L.orc_create(C.cast(desc_holder.ptr(), C.c_void_p), C.c_uint64(seed))
         if not self._c:
             raise ValueError(L.orc_error().decode())
         nw, nh = C.c_uint32(), C.c_uint32()
@@ -161,6 +173,33 @@ def math(op, a, b=None):
         b = np.ascontiguousarray(b, np.float32)
         bp = _fp(b)
     lib().orc_math(op, _fp(a), bp, _fp(out), a.size)
+    return out
+
+
+def vattr(p, v0, e1, e2, vn, uv):
+    """DESIGN.md section 14 elementwise: (shading normal before xf_vec / norm, wrapped UV) of n cases."""
+    a = [np.ascontiguousarray(x, np.float32) for x in (p, v0, e1, e2, vn, uv)]
+    n = a[0].shape[0]
+    nrm, tex = np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float32)
+    lib().orc_vattr(n, *[_fp(x) for x in a], _fp(nrm), _fp(tex))
+    return nrm, tex
+
+
+def env_lookup(w, h, dat, mapping, rot, filt, d):
+    """DESIGN.md sections 15 / 16 elementwise: (texel, coordinate) of n directions; mapping / filt are MRT_ENV_* / MRT_FILTER_*."""
+    dat = np.ascontiguousarray(dat, np.float32)
+    assert dat.size == w * h * 3
+    d = np.ascontiguousarray(d, np.float32)
+    rgb, uv = np.zeros((d.shape[0], 3), np.float32), np.zeros((d.shape[0], 2), np.float32)
+    lib().orc_env_lookup(w, h, _fp(dat), mapping, C.c_float(float(np.float32(rot))), filt, d.shape[0], _fp(d), _fp(rgb), _fp(uv))
+    return rgb, uv
+
+
+def env_mean(w, h, dat, mapping):
+    dat = np.ascontiguousarray(dat, np.float32)
+    assert dat.size == w * h * 3
+    out = np.zeros(3, np.float32)
+    lib().orc_env_mean(w, h, _fp(dat), mapping, _fp(out))
     return out
 
 
