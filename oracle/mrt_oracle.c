@@ -25,6 +25,8 @@
  * restated from the contract text of DESIGN.md sections 14, 15 and 16 and of include/mrt.h (mrt_tri_attrs, mrt_env,
  * mrt_desc_ext), each function citing its section.  They share no code with the kernel headers and know nothing of the packed
  * layout: attributes are indexed by the description-order triangle id (hit_t.idx), texels are the description's f32 values.
+ * orc_aov (first-hit AOVs) is written from the same text and reuses this file's pixel_cam, closest_hit,
+ * renderer_normal and hit_get_color.
  */
 #define _GNU_SOURCE
 #include "mrt_oracle.h"
@@ -910,6 +912,51 @@ void orc_trace_pixel(const orc_ctx *c, uint32_t x, uint32_t y, uint32_t sidx, fl
     v3 col = trace_sample(c, &s, &pc, y * c->nw + x, sidx);
     rgb[0] = col.x; rgb[1] = col.y; rgb[2] = col.z;
     if (segments) *segments = (uint32_t)s.segments;
+    scratch_free(&s);
+}
+
+/* ------------------------------------------------------------------ first-hit AOVs (beyond the reference) */
+/* Written from the contract text: section 13 -- one ray per supersampled pixel from the lens CENTRE (the camera ray of
+ * src/rt.rs:916-931 with the lens position at cam.pos: no random draw), its closest hit, depth t0 along the unit direction from
+ * the origin Ray::cast shifted by E_, world normal, albedo x texture at the hit's UV, world point o + d t0, ids in description
+ * order; section 14 -- the normal is the shading normal, the UV the interpolated one (renderer_normal / renderer_to_uv take
+ * both); sections 15, 16 -- with an environment the albedo of a miss is E(d) = sky.color x texel(d) of the centre ray's
+ * direction, under the environment's mapping, rot and filter: no sky.pwr, no mean.  Every other plane of a miss: depth +inf,
+ * normal and point 0, ids -1; without an environment its albedo is 0.  Any output may be NULL. */
+static ray_t camera_ray_centre(const orc_ctx *c, const pixel_cam_t *pc)
+{
+    v3 pos = V3(c->cam.pos[0], c->cam.pos[1], c->cam.pos[2]);
+    v3 new_dir = v3_norm(v3_sub(pc->focus, pos));
+    v4 cd = {c->cam.dir[0], c->cam.dir[1], c->cam.dir[2], c->cam.dir[3]};
+    m3 look = m3_lookat(cd, V3(0.0f, 0.0f, 1.0f));
+    m3 rot_y = m3_rotate_y(cd);
+    v3 t = m3_mul(&look, new_dir);
+    return ray_cast_default(pos, m3_mul(&rot_y, t));
+}
+
+void orc_aov(const orc_ctx *c, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance, float *point)
+{
+    scratch_t s; scratch_init(c, &s);
+    for (uint32_t y = 0; y < c->nh; y++)
+        for (uint32_t x = 0; x < c->nw; x++) {
+            size_t p = (size_t)y * c->nw + x;
+            pixel_cam_t pc = pixel_cam(c, (float)x, (float)y);
+            ray_t ray = camera_ray_centre(c, &pc);
+            hit_t h0, h1;
+            float t = INFINITY; v3 n = V3(0.0f, 0.0f, 0.0f), a = n, w = n; int32_t r = -1, i = -1;
+            if (closest_hit(c, &ray, &s.ids, 1, &h0, &h1)) {
+                t = h0.ray.t; n = h0.norm; a = hit_get_color(c, &h0); w = ray_point(&h0.ray);
+                r = (int32_t)(h0.obj - c->rend); i = (int32_t)(h0.inst - h0.obj->inst);
+            } else if (c->has_env) {
+                a = v3_hadam(c->sky_color, env_texel(&c->env_tex, c->env_map, c->env_rot, c->env_bilinear, ray.dir, NULL));
+            }
+            if (depth) depth[p] = t;
+            if (normal) { normal[3 * p] = n.x; normal[3 * p + 1] = n.y; normal[3 * p + 2] = n.z; }
+            if (albedo) { albedo[3 * p] = a.x; albedo[3 * p + 1] = a.y; albedo[3 * p + 2] = a.z; }
+            if (point) { point[3 * p] = w.x; point[3 * p + 1] = w.y; point[3 * p + 2] = w.z; }
+            if (renderer) renderer[p] = r;
+            if (instance) instance[p] = i;
+        }
     scratch_free(&s);
 }
 

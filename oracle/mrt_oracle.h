@@ -22,6 +22,13 @@
  * nothing in the reference to pin these against: they are held to the x86 build of the kernel headers and to the GPU
  * (tests/test_oracle_ext.py, tests/test_gpu_oracle_ext.py), and their elementwise pieces to the float32 numpy restatements of
  * tests/vattr_ref.py, tests/env_ref.py and tests/filter_ref.py.
+ *
+ * FIRST-HIT AOVS: orc_aov restates mrt_aov from DESIGN.md section 13 (lens-centre ray, closest hit, t0, world normal, albedo x
+ * texture, world point, description-order ids), section 14 (shading normal, interpolated UV) and sections 15 / 16 (the albedo of
+ * a miss under an environment is E(d) = sky.color (hadamard) texel, the texel the centre ray's direction d sees under the
+ * environment's mapping, rot and filter -- neither sky.pwr nor the mean m enters it), not from csrc/mrt_denoise.h.  It is
+ * anchored to float64 closest hits, rotated instances and camera included, and holds the x86 build of aov_pixel and the GPU to
+ * bit equality on every plane (tests/test_oracle_aov.py, tests/test_gpu_oracle_aov.py, the fuzz of tests/test_fuzz_scenes.py).
  */
 #ifndef MRT_ORACLE_H
 #define MRT_ORACLE_H
@@ -67,6 +74,15 @@ int orc_img_ss(const orc_ctx *c, uint8_t *rgb8);   /* before the resize: rgb8[nh
 
 /* One reduce_light(iter(x, y)) evaluation (src/rt.rs:937-994) for sample index s. */
 void orc_trace_pixel(const orc_ctx *c, uint32_t x, uint32_t y, uint32_t s, float rgb[3], uint32_t *segments);
+
+/* First-hit AOVs of the supersampled frame (with the additions of sections 14-16), one ray per pixel
+ * through the lens centre, no random draw: depth[nh][nw] (t0 along the unit direction, +inf on a miss), normal[nh][nw][3] (the
+ * world shading normal), albedo[nh][nw][3] (albedo x texture at the hit's UV), renderer[nh][nw] (index into mrt_scene.renderer),
+ * instance[nh][nw] (index into that renderer's inst list), point[nh][nw][3] (o + d t0, o the shifted origin).  A miss has
+ * normal, point 0 and ids -1; its albedo is 0, or with an environment E(d) = sky.color x texel, the texel being the one the
+ * centre ray's direction d sees under the environment's mapping, rot and filter (no sky.pwr, not the mean).  Any output may be
+ * NULL. */
+void orc_aov(const orc_ctx *c, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance, float *point);
 
 /* Stand-alone pieces for unit tests */
 void orc_tonemap_px(const float sum[3], uint32_t count, float gamma, float exp, uint8_t out[3]);

@@ -50,6 +50,8 @@ def lib():
     L.orc_segments.argtypes = [vp]
     L.orc_img.argtypes = [vp, u8p]
     L.orc_img_ss.argtypes = [vp, u8p]
+    L.orc_aov.argtypes = [vp, f32p, f32p, f32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), f32p]
+    L.orc_aov.restype = None
     L.orc_trace_pixel.argtypes = [vp, u32, u32, u32, f32p, u32p]
     L.orc_tonemap_px.argtypes = [f32p, u32, C.c_float, C.c_float, u8p]
     L.orc_lanczos3_resize.argtypes = [u8p, u32, u32, u8p, u32, u32]
@@ -143,6 +145,17 @@ class Oracle:
         out = np.empty((self.nh, self.nw, 3), np.uint8)
         if lib().orc_img_ss(self._c, _up(out)) != 0:
             raise RuntimeError("img before any sample")
+        return out
+
+    def aov(self):
+        """First-hit AOVs of the supersampled frame (orc_aov): the planes of Sampler.aov() -- depth f32 [nh][nw] (inf: miss),
+        normal and albedo f32 [nh][nw][3], renderer and instance int32 [nh][nw] (-1: miss) -- plus the world point f32 [nh][nw][3]."""
+        sh = (self.nh, self.nw)
+        out = {"depth": np.empty(sh, np.float32), "normal": np.empty(sh + (3,), np.float32), "albedo": np.empty(sh + (3,), np.float32),
+               "renderer": np.empty(sh, np.int32), "instance": np.empty(sh, np.int32), "point": np.empty(sh + (3,), np.float32)}
+        ip = C.POINTER(C.c_int32)
+        lib().orc_aov(self._c, _fp(out["depth"]), _fp(out["normal"]), _fp(out["albedo"]), out["renderer"].ctypes.data_as(ip),
+                      out["instance"].ctypes.data_as(ip), _fp(out["point"]))
         return out
 
     def trace_pixel(self, x, y, s):

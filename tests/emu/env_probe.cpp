@@ -123,14 +123,17 @@ int ev_sky_init(const mrt_render_desc *d, const mrt_desc_ext *ext, float *out /*
     return 0;
 }
 
-// mrt_aov: guide[nh][nw][8] (normal, depth, world point, hit flag), albedo[nh][nw][3], renderer[nh][nw]
-int ev_aov(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, float *albedo, int32_t *renderer)
+// mrt_aov: guide[nh][nw][8] (normal, depth, world point, hit flag), albedo[nh][nw][3], renderer[nh][nw] and, where instance is not
+// NULL, instance[nh][nw]: the index within the renderer's inst list (the flat index less the renderer's first, as mrt_aov maps it)
+int ev_aov_inst(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, float *albedo, int32_t *renderer, int32_t *instance)
 {
     Packing k;
     const int rc = pack(d, ext, k);
     if (rc) return rc;
     unsigned long long seg[8] = {0};
     k.P.segments = seg;
+    std::vector<u32> first(k.P.n_rend, 0u);
+    for (u32 i = k.P.n_inst; i-- > 0;) first[k.pk.blob[k.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
     for (u32 y = 0; y < k.pk.nh; ++y)
         for (u32 x = 0; x < k.pk.nw; ++x) {
             const AovPixel a = aov_one(k, x, y);
@@ -138,8 +141,14 @@ int ev_aov(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, floa
             memcpy(guide + 8 * p, &a.g, sizeof(DnGuide));
             albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
             renderer[p] = a.rend;
+            if (instance) instance[p] = a.rend < 0 ? -1 : a.inst - (i32)first[(u32)a.rend];
         }
     return 0;
+}
+
+int ev_aov(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, float *albedo, int32_t *renderer)
+{
+    return ev_aov_inst(d, ext, guide, albedo, renderer, nullptr);
 }
 
 // mrt_denoise: the filtered means out[nh][nw][3] of the sums A[nh][nw][3] at per-pixel counts[nh][nw]; env: the context has an

@@ -46,10 +46,25 @@ def build_probe(out_dir):
     L.ev_pack.argtypes = [vp, vp, u32p, vp, u32p, C.c_uint64]
     L.ev_sky_init.argtypes = [vp, vp, fp]
     L.ev_aov.argtypes = [vp, vp, fp, fp, i32p]
+    L.ev_aov_inst.argtypes = [vp, vp, fp, fp, i32p, i32p]
     L.ev_filter.argtypes = [fp, u32p, fp, fp, u32, u32, u32, C.c_float, C.c_float, C.c_float, u32, fp]
     L.ev_filter.restype = None
     L.ev_render.argtypes = [vp, vp, C.c_uint64, u32, u32, u32, u32, fp]
     return L
+
+
+_SHARED = []
+
+
+def shared_probe():
+    """One build of the probe per process, for the modules that only call it (the build takes about a minute)."""
+    if not _SHARED:
+        import atexit
+        import tempfile
+        d = tempfile.mkdtemp(prefix="env_probe_")
+        atexit.register(shutil.rmtree, d, True)
+        _SHARED.append(build_probe(d))
+    return _SHARED[0]
 
 
 def _p(a, t=C.c_float):
@@ -108,8 +123,14 @@ def x86_sky_init(L, holder):
     return out
 
 
+def ss_dims(holder):
+    """(nw, nh) of the supersampled frame the probe writes: `(res as f32 * ssaa) as usize` (src/sampler.rs:29-30), not frame.res."""
+    fr = holder.desc.frame
+    return int(f32(fr.res_w) * f32(fr.ssaa)), int(f32(fr.res_h) * f32(fr.ssaa))
+
+
 def x86_aov(L, holder):
-    nw, nh = holder.desc.frame.res_w, holder.desc.frame.res_h
+    nw, nh = ss_dims(holder)
     g, alb, rend = np.zeros((nh, nw, 8), f32), np.zeros((nh, nw, 3), f32), np.zeros((nh, nw), np.int32)
     d, e = _ptrs(holder)
     rc = L.ev_aov(d, e, _p(g), _p(alb), _p(rend, C.c_int32))
@@ -117,8 +138,18 @@ def x86_aov(L, holder):
     return g, alb, rend
 
 
+def x86_aov_inst(L, holder):
+    """x86_aov plus the instance plane (the index within the renderer's inst list, -1 on a miss)."""
+    nw, nh = ss_dims(holder)
+    g, alb, rend, inst = np.zeros((nh, nw, 8), f32), np.zeros((nh, nw, 3), f32), np.zeros((nh, nw), np.int32), np.zeros((nh, nw), np.int32)
+    d, e = _ptrs(holder)
+    rc = L.ev_aov_inst(d, e, _p(g), _p(alb), _p(rend, C.c_int32), _p(inst, C.c_int32))
+    assert rc == 0, L.ev_error()
+    return g, alb, rend, inst
+
+
 def x86_render(L, holder, seed, n_samples, warm=False, sample_base=0, threads=8, with_ext=True):
-    nw, nh = holder.desc.frame.res_w, holder.desc.frame.res_h
+    nw, nh = ss_dims(holder)
     acc = np.zeros((nh, nw, 3), f32)
     d, e = _ptrs(holder, with_ext)
     rc = L.ev_render(d, e, seed, sample_base, n_samples, threads, 1 if warm else 0, _p(acc))

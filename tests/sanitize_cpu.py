@@ -37,5 +37,6 @@ for d in descs:
     got,_=E.render(h,3,spp,threads=3)
     _check(got,ref,spp)
     o.set_accum(got,spp); ss,out=E.img(h,got,spp); assert np.array_equal(out,o.img())
+    a=o.aov(); assert a["depth"].shape==(o.nh,o.nw)        # orc_aov writes the supersampled frame
     o.close(); n+=1
 print("sanitizer run ok:", n, "scenes")

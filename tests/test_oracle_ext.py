@@ -215,11 +215,9 @@ def compare(label, got, ref, spp):
 
 
 def x86_frame(L, holder, seed, spp, shape):
-    """env_ref.x86_render for a frame whose supersampled size is not its resolution."""
-    import ctypes as C
-    acc = np.zeros(shape, f32)
-    rc = L.ev_render(C.cast(holder.ptr(), C.c_void_p), holder.ext_ptr(), seed, 0, spp, THREADS, 0, acc.ctypes.data_as(C.POINTER(C.c_float)))
-    assert rc == 0, L.ev_error()
+    """env_ref.x86_render (which sizes its frame by the supersampled size) on this module's worker count."""
+    acc = E.x86_render(L, holder, seed, spp, threads=THREADS)
+    assert acc.shape == tuple(shape)
     return acc
 
 
