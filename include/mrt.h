@@ -437,6 +437,19 @@ int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mr
  * op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 pow(a,b), 5 1/a, 6 sqrt(a), 7 a/b.  b may be NULL for unary ops. */
 int mrt_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n);
 
+/* Test hook: closest-hit queries on caller-supplied rays, through the closest-hit code of the context's own path-tracing kernel.
+ * Ray i (origin orig[i], direction dir[i], traced as given: no shift of the origin, no normalisation) is thread i of a launch of
+ * 256-thread workgroups -- lane i % 64 of wavefront i / 64, so the caller composes the wavefronts; threads >= n leave before the
+ * query.  The kernel stages the scene as the context's path-tracing kernel does (LDS, warm, deep or through L2, with its walk
+ * areas) and is the instantiation the context would run at 256 threads (mrt_stats.kernel_features of such a context).
+ * out[i][MRT_TRACE_WORDS]: [0] hit (0 / 1)  [1] the shadow query's answer on the same ray (0 / 1)  [2] renderer and [3] instance
+ * as mrt_aov numbers them (0xffffffff = -1 on a miss)  [4] t0 and [5] t1 as bit patterns  [6..8] the world shading normal at t0 as
+ * bit patterns (the normal plane of mrt_aov); words 4..8 are 0 on a miss.
+ * MRT_ERR_ARG: n == 0, n >= 2^31 or a null pointer; MRT_ERR_STATE: a sharded or multi-device context, or a kernel instantiation
+ * the hook is not built for (the message names it).  Accumulator, booked samples and cached AOVs are not touched. */
+#define MRT_TRACE_WORDS 9u
+int mrt_selftest_trace(mrt_ctx *ctx, size_t n, const float *orig /*[n][3]*/, const float *dir /*[n][3]*/, uint32_t *out /*[n][MRT_TRACE_WORDS]*/);
+
 /* Test hook: compare, on the device, the fast correctly rounded cores of the math contract (sqrt, 1/x, a/b and the
  * 1/sqrt(m) of Vec3f::norm, src/lin.rs:60-66) with the compiler's full IEEE expansions, on `count` inputs generated
  * from the indices first .. first+count-1: op 0 sqrt and op 1 recip take the index as the f32 bit pattern (first = 0,

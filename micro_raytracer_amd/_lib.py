@@ -18,6 +18,7 @@ SYMBOLS = (
     "mrt_execute_adaptive", "mrt_sample_counts", "mrt_adapt_half",
     "mrt_aov", "mrt_denoise", "mrt_img_denoised",
     "mrt_create_ext", "mrt_plan_launch_ext",
+    "mrt_selftest_trace",
 )
 
 
@@ -83,6 +84,7 @@ def lib():
     L.mrt_plan_launch.argtypes = [vp, C.POINTER(_abi.Plan)]
     L.mrt_selftest_math.argtypes = [C.c_int, C.c_int, f32p, f32p, f32p, C.c_size_t]
     L.mrt_selftest_sweep.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, u32, C.POINTER(C.c_uint64), f32p]
+    L.mrt_selftest_trace.argtypes = [vp, C.c_size_t, f32p, f32p, u32p]
     _LIB = L
     return L
 
@@ -127,6 +129,25 @@ def selftest_sweep(op, first, count, seed=1, device=0):
     ex = np.zeros(4, np.float32)
     check(lib().mrt_selftest_sweep(device, op, first, count, seed, C.byref(mis), ex.ctypes.data_as(C.POINTER(C.c_float))))
     return mis.value, ex
+
+
+def selftest_trace(sampler_or_ctx, orig, dir):
+    """mrt_selftest_trace: closest-hit queries on caller-supplied rays through the context's own kernel instantiation.  Ray i is
+    lane i % 64 of wavefront i / 64.  Returns a dict of arrays over the n rays: hit, any (bool), renderer, instance (int32, -1 on
+    a miss), t0, t1 (float32), normal (float32 [n][3]) and words, the raw uint32 [n][TRACE_WORDS] output."""
+    import numpy as np
+    ctx = getattr(sampler_or_ctx, "_ctx", sampler_or_ctx)
+    if ctx is None:
+        raise MrtError(_abi.MRT_ERR_STATE, "selftest_trace: the sampler has no context yet")
+    orig, dir = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
+    if orig.ndim != 2 or orig.shape[1] != 3 or orig.shape != dir.shape:
+        raise ValueError("selftest_trace: orig and dir are [n][3]")
+    n = orig.shape[0]
+    w = np.zeros((n, _abi.TRACE_WORDS), np.uint32)
+    f32p = C.POINTER(C.c_float)
+    check(lib().mrt_selftest_trace(ctx, n, orig.ctypes.data_as(f32p), dir.ctypes.data_as(f32p), w.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return {"hit": w[:, 0] != 0, "any": w[:, 1] != 0, "renderer": w[:, 2].astype(np.int32), "instance": w[:, 3].astype(np.int32),
+            "t0": w[:, 4].view(np.float32), "t1": w[:, 5].view(np.float32), "normal": w[:, 6:9].view(np.float32), "words": w}
 
 
 def save_image(path, rgb8):

@@ -1604,6 +1604,50 @@ int mrt_selftest_math(int device, int op, const float *a, const float *b, float 
     return MRT_OK;
 }
 
+int mrt_selftest_trace(mrt_ctx *c, size_t n, const float *orig, const float *dir, uint32_t *out)
+{
+    if (!c || !orig || !dir || !out) return fail(MRT_ERR_ARG, "mrt_selftest_trace: null argument");
+    if (n == 0 || n >= ((size_t)1 << 31)) return fail(MRT_ERR_ARG, "mrt_selftest_trace: n = %zu", n);
+    if (c->group) return fail(MRT_ERR_STATE, "mrt_selftest_trace: multi-device context");
+    if (c->shard_count > 1) return fail(MRT_ERR_STATE, "mrt_selftest_trace: sharded context");
+    const u32 inst = pt_instantiation(256u, c->scene_in_lds, c->pk.features);
+    if (!rayq_has(c->scene_in_lds, inst))
+        return fail(MRT_ERR_STATE, "mrt_selftest_trace: no ray-query kernel for FEAT %u with the scene in %s", inst, c->scene_in_lds ? "LDS" : "L2");
+    const size_t lds = pt_lds_bytes(c->P, 256u, c->scene_in_lds, c->pk.features);
+    if (lds > kLdsLimit) return fail(MRT_ERR_STATE, "mrt_selftest_trace: FEAT %u needs %zu bytes of LDS at 256 threads", inst, lds);
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    DeviceMem<float> d_o, d_d;
+    DeviceMem<u32> d_out;
+    HIP_TRY(d_o.alloc(n * 3u));
+    HIP_TRY(d_d.alloc(n * 3u));
+    HIP_TRY(d_out.alloc(n * MRT_TRACE_WORDS));
+    HIP_TRY(hipMemcpy(d_o.p, orig, n * 3u * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.p, dir, n * 3u * sizeof(float), hipMemcpyHostToDevice));
+    // the context's own parameter block and blob: staging level, walk areas and the axis scan act as in its renders; the diagnostic
+    // counters of the mesh walks (mrt_trace.h count_fallback) go to a buffer of the call's own: nothing of the context is written
+    DeviceMem<unsigned long long> d_seg;
+    HIP_TRY(d_seg.alloc(8u));
+    HIP_TRY(hipMemset(d_seg.p, 0, 8u * sizeof(unsigned long long)));
+    Params P = c->P;
+    P.count_segments = 0u;
+    P.segments = d_seg.p;
+    P.tile_counter = nullptr; P.accum = nullptr; P.partial = nullptr;
+    HIP_TRY(launch_rayq(P, c->scene_in_lds, inst, lds, (u32)n, d_o.p, d_d.p, d_out.p, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    HIP_TRY(hipMemcpy(out, d_out.p, n * MRT_TRACE_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    // flat instance index -> index within its renderer's inst list (instances are flattened renderer by renderer, mrt_pack.cpp)
+    const Packed &pk = c->pk;
+    std::vector<u32> inst_first(pk.P.n_rend, 0u);
+    for (u32 i = pk.P.n_inst; i-- > 0;) inst_first[pk.blob[pk.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t *q = out + i * MRT_TRACE_WORDS;
+        if (q[0] && q[2] < pk.P.n_rend) q[3] -= inst_first[q[2]];
+    }
+    ok();
+    return MRT_OK;
+}
+
 int mrt_selftest_sweep(int device, int op, uint64_t first, uint64_t count, uint32_t seed, uint64_t *mismatches, float *example)
 {
     if (!mismatches) return fail(MRT_ERR_ARG, "mrt_selftest_sweep: null argument");

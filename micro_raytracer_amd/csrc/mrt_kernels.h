@@ -32,6 +32,10 @@ hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh
                             const float *weight, u32 cap, hipStream_t stream);
 hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count,
                             const float *weight, u32 cap, hipStream_t stream);
+// mrt_rayq.hip: the ray-query test hook (mrt_selftest_trace), instantiation `inst` at 256 threads with `lds` bytes of LDS; n rays,
+// out [n][MRT_TRACE_WORDS].  rayq_has: that instantiation exists
+hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream);
+bool rayq_has(bool scene_in_lds, u32 inst);
 hipError_t launch_math_selftest(int op, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
 hipError_t launch_math_sweep(int op, unsigned long long first, unsigned long long n, u32 seed, unsigned long long *mismatches, float *example, hipStream_t stream);
 

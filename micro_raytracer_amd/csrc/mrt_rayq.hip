@@ -1,0 +1,84 @@
+// mrt_rayq.hip — gfx950 kernel of the ray-query test hook (mrt_selftest_trace).  A translation unit of its own, so
+// that the other kernels are compiled exactly as without it.
+//
+//   rayq   ray i = thread i of a launch of 256-thread workgroups (lane i % 64 of wavefront i / 64): the closest-hit and the
+//          shadow query of trace on a caller-supplied ray, behind the prologue of pt_megakernel (mrt_pt_kernel.h) -- the
+//          scene staged in LDS as the context's path-tracing kernel stages it, the walk areas behind the stash region
+//
+// Build: as mrt_kernels.hip.
+#include <hip/hip_runtime.h>
+
+#include "mrt_kernels.h"
+#include "mrt_megakernel.h"
+#include "mrt_rayq.h"
+
+namespace mrt {
+
+template <bool SCENE_IN_LDS, u32 FEAT>
+__global__ void __launch_bounds__(256) rayq(const Params P, const u32 *__restrict__ blob_g, u32 n, const float *__restrict__ orig,
+                                            const float *__restrict__ dir, u32 *__restrict__ out)
+{
+    constexpr int BLOCK_THREADS = 256;
+    extern __shared__ uint4 lds_blob[];
+    const float *F;
+    const u32 staged_words = !SCENE_IN_LDS ? 0u : staged_words_for(P, FEAT);
+    if (SCENE_IN_LDS) {
+        const uint4 *g = reinterpret_cast<const uint4 *>(P.blob);
+        const u32 n4 = staged_words >> 2;
+        for (u32 i = threadIdx.x; i < n4; i += blockDim.x) lds_blob[i] = g[i];
+        __syncthreads();
+        F = reinterpret_cast<const float *>(lds_blob);
+    } else {
+        F = reinterpret_cast<const float *>(P.blob);
+    }
+    Scn S;
+    S.F = F;
+#ifdef MRT_UNIFORM_SMEM
+    S.U = reinterpret_cast<const float *>(blob_g);
+#else
+    S.U = F;
+#endif
+    S.G = reinterpret_cast<const float *>(blob_g);
+    S.P = &P;
+    // behind the staged scene (16-byte aligned): [lane stash region, unused here] [walk areas: P.walk_cap x blockDim words]
+    const u32 stash_base4 = (staged_words + 3u) >> 2;
+    constexpr bool kStash = lds_stash_for(SCENE_IN_LDS, BLOCK_THREADS, FEAT);
+    S.wk = nullptr; S.wk_stride = BLOCK_THREADS;
+    if constexpr (has_walk_area(FEAT))
+        S.wk = (void *)(reinterpret_cast<float *>(lds_blob + stash_base4) + (kStash ? stash_slots_for(FEAT, BLOCK_THREADS) * BLOCK_THREADS : 0u) + threadIdx.x);
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;                              // (after the staging barrier) as do_tile's !active lanes: not part of any wave vote
+    const V3 o = v3(orig[(size_t)i * 3], orig[(size_t)i * 3 + 1], orig[(size_t)i * 3 + 2]);
+    const V3 d = v3(dir[(size_t)i * 3], dir[(size_t)i * 3 + 1], dir[(size_t)i * 3 + 2]);
+    u32 r[MRT_TRACE_WORDS];
+    rayq_body<FEAT>(S, o, d, r);
+    for (u32 k = 0; k < MRT_TRACE_WORDS; ++k) out[(size_t)i * MRT_TRACE_WORDS + k] = r[k];
+}
+
+// ---- launcher (declared in mrt_kernels.h) ----
+hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream)
+{
+    const dim3 grid((n + 255u) / 256u);
+#define MRT_RQ(L, F) \
+    if (scene_in_lds == (L) && inst == (u32)(F)) { \
+        if (L) { \
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rayq<L, (F)>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            if (e != hipSuccess) return e; \
+        } \
+        hipLaunchKernelGGL((rayq<L, (F)>), grid, dim3(256), lds, stream, P, P.blob, n, orig, dir, out); \
+        return hipGetLastError(); \
+    }
+    MRT_RAYQ_LIST
+#undef MRT_RQ
+    return hipErrorInvalidConfiguration;
+}
+
+bool rayq_has(bool scene_in_lds, u32 inst)
+{
+#define MRT_RQ(L, F) if (scene_in_lds == (L) && inst == (u32)(F)) return true;
+    MRT_RAYQ_LIST
+#undef MRT_RQ
+    return false;
+}
+
+}  // namespace mrt

@@ -960,6 +960,32 @@ void orc_aov(const orc_ctx *c, float *depth, float *normal, float *albedo, int32
     scratch_free(&s);
 }
 
+/* Closest-hit queries on caller-supplied rays (mrt_oracle.h).  The ray is one that Ray::cast has already made: `orig` is the
+ * origin the intersection routines see (src/rt.rs:551-557 shifts it by E along dir; the caller has done that, or wants an origin
+ * exactly on a surface), dir is taken as it is. */
+void orc_ray_query(const orc_ctx *c, size_t n, const float *orig, const float *dir, uint32_t *out)
+{
+    scratch_t s; scratch_init(c, &s);
+    for (size_t k = 0; k < n; k++) {
+        uint32_t *q = out + k * ORC_RAY_WORDS;
+        ray_t ray = ray_cast_default(V3(orig[3 * k], orig[3 * k + 1], orig[3 * k + 2]), V3(dir[3 * k], dir[3 * k + 1], dir[3 * k + 2]));
+        ray.orig = V3(orig[3 * k], orig[3 * k + 1], orig[3 * k + 2]);      /* (pwr, bounce, t of cast_default; the origin as given) */
+        hit_t h0, h1;
+        int any = closest_hit(c, &ray, &s.ids, 0, &h0, &h1) ? 1 : 0;
+        int hit = closest_hit(c, &ray, &s.ids, 1, &h0, &h1);
+        memset(q, 0, sizeof(uint32_t) * ORC_RAY_WORDS);
+        q[1] = (uint32_t)any;
+        q[2] = q[3] = 0xffffffffu;
+        if (!hit) continue;
+        q[0] = 1u;
+        q[2] = (uint32_t)(h0.obj - c->rend);
+        q[3] = (uint32_t)(h0.inst - h0.obj->inst);
+        memcpy(&q[4], &h0.ray.t, 4); memcpy(&q[5], &h1.ray.t, 4);
+        memcpy(&q[6], &h0.norm.x, 4); memcpy(&q[7], &h0.norm.y, 4); memcpy(&q[8], &h0.norm.z, 4);
+    }
+    scratch_free(&s);
+}
+
 /* ------------------------------------------------------------------ Sampler::execute (src/sampler.rs:28-78) */
 typedef struct {
     orc_ctx *c;

@@ -84,6 +84,14 @@ void orc_trace_pixel(const orc_ctx *c, uint32_t x, uint32_t y, uint32_t s, float
  * NULL. */
 void orc_aov(const orc_ctx *c, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance, float *point);
 
+/* n closest-hit queries on caller-supplied rays: RayTracer::closest_hit (src/rt.rs:867-898) on the ray (orig, dir) -- a ray as
+ * Ray::cast leaves it, i.e. orig is the origin the intersection routines see and is not shifted again, dir is not normalised --
+ * and the shadow form of the same query.  out[i][ORC_RAY_WORDS]: [0] hit  [1] the shadow query's Some / None  [2] renderer and
+ * [3] instance as orc_aov numbers them (0xffffffff on a miss)  [4] t0 and [5] t1 of the entry / exit hit as bit patterns  [6..8] the
+ * world shading normal at t0 as orc_aov forms it, as bit patterns; words 4..8 are 0 on a miss. */
+#define ORC_RAY_WORDS 9u
+void orc_ray_query(const orc_ctx *c, size_t n, const float *orig, const float *dir, uint32_t *out);
+
 /* Stand-alone pieces for unit tests */
 void orc_tonemap_px(const float sum[3], uint32_t count, float gamma, float exp, uint8_t out[3]);
 int  orc_lanczos3_resize(const uint8_t *src, uint32_t sw, uint32_t sh, uint8_t *dst, uint32_t dw, uint32_t dh);

@@ -52,6 +52,8 @@ def lib():
     L.orc_img_ss.argtypes = [vp, u8p]
     L.orc_aov.argtypes = [vp, f32p, f32p, f32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), f32p]
     L.orc_aov.restype = None
+    L.orc_ray_query.argtypes = [vp, C.c_size_t, f32p, f32p, u32p]
+    L.orc_ray_query.restype = None
     L.orc_trace_pixel.argtypes = [vp, u32, u32, u32, f32p, u32p]
     L.orc_tonemap_px.argtypes = [f32p, u32, C.c_float, C.c_float, u8p]
     L.orc_lanczos3_resize.argtypes = [u8p, u32, u32, u8p, u32, u32]
@@ -156,6 +158,14 @@ class Oracle:
         ip = C.POINTER(C.c_int32)
         lib().orc_aov(self._c, _fp(out["depth"]), _fp(out["normal"]), _fp(out["albedo"]), out["renderer"].ctypes.data_as(ip),
                       out["instance"].ctypes.data_as(ip), _fp(out["point"]))
+        return out
+
+    def ray_query(self, orig, dir):
+        """orc_ray_query on n rays (traced as given): uint32 [n][9] -- hit, any, renderer, instance, t0 bits, t1 bits, normal bits."""
+        orig, dir = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
+        assert orig.ndim == 2 and orig.shape[1] == 3 and orig.shape == dir.shape
+        out = np.zeros((orig.shape[0], 9), np.uint32)
+        lib().orc_ray_query(self._c, orig.shape[0], _fp(orig), _fp(dir), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def trace_pixel(self, x, y, s):

@@ -368,7 +368,7 @@ def test_denoise_opts_defaults_match_header():
 
 def test_lib_symbols_list_the_new_entry_points():
     from micro_raytracer_amd import _lib
-    for s in ("mrt_aov", "mrt_denoise", "mrt_img_denoised"):
+    for s in ("mrt_aov", "mrt_denoise", "mrt_img_denoised", "mrt_selftest_trace"):
         assert s in _lib.SYMBOLS
         assert s in open(os.path.join(ROOT, "include", "mrt.h")).read()
 
