@@ -434,7 +434,10 @@ mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const
 int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mrt_plan *out);
 
 /* Test hook: run one device math-contract function elementwise on the GPU.
- * op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 pow(a,b), 5 1/a, 6 sqrt(a), 7 a/b.  b may be NULL for unary ops. */
+ * op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 pow(a,b), 5 1/a, 6 sqrt(a), 7 a/b, 12 the first component of norm(a, b, 0.25);
+ * 16 the longitude 0.5 + 0.5 atan2(a, -b) / pi and 17 the latitude acos(clamp(a, -1, 1)) / pi of the texture lookups, 18 / 19 the
+ * two quotients a / (a + b), b / (a + b) over one reciprocal.  Element i is thread i of 256-thread workgroups (lane i % 64 of
+ * wavefront i / 64).  b may be NULL for unary ops. */
 int mrt_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n);
 
 /* Test hook: closest-hit queries on caller-supplied rays, through the closest-hit code of the context's own path-tracing kernel.

@@ -1597,7 +1597,12 @@ int mrt_selftest_math(int device, int op, const float *a, const float *b, float 
     HIP_TRY(dout.alloc(n));
     HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
     if (b) { HIP_TRY(db.alloc(n)); HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice)); }
-    HIP_TRY(launch_math_selftest(op, da.p, db.p, dout.p, n, nullptr));
+    if (op >= 16) {
+        if (op > 19) return fail(MRT_ERR_ARG, "mrt_selftest_math: op %d", op);
+        HIP_TRY(launch_math_selftest_ext(op, da.p, db.p, dout.p, n, nullptr));
+    } else {
+        HIP_TRY(launch_math_selftest(op, da.p, db.p, dout.p, n, nullptr));
+    }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
     ok();

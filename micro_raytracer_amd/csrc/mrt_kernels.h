@@ -37,6 +37,8 @@ hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw
 hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream);
 bool rayq_has(bool scene_in_lds, u32 inst);
 hipError_t launch_math_selftest(int op, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
+// ops 16..19 of mrt_selftest_math, in the test hook's translation unit (mrt_rayq.hip)
+hipError_t launch_math_selftest_ext(int op, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
 hipError_t launch_math_sweep(int op, unsigned long long first, unsigned long long n, u32 seed, unsigned long long *mismatches, float *example, hipStream_t stream);
 
 }  // namespace mrt

@@ -4,6 +4,8 @@
 //   rayq   ray i = thread i of a launch of 256-thread workgroups (lane i % 64 of wavefront i / 64): the closest-hit and the
 //          shadow query of trace on a caller-supplied ray, behind the prologue of pt_megakernel (mrt_pt_kernel.h) -- the
 //          scene staged in LDS as the context's path-tracing kernel stages it, the walk areas behind the stash region
+//   math_selftest_ext   ops 16.. of mrt_selftest_math: the composed expressions of the math contract as their call sites write
+//          them (hit_uv / env_uv's longitude and latitude, the sphere's two roots over one reciprocal), elementwise
 //
 // Build: as mrt_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -55,7 +57,32 @@ __global__ void __launch_bounds__(256) rayq(const Params P, const u32 *__restric
     for (u32 k = 0; k < MRT_TRACE_WORDS; ++k) out[(size_t)i * MRT_TRACE_WORDS + k] = r[k];
 }
 
-// ---- launcher (declared in mrt_kernels.h) ----
+// element i = thread i of 256-thread workgroups, as in math_selftest (mrt_kernels.hip): lane i % 64 of wavefront i / 64, and the
+// lanes behind n leave before any wave vote
+__global__ void __launch_bounds__(256) math_selftest_ext(int op, const float *__restrict__ a, const float *__restrict__ b,
+                                                         float *__restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = a[i], y = b ? b[i] : 0.0f;
+    float q0, q1, r = 0.0f;
+    switch (op) {
+    case 16: r = 0.5f + div_(0.5f * atan2_(x, -y), kPi); break;                   // hit_uv's sphere branch, env_uv: u
+    case 17: r = div_(acos_(fmin_(fmax_(x, -1.0f), 1.0f)), kPi); break;           // env_uv, latlong: v
+    case 18: div2_(x, y, x + y, q0, q1); r = q0; break;
+    case 19: div2_(x, y, x + y, q0, q1); r = q1; break;
+    default: break;
+    }
+    out[i] = r;
+}
+
+// ---- launchers (declared in mrt_kernels.h) ----
+hipError_t launch_math_selftest_ext(int op, const float *a, const float *b, float *out, size_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(math_selftest_ext, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, op, a, b, out, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream)
 {
     const dim3 grid((n + 255u) / 256u);

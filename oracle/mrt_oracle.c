@@ -1386,6 +1386,14 @@ void orc_math(int op, const float *a, const float *b, float *out, size_t n)
         case 9: { float s, c; rt_rand_polar(x, &s, &c); out[i] = c; break; }
         case 10: { float s, c; rt_rand_polar_literal(x, &s, &c); out[i] = s; break; }
         case 11: { float s, c; rt_rand_polar_literal(x, &s, &c); out[i] = c; break; }
+        /* norm of (x, y, 0.25), first component, in lin.rs:60-66's order: self * mag().recip() */
+        case 12: out[i] = x * f_recip(sqrtf((x * x + y * y) + 0.25f * 0.25f)); break;
+        /* the longitude of sphere_uv / env_coord and env_coord's latitude (DESIGN.md sections 4 and 15) on (x, y) = (v.x, v.y)
+         * resp. x = d.z; the sphere's two roots a / c, b / c over c = a + b (src/rt.rs:350-351) */
+        case 16: out[i] = 0.5f + 0.5f * om_atan2f(x, -y) / OM_PI; break;
+        case 17: out[i] = om_acosf(f_min(f_max(x, -1.0f), 1.0f)) / OM_PI; break;
+        case 18: out[i] = x / (x + y); break;
+        case 19: out[i] = y / (x + y); break;
         default: out[i] = 0.0f;
         }
     }

@@ -8,7 +8,8 @@
  * (libm) at src/rt.rs:522,997-1003 and src/sampler.rs:88; libm is not available on the GPU,
  * so the contract pins one concrete f32 result per input that both this oracle and the HIP
  * kernel (micro_raytracer_amd/csrc/mrt_math.h, written independently against DESIGN.md §4)
- * must reproduce bit for bit.  Accuracy is ~1-2 ulp vs libm (tests/test_oracle_math.py).
+ * must reproduce bit for bit.  Accuracy against float64: sin / cos 1.0e-7 absolute, acos 1.5 ulp, atan2 3.25 ulp
+ * (tests/test_math_domains_host.py).
  *
  * Compile with -ffp-contract=off and without -ffast-math.  OM_FMA is fmaf: one rounding, a hardware
  * instruction on every x86-64 since 2013 (-mfma) and on the GPU; the polynomial and argument-reduction steps of
@@ -106,7 +107,8 @@ static inline float om_atan_pos(float t)
     return y0 + OM_FMA(p * z, x, x);
 }
 
-/* atan2(y, x): result in [-pi, pi]; (0,0) -> 0 (sign of zero ignored: +/-0 are the same input) */
+/* atan2(y, x): result in [-pi, pi]; (0,0) -> 0.  The sign of a zero is ignored, +/-0 are the same input: atan2(-0, x < 0) is +pi
+ * where libm has -pi, atan2(+/-0, -0) is 0 where libm has +/-pi (pinned by tests/test_math_domains_host.py) */
 static inline float om_atan2f(float y, float x)
 {
     if (x != x || y != y) return OM_QNAN;

@@ -227,7 +227,7 @@ void emu_math(int op, const float *a, const float *b, float *out, size_t n)
 {
     for (size_t i = 0; i < n; ++i) {
         const float x = a[i], y = b ? b[i] : 0.0f;
-        float s, c, r = 0.0f;
+        float s, c, q0, q1, r = 0.0f;
         switch (op) {
         case 0: sincos_(x, s, c); r = s; break;
         case 1: sincos_(x, s, c); r = c; break;
@@ -242,6 +242,11 @@ void emu_math(int op, const float *a, const float *b, float *out, size_t n)
         case 10: r = u2f((u32)total_key(x)); break;
         case 11: r = u32_to_unit(draw_u32(f2u(x), f2u(y))); break;
         case 12: r = norm(v3(x, y, 0.25f)).x; break;
+        // 16..19: the composed expressions of math_selftest_ext (csrc/mrt_rayq.hip), the same text
+        case 16: r = 0.5f + div_(0.5f * atan2_(x, -y), kPi); break;
+        case 17: r = div_(acos_(fmin_(fmax_(x, -1.0f), 1.0f)), kPi); break;
+        case 18: div2_(x, y, x + y, q0, q1); r = q0; break;
+        case 19: div2_(x, y, x + y, q0, q1); r = q1; break;
         default: break;
         }
         out[i] = r;
