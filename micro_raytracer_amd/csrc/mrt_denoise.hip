@@ -76,8 +76,7 @@ constexpr u32 kDnB = 16, kDnT = kDnB + 4;   // output block, LDS tile with the 2
 hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo, i32 *ids, hipStream_t stream)
 {
     constexpr u32 FN = F_ALL & ~F_TRI;
-    const u32 inst = (features & F_VATTR) ? (F_ALL | F_VATTR | (features & (F_BVH | F_ENV)))       // pt_instantiation of the L2 shape
-                                          : (((features & F_TRI) ? (u32)F_ALL : FN) | (features & F_BVH));
+    const u32 inst = pt_instantiation(256u, false, features);       // the L2 shape
     const dim3 grid((P.nw + 15u) / 16u, (P.nh + 15u) / 16u);
     float4 *g = reinterpret_cast<float4 *>(guide);
     switch (inst) {

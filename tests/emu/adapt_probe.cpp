@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: x86 build of csrc/mrt_adapt.h (the adaptive stop rule), for tests/test_adaptive_host.py.
-// Built by the test itself: g++ -O2 -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math).
+// Built by the test itself through tests/emu/build.py: the flags of tests/emu/Makefile.
 #include <stddef.h>
 
 #include "../../micro_raytracer_amd/csrc/mrt_adapt.h"

@@ -1,22 +1,19 @@
 // TEST INFRASTRUCTURE: x86 build of the closest-hit scan of csrc/mrt_trace.h with its axis body (F_IDENT) -- the
 // packer's classification and AXIS table, single closest-hit queries through either scan body, and the path tracer's
 // render_pixel -- for tests/test_axis_scan.py.  wave_all is the lane's own predicate here, so every ray chooses its body itself.
-// Built by the test itself: g++ -O2 [-mfma] -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math) with mrt_pack.cpp.
+// Built by the test itself through tests/emu/build.py: the flags of tests/emu/Makefile, with mrt_pack.cpp.
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
 #include <string>
-#include <thread>
-#include <vector>
 
 // queries answered by the axis body (CT_AXIS_SCAN of mrt_trace.h), per thread: ax_trace reads it around every query
 static thread_local unsigned long long g_axis_queries = 0;
 #define MRT_COUNT(counter) do { if ((counter) == CT_AXIS_SCAN) ++g_axis_queries; } while (0)
 
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
-#include "../../micro_raytracer_amd/csrc/mrt_trace.h"
+#define LANE_FEAT_LIST LANE_F(F_IDENT)      // the one kernel this probe is about
+#include "lane_host.h"                      // (after the hook above)
 
 using namespace mrt;
 
@@ -24,23 +21,15 @@ static std::string g_err;
 
 namespace {
 
-struct Packing {
-    Packed pk;
-    Params P;
-    Scn S;
-};
+using lane::Packing;
 
 // axis: 0 clears Params.axis_scan, 1 leaves the packer's verdict, -1 follows MRT_AXIS_SCAN as mrt_create does
 int pack(const mrt_render_desc *d, int axis, Packing &k)
 {
-    const int rc = pack_scene(d, k.pk, g_err);
+    const int rc = lane::pack(d, nullptr, PackOpts(), lane::Level(), k, g_err);
     if (rc) return rc;
-    k.P = k.pk.P;
     if (axis < 0) { const char *e = getenv("MRT_AXIS_SCAN"); axis = (e && !atoi(e)) ? 0 : 1; }
     if (!axis) k.P.axis_scan = 0u;
-    k.P.local_rows = k.pk.nh; k.P.shard_index = 0; k.P.shard_count = 1; k.P.shard_rows = 8; k.P.k_split = 1;
-    k.S.F = reinterpret_cast<const float *>(k.pk.blob.data());
-    k.S.U = k.S.F; k.S.G = k.S.F; k.S.P = &k.P; k.S.wk = nullptr; k.S.wk_stride = 1;
     return 0;
 }
 
@@ -93,29 +82,7 @@ int ax_render(const mrt_render_desc *d, int axis, uint64_t seed, uint32_t n_samp
     const int rc = pack(d, axis, k);
     if (rc) return rc;
     if (!plain_ident(k.pk)) { g_err = "not a scene of the plain F_IDENT kernel"; return -100; }
-    k.P.seed_lo = (u32)seed; k.P.seed_hi = (u32)(seed >> 32);
-    k.P.n_samples = n_samples; k.P.sample_base = 0; k.P.accum = accum;
-    std::atomic<uint32_t> next(0);
-    std::atomic<uint64_t> segs(0);
-    if (threads == 0) threads = 1;
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t) pool.emplace_back([&]() {
-        uint64_t local = 0;
-        for (;;) {
-            const uint32_t y = next.fetch_add(1);
-            if (y >= k.pk.nh) break;
-            for (uint32_t x = 0; x < k.pk.nw; ++x) {
-                u32 sg = 0;
-                RegStash st; LaneJob job; job.k = 0; job.word = (y * k.pk.nw + x) * 3u;
-                render_pixel<F_IDENT>(k.S, st, x, y, job, sg);
-                local += sg;
-            }
-        }
-        segs += local;
-    });
-    for (auto &th : pool) th.join();
-    if (segments) *segments = segs.load();
-    return 0;
+    return lane::render_frame(k, F_IDENT, seed, 0, n_samples, 0, k.pk.nh, threads, accum, segments, g_err);
 }
 
 }

@@ -2,13 +2,13 @@
 // (mrt_trace.h, mrt_post.h, mrt_math.h) and the host packer for x86 so that `-m "not gpu"` tests
 // can check the kernel's per-lane logic and the packed scene layout against the CPU oracle
 // without a GPU.  Nothing in the product loads this library; libmrt_hip.so has no CPU path.
+// Packing, the choice of the instantiation and the frame loop are the shared harness's (lane_host.h).
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 
 // walks of the 4-wide triangle-BVH that ran out of walk area and answered through the reference's walk (emu_walk_overflows):
@@ -16,9 +16,8 @@
 static std::atomic<unsigned long long> g_walk_overflows(0);
 #define MRT_COUNT(counter) do { if ((counter) == CT_WALK_OVERFLOW) g_walk_overflows.fetch_add(1, std::memory_order_relaxed); } while (0)
 
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
 #include "../../micro_raytracer_amd/csrc/mrt_post.h"
-#include "../../micro_raytracer_amd/csrc/mrt_trace.h"
+#include "lane_host.h"      // after the hook above: it includes mrt_trace.h
 
 using namespace mrt;
 
@@ -31,30 +30,6 @@ static uint32_t walk_cap()
     const char *v = getenv("MRT_EMU_WALK_CAP");
     const int c = v ? atoi(v) : (int)kWalkCapDefault;
     return c < 4 ? 4u : (c > (int)kWalkCapMax ? kWalkCapMax : (uint32_t)c);
-}
-
-// The F_IDENT form the 256-thread kernels take for this scene (pt_instantiation, mrt_kernels.hip): every instance untransformed
-// and no triangle / map code -- the plain feature set of the scene, or with the instance BVH only its light bit -- or -1
-static int ident_form(const Packed &pk)
-{
-    if (!pk.all_ident) return -1;
-    const u32 need = pk.features & F_ALL;
-    if (pk.features & F_BVH) return (need & (F_BOX | F_TRI | F_MAPS)) ? -1 : (int)((need & F_LIGHTS) | F_BVH | F_IDENT);
-    return (need & (F_TRI | F_MAPS)) ? -1 : (int)(need | F_IDENT);
-}
-
-template <class Stash>
-static void render_ident(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &job, u32 &sg, u32 feat)
-{
-    switch (feat) {
-    case F_IDENT: render_pixel<F_IDENT>(S, st, x, y, job, sg); break;
-    case F_IDENT | F_BOX: render_pixel<F_IDENT | F_BOX>(S, st, x, y, job, sg); break;
-    case F_IDENT | F_LIGHTS: render_pixel<F_IDENT | F_LIGHTS>(S, st, x, y, job, sg); break;
-    case F_IDENT | F_BOX | F_LIGHTS: render_pixel<F_IDENT | F_BOX | F_LIGHTS>(S, st, x, y, job, sg); break;
-    case F_IDENT | F_BVH: render_pixel<F_IDENT | F_BVH>(S, st, x, y, job, sg); break;
-    case F_IDENT | F_LIGHTS | F_BVH: render_pixel<F_IDENT | F_LIGHTS | F_BVH>(S, st, x, y, job, sg); break;
-    default: break;
-    }
 }
 
 extern "C" {
@@ -132,52 +107,13 @@ int emu_features(const mrt_render_desc *d)
 int emu_render_deep(const mrt_render_desc *d, uint64_t seed, uint32_t sample_base, uint32_t n_samples, uint32_t row0, uint32_t row1,
                     uint32_t threads, float *accum, uint64_t *segments, uint32_t deep_nodes)
 {
-    Packed pk;
-    const bool warm_only = deep_nodes == 0xffffffffu;      // F_COLD without F_DEEP: the queued closest-hit walk on the binary table
-    if (warm_only) deep_nodes = 0;
-    PackOpts po;
-    po.tbvh_wide = deep_nodes != 0;
-    const int rc = pack_scene(d, pk, g_err, po);
+    // deep_nodes 0xffffffff: F_COLD without F_DEEP, the queued closest-hit walk on the binary table.  Level 0 runs the F_IDENT
+    // build wherever the 256-thread kernels have one for the scene (lane_inst)
+    lane::Packing k;
+    const lane::Level lv = lane::level_of(deep_nodes, walk_cap());
+    const int rc = lane::pack(d, nullptr, PackOpts(), lv, k, g_err);
     if (rc) return rc;
-    if (deep_nodes && !pk.tbvh_wide) { g_err = "no triangle BVH to widen"; return -100; }
-    Params P = pk.P;
-    P.n_tbvh_hot = deep_nodes;
-    if (deep_nodes) P.walk_cap = walk_cap();
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32);
-    P.n_samples = n_samples; P.sample_base = sample_base; P.k_split = 1; P.accum = accum;
-    if (row1 > pk.nh) row1 = pk.nh;
-    const int ident = deep_nodes || warm_only ? -1 : ident_form(pk);
-    Scn S;
-    S.F = reinterpret_cast<const float *>(pk.blob.data());
-    S.U = S.F; S.G = S.F;
-    S.P = &P;
-    std::atomic<uint32_t> next(row0);
-    std::atomic<uint64_t> segs(0);
-    if (threads == 0) threads = 1;
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t) pool.emplace_back([&]() {
-        uint64_t local = 0;
-        for (;;) {
-            const uint32_t y = next.fetch_add(1);
-            if (y >= row1) break;
-            for (uint32_t x = 0; x < pk.nw; ++x) {
-                u32 sg = 0;
-                {
-                    RegStash st; LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-                    if (warm_only) { if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH | F_COLD>(S, st, x, y, job, sg); else render_pixel<F_ALL | F_COLD>(S, st, x, y, job, sg); }
-                    else if (deep_nodes) { if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH | F_COLD | F_DEEP>(S, st, x, y, job, sg); else render_pixel<F_ALL | F_COLD | F_DEEP>(S, st, x, y, job, sg); }
-                    else if (ident >= 0) render_ident(S, st, x, y, job, sg, (u32)ident);
-                    else if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
-                }
-                local += sg;
-            }
-        }
-        segs += local;
-    });
-    for (auto &th : pool) th.join();
-    if (segments) *segments = segs.load();
-    return 0;
+    return lane::render_frame(k, lane::lane_inst(k.pk, lv.flags, true), seed, sample_base, n_samples, row0, row1, threads, accum, segments, g_err);
 }
 
 int emu_render(const mrt_render_desc *d, uint64_t seed, uint32_t sample_base, uint32_t n_samples, uint32_t row0, uint32_t row1,
@@ -259,27 +195,19 @@ void emu_math(int op, const float *a, const float *b, float *out, size_t n)
 // Returns the number of rays on which the routes differ (ANY queries included), or < 0.
 int emu_mesh_probe(const mrt_render_desc *d, uint32_t n, const float *orig, const float *dir, uint32_t *out, uint32_t *stats /*[2]*/)
 {
-    Packed pk;
-    const int rc = pack_scene(d, pk, g_err);
+    lane::Packing k, kw;
+    const int rc = lane::pack(d, nullptr, PackOpts(), lane::Level(), k, g_err);
     if (rc) return rc;
-    Params P = pk.P;
-    Scn S;
-    S.F = reinterpret_cast<const float *>(pk.blob.data());
-    S.U = S.F; S.G = S.F; S.P = &P;
+    const Params &P = k.P;
+    const Scn &S = k.S;
     if (P.n_inst == 0) return -100;
     int bad = 0;
     uint32_t hits = 0, with_tbvh = 0;
     const float *M = S.F + P.off_mesh;
     with_tbvh = ldu(M, MESH_TBVH) != NO_NODE;
     // the same mesh with the 4-wide table (what the F_DEEP kernels walk): a third route through the same exact tests
-    Packed pkw;
-    PackOpts po; po.tbvh_wide = true;
-    if (pack_scene(d, pkw, g_err, po)) return -101;
-    Params Pw = pkw.P;
-    Pw.n_tbvh_hot = 1; Pw.walk_cap = walk_cap();
-    Scn Sw;
-    Sw.F = reinterpret_cast<const float *>(pkw.blob.data());
-    Sw.U = Sw.F; Sw.G = Sw.F; Sw.P = &Pw;
+    if (lane::pack(d, nullptr, PackOpts(), lane::level_of(1, walk_cap()), kw, g_err)) return -101;
+    const Scn &Sw = kw.S;
     for (uint32_t i = 0; i < n; ++i) {
         const V3 o = v3(orig[i * 3], orig[i * 3 + 1], orig[i * 3 + 2]), dr = v3(dir[i * 3], dir[i * 3 + 1], dir[i * 3 + 2]);
         const RayPre ray = ray_pre<F_ALL>(o, dr);

@@ -1,63 +1,18 @@
 // TEST INFRASTRUCTURE: x86 build of the environment-texture code of csrc/mrt_trace.h -- env_uv alone, the packer
 // with a mrt_env, the first-hit AOV pass, the a-trous filter and the path tracer's render_pixel -- for tests/test_env_host.py and
 // tests/test_gpu_env.py.
-// Built by the tests themselves: g++ -O2 [-mfma] -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math) with mrt_pack.cpp.
+// Built by the tests themselves through tests/emu/build.py: the flags of tests/emu/Makefile, with mrt_pack.cpp.
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
 #include <string>
-#include <thread>
-#include <vector>
 
-#include "../../micro_raytracer_amd/csrc/mrt_denoise.h"
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
+#include "lane_host.h"
 
 using namespace mrt;
 
 static std::string g_err;
-
-namespace {
-
-struct Packing {
-    Packed pk;
-    Params P;
-    Scn S;
-};
-
-int pack(const mrt_render_desc *d, const mrt_desc_ext *ext, Packing &k)
-{
-    const int rc = pack_scene(d, k.pk, g_err, PackOpts(), ext);
-    if (rc) return rc;
-    k.P = k.pk.P;
-    k.P.local_rows = k.pk.nh; k.P.shard_index = 0; k.P.shard_count = 1; k.P.shard_rows = 8; k.P.k_split = 1;
-    k.S.F = reinterpret_cast<const float *>(k.pk.blob.data());
-    k.S.U = k.S.F; k.S.G = k.S.F; k.S.P = &k.P; k.S.wk = nullptr; k.S.wk_stride = 1;
-    return 0;
-}
-
-// the instantiation pt_instantiation picks: the full feature set with F_VATTR | F_ENV for a scene with an environment
-template <u32 X>
-void render_one(const Packing &k, RegStash &st, u32 x, u32 y, const LaneJob &job, u32 &sg)
-{
-    const u32 f = k.pk.features;
-    constexpr u32 E = F_ALL | F_VATTR | F_ENV | X, V = F_ALL | F_VATTR | X, A = F_ALL | X;
-    if (f & F_ENV) { if (f & F_BVH) render_pixel<E | F_BVH>(k.S, st, x, y, job, sg); else render_pixel<E>(k.S, st, x, y, job, sg); }
-    else if (f & F_VATTR) { if (f & F_BVH) render_pixel<V | F_BVH>(k.S, st, x, y, job, sg); else render_pixel<V>(k.S, st, x, y, job, sg); }
-    else { if (f & F_BVH) render_pixel<A | F_BVH>(k.S, st, x, y, job, sg); else render_pixel<A>(k.S, st, x, y, job, sg); }
-}
-
-AovPixel aov_one(const Packing &k, u32 x, u32 y)
-{
-    const u32 f = k.pk.features;
-    constexpr u32 E = F_ALL | F_VATTR | F_ENV, V = F_ALL | F_VATTR, A = F_ALL;
-    if (f & F_ENV) return (f & F_BVH) ? aov_pixel<E | F_BVH>(k.S, x, y) : aov_pixel<E>(k.S, x, y);
-    if (f & F_VATTR) return (f & F_BVH) ? aov_pixel<V | F_BVH>(k.S, x, y) : aov_pixel<V>(k.S, x, y);
-    return (f & F_BVH) ? aov_pixel<A | F_BVH>(k.S, x, y) : aov_pixel<A>(k.S, x, y);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -127,23 +82,10 @@ int ev_sky_init(const mrt_render_desc *d, const mrt_desc_ext *ext, float *out /*
 // NULL, instance[nh][nw]: the index within the renderer's inst list (the flat index less the renderer's first, as mrt_aov maps it)
 int ev_aov_inst(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, float *albedo, int32_t *renderer, int32_t *instance)
 {
-    Packing k;
-    const int rc = pack(d, ext, k);
+    lane::Packing k;
+    const int rc = lane::pack(d, ext, PackOpts(), lane::Level(), k, g_err);
     if (rc) return rc;
-    unsigned long long seg[8] = {0};
-    k.P.segments = seg;
-    std::vector<u32> first(k.P.n_rend, 0u);
-    for (u32 i = k.P.n_inst; i-- > 0;) first[k.pk.blob[k.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
-    for (u32 y = 0; y < k.pk.nh; ++y)
-        for (u32 x = 0; x < k.pk.nw; ++x) {
-            const AovPixel a = aov_one(k, x, y);
-            const size_t p = (size_t)y * k.pk.nw + x;
-            memcpy(guide + 8 * p, &a.g, sizeof(DnGuide));
-            albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
-            renderer[p] = a.rend;
-            if (instance) instance[p] = a.rend < 0 ? -1 : a.inst - (i32)first[(u32)a.rend];
-        }
-    return 0;
+    return lane::aov_frame(k, lane::lane_inst(k.pk, 0u, false), guide, albedo, renderer, instance, g_err);
 }
 
 int ev_aov(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, float *albedo, int32_t *renderer)
@@ -156,51 +98,19 @@ int ev_aov(const mrt_render_desc *d, const mrt_desc_ext *ext, float *guide, floa
 void ev_filter(const float *A, const uint32_t *counts, const float *guide, const float *albedo, uint32_t nw, uint32_t nh, uint32_t passes,
                float sc, float sn, float sp, uint32_t env, float *out)
 {
-    const size_t np = (size_t)nw * nh;
-    const DnGuide *g = reinterpret_cast<const DnGuide *>(guide);
-    std::vector<float> e(np * 3), t(np * 3);
-    for (size_t p = 0; p < np; ++p) {
-        const float rc = 1.0f / (float)counts[p];
-        for (int k = 0; k < 3; ++k) {
-            const float c = A[3 * p + k] * rc;
-            if (passes == 0u) out[3 * p + k] = c;
-            else e[3 * p + k] = c / dn_demod(albedo[3 * p + k], g[p].hit, env != 0u);
-        }
-    }
-    if (passes == 0u) return;
-    for (u32 i = 0; i < passes; ++i) {
-        dn_pass_host(e.data(), g, nw, nh, 1u << i, dn_pass_sc(sc, i), sn, sp, t.data());
-        e.swap(t);
-    }
-    for (size_t p = 0; p < np; ++p)
-        for (int k = 0; k < 3; ++k) out[3 * p + k] = e[3 * p + k] * dn_demod(albedo[3 * p + k], g[p].hit, env != 0u);
+    lane::atrous_host(A, counts, guide, albedo, nw, nh, passes, sc, sn, sp, env != 0u, out);
 }
 
 // the path tracer's per-lane body over the whole frame: accum[nh][nw][3]; warm != 0: the F_COLD lane code
 int ev_render(const mrt_render_desc *d, const mrt_desc_ext *ext, uint64_t seed, uint32_t sample_base, uint32_t n_samples, uint32_t threads,
               uint32_t warm, float *accum)
 {
-    Packing k;
-    const int rc = pack(d, ext, k);
+    lane::Packing k;
+    lane::Level lv;
+    if (warm) lv.flags = F_COLD;
+    const int rc = lane::pack(d, ext, PackOpts(), lv, k, g_err);
     if (rc) return rc;
-    k.P.seed_lo = (u32)seed; k.P.seed_hi = (u32)(seed >> 32);
-    k.P.n_samples = n_samples; k.P.sample_base = sample_base; k.P.accum = accum;
-    std::atomic<uint32_t> next(0);
-    if (threads == 0) threads = 1;
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t) pool.emplace_back([&]() {
-        for (;;) {
-            const uint32_t y = next.fetch_add(1);
-            if (y >= k.pk.nh) break;
-            for (uint32_t x = 0; x < k.pk.nw; ++x) {
-                u32 sg = 0;
-                RegStash st; LaneJob job; job.k = 0; job.word = (y * k.pk.nw + x) * 3u;
-                if (warm) render_one<F_COLD>(k, st, x, y, job, sg); else render_one<0u>(k, st, x, y, job, sg);
-            }
-        }
-    });
-    for (auto &th : pool) th.join();
-    return 0;
+    return lane::render_frame(k, lane::lane_inst(k.pk, lv.flags, false), seed, sample_base, n_samples, 0, k.pk.nh, threads, accum, nullptr, g_err);
 }
 
 }

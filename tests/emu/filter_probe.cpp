@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE: x86 build of the bilinear texture filter of csrc/mrt_trace.h -- tex_bilinear alone, the
 // material lookup tex_fetch_bilinear and the environment's env_color on a hand-made blob -- for tests/test_filter_host.py.  (The
 // packer, the AOV pass and render_pixel with the filter switches go through tests/emu/env_probe.cpp, which takes any ext.)
-// Built by the test itself: g++ -O2 [-mfma] -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math).
+// Built by the test itself through tests/emu/build.py: the flags of tests/emu/Makefile.
 #include <stddef.h>
 #include <string.h>
 

@@ -25,20 +25,17 @@ static thread_local std::vector<uint32_t> *g_work_r = nullptr, *g_work_any_r = n
         if ((counter) == 2 || (counter) == 6) w_->back() += 1; else if ((counter) == 1 || (counter) == 7) w_->back() += 3; \
         if (g_work_r && g_right && ((counter) == 6 || (counter) == 7)) { std::vector<uint32_t> *r_ = g_in_any ? g_work_any_r : g_work_r; r_->back() += ((counter) == 6 ? 1 : 3); } } } while (0)
 
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
-#include "../../micro_raytracer_amd/csrc/mrt_trace.h"
+#define LANE_FEAT_LIST LANE_F(F_ALL) LANE_F(F_ALL | F_BVH) LANE_F(F_ALL | F_COLD | F_DEEP) LANE_F(F_ALL | F_BVH | F_COLD | F_DEEP)
+#include "lane_host.h"      // (after the hooks above)
 using namespace mrt;
 
 extern "C" int probe_divergence(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tile_x0, uint32_t tile_y0,
                                 uint32_t tiles_x, uint32_t tiles_y, double *active /*[PH_COUNT]*/, double *executed /*[PH_COUNT]*/)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.n_samples = n_samples; P.sample_base = 0; P.k_split = 1;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    const u32 inst = lane::lane_inst(pk, 0u, false);
     for (u32 p = 0; p < PH_COUNT; ++p) { active[p] = 0; executed[p] = 0; }
     for (uint32_t ty = tile_y0; ty < tile_y0 + tiles_y; ++ty)
         for (uint32_t tx = tile_x0; tx < tile_x0 + tiles_x; ++tx) {
@@ -48,9 +45,8 @@ extern "C" int probe_divergence(const mrt_render_desc *d, uint64_t seed, uint32_
                 const uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
                 if (x >= pk.nw || y >= pk.nh) continue;
                 g_rec = &rec[l];
-                u32 sg = 0; RegStash st;
-                LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-                if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
+                uint64_t sg = 0;
+                lane::render_lane(k, inst, x, y, sg);
                 g_rec = nullptr;
                 if (rec[l].size() > max_it) max_it = rec[l].size();
             }
@@ -67,26 +63,18 @@ extern "C" int probe_divergence(const mrt_render_desc *d, uint64_t seed, uint32_
 // work counters (CT_* of mrt_trace.h) summed over every pixel of the frame, n_samples each
 extern "C" int probe_counts(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint64_t *counts /*[CT_COUNT]*/, uint64_t *segments)
 {
-    Packed pk; std::string err;
+    lane::Packing k; std::string err;
     const bool deep = getenv("MRT_EMU_DEEP") != nullptr;           // the 4-wide walk of the F_DEEP kernels (one staged node)
-    PackOpts po; po.tbvh_wide = deep;
-    if (pack_scene(d, pk, err, po)) return -1;
-    Params P = pk.P;
-    if (deep) P.n_tbvh_hot = 1;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.n_samples = n_samples; P.sample_base = 0; P.k_split = 1;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
-    if (const char *v = getenv("MRT_EMU_WALK_CAP")) { const int c = atoi(v); if (c >= 4 && c <= (int)kWalkCapMax) P.walk_cap = (u32)c; }
+    const lane::Level lv = lane::level_of(deep ? 1u : 0u, 0u);
+    if (lane::pack_scratch(d, lv, seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    if (const char *v = getenv("MRT_EMU_WALK_CAP")) { const int c = atoi(v); if (c >= 4 && c <= (int)kWalkCapMax) k.P.walk_cap = (u32)c; }
+    const u32 inst = lane::lane_inst(pk, lv.flags, false);
     memset(g_cnt, 0, sizeof g_cnt);
     uint64_t seg = 0;
     for (uint32_t y = 0; y < pk.nh; ++y)
         for (uint32_t x = 0; x < pk.nw; ++x) {
-            u32 sg = 0; RegStash st;
-            LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-            if (deep) { if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH | F_COLD | F_DEEP>(S, st, x, y, job, sg); else render_pixel<F_ALL | F_COLD | F_DEEP>(S, st, x, y, job, sg); }
-            else if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
-            seg += sg;
+            lane::render_lane(k, inst, x, y, seg);
         }
     for (u32 c = 0; c < CT_COUNT; ++c) counts[c] = g_cnt[c];
     if (segments) *segments = seg;
@@ -98,13 +86,10 @@ extern "C" int probe_counts(const mrt_render_desc *d, uint64_t seed, uint32_t n_
 extern "C" double probe_traversal_efficiency(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tile_x0, uint32_t tile_y0,
                                              uint32_t tiles_x, uint32_t tiles_y, double *mean_work, double *max_work)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.n_samples = n_samples; P.sample_base = 0; P.k_split = 1;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    const u32 inst = lane::lane_inst(pk, 0u, false);
     double sum_mean = 0, sum_max = 0;
     for (uint32_t ty = tile_y0; ty < tile_y0 + tiles_y; ++ty)
         for (uint32_t tx = tile_x0; tx < tile_x0 + tiles_x; ++tx) {
@@ -114,9 +99,8 @@ extern "C" double probe_traversal_efficiency(const mrt_render_desc *d, uint64_t 
                 const uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
                 if (x >= pk.nw || y >= pk.nh) continue;
                 g_work = &w[l];
-                u32 sg = 0; RegStash st;
-                LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-                if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
+                uint64_t sg = 0;
+                lane::render_lane(k, inst, x, y, sg);
                 g_work = nullptr;
                 if (w[l].size() > max_it) max_it = w[l].size();
             }
@@ -136,22 +120,18 @@ extern "C" double probe_traversal_efficiency(const mrt_render_desc *d, uint64_t 
 extern "C" int probe_tile_work(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tx, uint32_t ty, uint32_t cap,
                                uint32_t *out /*[64][cap]*/, uint32_t *out_any /*[64][cap]*/, uint32_t *n_it /*[64]*/)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.n_samples = n_samples; P.sample_base = 0; P.k_split = 1;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    const u32 inst = lane::lane_inst(pk, 0u, false);
     for (int l = 0; l < 64; ++l) {
         n_it[l] = 0;
         const uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
         if (x >= pk.nw || y >= pk.nh) continue;
         std::vector<uint32_t> w, wa;
         g_work = &w; g_work_any = &wa;
-        u32 sg = 0; RegStash st;
-        LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-        if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
+        uint64_t sg = 0;
+        lane::render_lane(k, inst, x, y, sg);
         g_work = nullptr; g_work_any = nullptr;
         const size_t n = w.size() < cap ? w.size() : cap;
         for (size_t k = 0; k < n; ++k) { out[(size_t)l * cap + k] = w[k]; out_any[(size_t)l * cap + k] = wa[k]; }
@@ -164,22 +144,18 @@ extern "C" int probe_tile_work(const mrt_render_desc *d, uint64_t seed, uint32_t
 extern "C" int probe_tile_work_split(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tx, uint32_t ty, uint32_t cap,
                                      uint32_t *out, uint32_t *out_any, uint32_t *out_r, uint32_t *out_any_r, uint32_t *n_it)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.n_samples = n_samples; P.sample_base = 0; P.k_split = 1;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    const u32 inst = lane::lane_inst(pk, 0u, false);
     for (int l = 0; l < 64; ++l) {
         n_it[l] = 0;
         const uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
         if (x >= pk.nw || y >= pk.nh) continue;
         std::vector<uint32_t> w, wa, wr, war;
         g_work = &w; g_work_any = &wa; g_work_r = &wr; g_work_any_r = &war;
-        u32 sg = 0; RegStash st;
-        LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-        if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
+        uint64_t sg = 0;
+        lane::render_lane(k, inst, x, y, sg);
         g_work = nullptr; g_work_any = nullptr; g_work_r = nullptr; g_work_any_r = nullptr;
         const size_t n = w.size() < cap ? w.size() : cap;
         for (size_t k = 0; k < n; ++k) { out[(size_t)l * cap + k] = w[k]; out_any[(size_t)l * cap + k] = wa[k]; out_r[(size_t)l * cap + k] = wr[k]; out_any_r[(size_t)l * cap + k] = war[k]; }

@@ -11,8 +11,7 @@ static thread_local bool g_shadow = false;
 #define MRT_PROBE_INST(i) (g_inst = (i))
 #define MRT_PROBE(phase) do { if (g_mask) { if ((phase) == 0) g_mask->push_back(0); else if ((phase) == 2 && !g_mask->empty() && g_inst < 32) g_mask->back() |= 1u << g_inst; } } while (0)
 
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
-#include "../../micro_raytracer_amd/csrc/mrt_trace.h"
+#include "lane_host.h"      // (after the hooks above)
 using namespace mrt;
 
 // out[0] = wave iterations, out[1] = masked sphere passes paid today, out[2] = passes of the compacted schedule,
@@ -20,13 +19,10 @@ using namespace mrt;
 extern "C" int probe_sphere_math(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tile_x0, uint32_t tile_y0,
                                  uint32_t tiles_x, uint32_t tiles_y, double *out)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.n_samples = n_samples; P.sample_base = 0; P.k_split = 1;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    const Scn &S = k.S;
     for (int i = 0; i < 5; ++i) out[i] = 0;
     for (uint32_t ty = tile_y0; ty < tile_y0 + tiles_y; ++ty)
         for (uint32_t tx = tile_x0; tx < tile_x0 + tiles_x; ++tx) {

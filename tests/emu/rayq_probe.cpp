@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE: x86 build of the ray-query body of csrc/mrt_rayq.h -- the per-ray text of the device hook
 // mrt_selftest_trace -- on a scene packed by pack_scene (with or without mrt_desc_ext), for tests/test_ray_query_host.py and
 // tests/test_gpu_ray_query.py.  wave_all is the lane's own predicate here, so every ray chooses its bodies itself.
-// Built by the tests themselves: g++ -O2 [-mfma] -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math) with mrt_pack.cpp.
+// Built by the tests themselves through tests/emu/build.py: the flags of tests/emu/Makefile, with mrt_pack.cpp.
 #include <stdint.h>
 #include <string.h>
 
@@ -11,8 +11,8 @@
 static thread_local unsigned long long g_axis_queries = 0;
 #define MRT_COUNT(counter) do { if ((counter) == CT_AXIS_SCAN) ++g_axis_queries; } while (0)
 
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
 #include "../../micro_raytracer_amd/csrc/mrt_rayq.h"
+#include "lane_host.h"      // (after the hook above)
 
 using namespace mrt;
 
@@ -45,27 +45,24 @@ int rq_pack(const mrt_render_desc *d, const mrt_desc_ext *ext, uint32_t wide, ui
 int rq_trace(const mrt_render_desc *d, const mrt_desc_ext *ext, const uint32_t *cfg, uint32_t n, const float *orig, const float *dir, uint32_t *out,
              uint32_t *inst_first)
 {
-    Packed pk;
+    lane::Packing k;
     PackOpts po; po.tbvh_wide = cfg[RQ_WIDE] != 0u;
-    const int rc = pack_scene(d, pk, g_err, po, ext);
+    const int rc = lane::pack(d, ext, po, lane::Level(), k, g_err);
     if (rc) return rc;
-    if (po.tbvh_wide && !pk.tbvh_wide) { g_err = "no triangle BVH to widen"; return -100; }
+    const Packed &pk = k.pk;
+    Params &P = k.P;
+    const Scn &S = k.S;
     const u32 feat = cfg[RQ_FEAT];
     if (((feat & F_DEEP) != 0u) != pk.tbvh_wide) { g_err = "F_DEEP goes with the 4-wide table and with nothing else"; return -101; }
     if (((feat & F_BVH) != 0u) != ((pk.features & F_BVH) != 0u)) { g_err = "F_BVH does not match the packed scene"; return -102; }
     if ((feat & F_IDENT) && !pk.all_ident) { g_err = "F_IDENT on a scene with a transformed instance"; return -103; }
     if ((pk.features & F_ALL & ~feat) != 0u) { g_err = "FEAT does not cover the scene"; return -104; }
     if (((pk.features & F_VATTR) != 0u) != ((feat & F_VATTR) != 0u)) { g_err = "F_VATTR does not match the packed scene"; return -105; }
-    Params P = pk.P;
     if (cfg[RQ_AXIS] == 0u) P.axis_scan = 0u;
     if (cfg[RQ_AXIS] == 2u) P.axis_scan = 1u;
     P.n_tbvh_hot = cfg[RQ_HOT];
     P.walk_cap = cfg[RQ_WALK_CAP] ? cfg[RQ_WALK_CAP] : kLeafQueue;
     if (P.walk_cap > kWalkCapMax || P.walk_cap < 4u) { g_err = "walk_cap"; return -106; }
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8; P.k_split = 1;
-    Scn S;
-    S.F = reinterpret_cast<const float *>(pk.blob.data());
-    S.U = S.F; S.G = S.F; S.P = &P; S.wk = nullptr; S.wk_stride = 1;
     const bool ref_walk = cfg[RQ_REF_WALK] != 0u;
     if (inst_first) {
         for (u32 r = 0; r < P.n_rend; ++r) inst_first[r] = 0u;

@@ -12,8 +12,7 @@ static thread_local std::vector<std::vector<Call>> *g_iters = nullptr;     // [i
 #define MRT_PROBE(phase) do { if (g_iters && (phase) == 0) g_iters->push_back(std::vector<Call>()); } while (0)
 #define MRT_COUNT(counter) do { if (g_iters && !g_iters->empty() && (counter) == 4) g_iters->back().push_back(Call()); } while (0)
 #define MRT_PROBE_ROUND(steps, tris, membs) do { if (g_iters && !g_iters->empty() && !g_iters->back().empty()) g_iters->back().back().rounds.push_back(Rd{(uint16_t)(steps), (uint16_t)(tris)}); } while (0)
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
-#include "../../micro_raytracer_amd/csrc/mrt_trace.h"
+#include "lane_host.h"      // (after the hooks above)
 using namespace mrt;
 #ifndef ROUND_FEAT                  // -DROUND_FEAT="(F_ALL | F_COLD)": the warm mesh kernel (every closest-hit leaf queued)
 #define ROUND_FEAT F_ALL
@@ -23,13 +22,10 @@ using namespace mrt;
 //      [6] mesh_isect call slots executed by the wave, [7] lane-calls / 64
 extern "C" int probe_rounds(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tx, uint32_t ty, double *out)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.k_split = 1; P.sample_base = 0; P.n_samples = n_samples;
-    std::vector<float> frame((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    Scn S; S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
+    const Packed &pk = k.pk;
+    const Scn &S = k.S;
     std::vector<std::vector<std::vector<Call>>> rec(64);
     size_t mx = 0;
     for (int l = 0; l < 64; ++l) {

@@ -17,39 +17,29 @@ static thread_local bool g_in_any = false;
     if (g_work && !g_work->empty()) { std::vector<uint32_t> *w_ = g_in_any ? g_any : g_work; \
         if ((counter) == 2 || (counter) == 6 || (counter) == 9) w_->back() += 1; else if ((counter) == 1 || (counter) == 7) w_->back() += 3; } } while (0)
 #define MRT_PROBE_TBVH_PART(node, right0) do { if (g_rec && !g_rec->empty()) (g_in_any ? g_rec->back().s : g_rec->back().c).push_back(node); } while (0)
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
-#include "../../micro_raytracer_amd/csrc/mrt_trace.h"
+#define LANE_FEAT_LIST LANE_F(F_ALL) LANE_F(F_ALL | F_BVH)
+#include "lane_host.h"      // (after the hooks above)
 using namespace mrt;
 
-static void setup(const Packed &pk, Params &P, std::vector<float> &frame, Scn &S, uint64_t seed)
+static void run(const lane::Packing &k, uint32_t x, uint32_t y)
 {
-    P = pk.P;
-    P.local_rows = pk.nh; P.shard_index = 0; P.shard_count = 1; P.shard_rows = 8;
-    P.seed_lo = (u32)seed; P.seed_hi = (u32)(seed >> 32); P.k_split = 1;
-    frame.assign((size_t)pk.nw * pk.nh * 3, 0.0f); P.accum = frame.data();
-    S.F = reinterpret_cast<const float *>(pk.blob.data()); S.U = S.F; S.G = S.F; S.P = &P;
-}
-static void run(const Packed &pk, const Scn &S, uint32_t x, uint32_t y)
-{
-    u32 sg = 0; RegStash st; LaneJob job; job.k = 0; job.word = (y * pk.nw + x) * 3u;
-    if (pk.features & F_BVH) render_pixel<F_ALL | F_BVH>(S, st, x, y, job, sg); else render_pixel<F_ALL>(S, st, x, y, job, sg);
+    uint64_t sg = 0;
+    lane::render_lane(k, lane::lane_inst(k.pk, 0u, false), x, y, sg);
 }
 
 // out[((y - y0) * w + (x - x0)) * n_samples + s][k] = closest work | shadow work << 16 of segment k; n_it likewise
 extern "C" int probe_paths(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t cap,
                            uint32_t *out, uint32_t *n_it)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P; std::vector<float> frame; Scn S;
-    setup(pk, P, frame, S, seed);
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, 1, k, err)) return -1;
     size_t idx = 0;
     for (uint32_t y = y0; y < y0 + h; ++y) for (uint32_t x = x0; x < x0 + w; ++x)
         for (uint32_t s = 0; s < n_samples; ++s, ++idx) {
             std::vector<uint32_t> wk, wa;
             g_work = &wk; g_any = &wa;
-            P.sample_base = s; P.n_samples = 1;
-            run(pk, S, x, y);
+            k.P.sample_base = s;
+            run(k, x, y);
             g_work = nullptr; g_any = nullptr;
             const size_t n = wk.size() < cap ? wk.size() : cap;
             for (size_t k = 0; k < n; ++k) out[idx * cap + k] = (wk[k] & 0xffff) | (wa[k] << 16);
@@ -62,16 +52,13 @@ extern "C" int probe_paths(const mrt_render_desc *d, uint64_t seed, uint32_t n_s
 //      [5] sum of mean (closest), [6] mean (shadow)
 extern "C" int probe_union(const mrt_render_desc *d, uint64_t seed, uint32_t n_samples, uint32_t tx, uint32_t ty, double *out)
 {
-    Packed pk; std::string err;
-    if (pack_scene(d, pk, err)) return -1;
-    Params P; std::vector<float> frame; Scn S;
-    setup(pk, P, frame, S, seed);
-    P.sample_base = 0; P.n_samples = n_samples;
+    lane::Packing k; std::string err;
+    if (lane::pack_scratch(d, lane::Level(), seed, 0, n_samples, k, err)) return -1;
     std::vector<std::vector<It>> rec(64);
     size_t mx = 0;
     for (int l = 0; l < 64; ++l) {
         g_rec = &rec[l];
-        run(pk, S, tx * 8 + (l & 7), ty * 8 + (l >> 3));
+        run(k, tx * 8 + (l & 7), ty * 8 + (l >> 3));
         g_rec = nullptr;
         if (rec[l].size() > mx) mx = rec[l].size();
     }

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: x86 build of csrc/mrt_denoise_var.h (the variance-guided denoiser mode), for
 // tests/test_denoise_var_host.py and tests/test_gpu_denoise_var.py.
-// Built by the tests themselves: g++ -O2 [-mfma] -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math).
+// Built by the tests themselves through tests/emu/build.py: the flags of tests/emu/Makefile.
 #include <stddef.h>
 #include <stdint.h>
 

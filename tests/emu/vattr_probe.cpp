@@ -1,72 +1,18 @@
 // TEST INFRASTRUCTURE: x86 build of the per-corner attribute code of csrc/mrt_trace.h -- the interpolation
 // functions alone, the first-hit AOV pass and the path tracer's render_pixel on scenes packed with a mrt_desc_ext -- for
 // tests/test_vattr_host.py and tests/test_gpu_vattr.py.
-// Built by the tests themselves: g++ -O2 [-mfma] -std=c++17 -ffp-contract=off -shared -fPIC (no fast-math) with mrt_pack.cpp.
+// Built by the tests themselves through tests/emu/build.py: the flags of tests/emu/Makefile, with mrt_pack.cpp.
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
 #include <string>
-#include <thread>
-#include <vector>
 
-#include "../../micro_raytracer_amd/csrc/mrt_denoise.h"
-#include "../../micro_raytracer_amd/csrc/mrt_pack.h"
+#include "lane_host.h"
 
 using namespace mrt;
 
 static std::string g_err;
-
-namespace {
-
-// deep: 0 = binary triangle BVHs (F_ALL), 0xffffffff = the warm lane code on them (F_COLD), n = 4-wide tables of which the
-// first n nodes count as staged (F_COLD | F_DEEP), as tests/emu/emu.cpp emu_render_deep
-struct Packing {
-    Packed pk;
-    Params P;
-    Scn S;
-    bool warm = false, deep = false;
-};
-
-int pack(const mrt_render_desc *d, const mrt_desc_ext *ext, uint32_t deep_nodes, Packing &k)
-{
-    k.warm = deep_nodes == 0xffffffffu;
-    k.deep = deep_nodes != 0u && !k.warm;
-    PackOpts po;
-    po.tbvh_wide = k.deep;
-    const int rc = pack_scene(d, k.pk, g_err, po, ext);
-    if (rc) return rc;
-    if (k.deep && !k.pk.tbvh_wide) { g_err = "no triangle BVH to widen"; return -100; }
-    k.P = k.pk.P;
-    if (k.deep) { k.P.n_tbvh_hot = deep_nodes; k.P.walk_cap = kWalkCapDefault; }
-    k.P.local_rows = k.pk.nh; k.P.shard_index = 0; k.P.shard_count = 1; k.P.shard_rows = 8; k.P.k_split = 1;
-    k.S.F = reinterpret_cast<const float *>(k.pk.blob.data());
-    k.S.U = k.S.F; k.S.G = k.S.F; k.S.P = &k.P; k.S.wk = nullptr; k.S.wk_stride = 1;
-    return 0;
-}
-
-// the instantiation pt_instantiation picks for a scene with attributes (always the full feature set) / without
-template <u32 X>
-void render_one(const Packing &k, RegStash &st, u32 x, u32 y, const LaneJob &job, u32 &sg)
-{
-    const u32 f = k.pk.features;
-    if (f & F_VATTR) {
-        if (f & F_BVH) render_pixel<F_ALL | F_BVH | F_VATTR | X>(k.S, st, x, y, job, sg); else render_pixel<F_ALL | F_VATTR | X>(k.S, st, x, y, job, sg);
-    } else {
-        if (f & F_BVH) render_pixel<F_ALL | F_BVH | X>(k.S, st, x, y, job, sg); else render_pixel<F_ALL | X>(k.S, st, x, y, job, sg);
-    }
-}
-
-template <u32 X>
-AovPixel aov_one(const Packing &k, u32 x, u32 y)
-{
-    const u32 f = k.pk.features;
-    if (f & F_VATTR) return (f & F_BVH) ? aov_pixel<F_ALL | F_BVH | F_VATTR | X>(k.S, x, y) : aov_pixel<F_ALL | F_VATTR | X>(k.S, x, y);
-    return (f & F_BVH) ? aov_pixel<F_ALL | F_BVH | X>(k.S, x, y) : aov_pixel<F_ALL | X>(k.S, x, y);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -109,51 +55,26 @@ int va_pack(const mrt_render_desc *d, const mrt_desc_ext *ext, uint32_t *blob, u
 }
 
 // mrt_aov of a scene with attributes: guide[nh][nw][8] (normal, depth, world point, hit flag), albedo[nh][nw][3], renderer[nh][nw]
+// deep_nodes: 0 = binary triangle BVHs (F_ALL), 0xffffffff = the warm lane code on them (F_COLD), n = 4-wide tables of which the
+// first n nodes count as staged (F_COLD | F_DEEP), as tests/emu/emu.cpp emu_render_deep
 int va_aov(const mrt_render_desc *d, const mrt_desc_ext *ext, uint32_t deep_nodes, float *guide, float *albedo, int32_t *renderer)
 {
-    Packing k;
-    const int rc = pack(d, ext, deep_nodes, k);
+    lane::Packing k;
+    const lane::Level lv = lane::level_of(deep_nodes);
+    const int rc = lane::pack(d, ext, PackOpts(), lv, k, g_err);
     if (rc) return rc;
-    unsigned long long seg[8] = {0};
-    k.P.segments = seg;
-    for (u32 y = 0; y < k.pk.nh; ++y)
-        for (u32 x = 0; x < k.pk.nw; ++x) {
-            const AovPixel a = k.deep ? aov_one<F_COLD | F_DEEP>(k, x, y) : (k.warm ? aov_one<F_COLD>(k, x, y) : aov_one<0u>(k, x, y));
-            const size_t p = (size_t)y * k.pk.nw + x;
-            memcpy(guide + 8 * p, &a.g, sizeof(DnGuide));
-            albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
-            renderer[p] = a.rend;
-        }
-    return 0;
+    return lane::aov_frame(k, lane::lane_inst(k.pk, lv.flags, false), guide, albedo, renderer, nullptr, g_err);
 }
 
 // the path tracer's per-lane body over the whole frame (tests/emu/emu.cpp emu_render_deep with attributes): accum[nh][nw][3]
 int va_render(const mrt_render_desc *d, const mrt_desc_ext *ext, uint64_t seed, uint32_t sample_base, uint32_t n_samples, uint32_t threads,
               uint32_t deep_nodes, float *accum)
 {
-    Packing k;
-    const int rc = pack(d, ext, deep_nodes, k);
+    lane::Packing k;
+    const lane::Level lv = lane::level_of(deep_nodes);
+    const int rc = lane::pack(d, ext, PackOpts(), lv, k, g_err);
     if (rc) return rc;
-    k.P.seed_lo = (u32)seed; k.P.seed_hi = (u32)(seed >> 32);
-    k.P.n_samples = n_samples; k.P.sample_base = sample_base; k.P.accum = accum;
-    std::atomic<uint32_t> next(0);
-    if (threads == 0) threads = 1;
-    std::vector<std::thread> pool;
-    for (uint32_t t = 0; t < threads; ++t) pool.emplace_back([&]() {
-        for (;;) {
-            const uint32_t y = next.fetch_add(1);
-            if (y >= k.pk.nh) break;
-            for (uint32_t x = 0; x < k.pk.nw; ++x) {
-                u32 sg = 0;
-                RegStash st; LaneJob job; job.k = 0; job.word = (y * k.pk.nw + x) * 3u;
-                if (k.deep) render_one<F_COLD | F_DEEP>(k, st, x, y, job, sg);
-                else if (k.warm) render_one<F_COLD>(k, st, x, y, job, sg);
-                else render_one<0u>(k, st, x, y, job, sg);
-            }
-        }
-    });
-    for (auto &th : pool) th.join();
-    return 0;
+    return lane::render_frame(k, lane::lane_inst(k.pk, lv.flags, false), seed, sample_base, n_samples, 0, k.pk.nh, threads, accum, nullptr, g_err);
 }
 
 }

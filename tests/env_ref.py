@@ -3,14 +3,12 @@
 kernels (the mapping, the texture's mean, the closed-form render of a mirror sphere under an environment), scene builders and
 a Radiance RGBE encoder."""
 import ctypes as C
-import os
 import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import ROOT, make_holder
+from conftest import make_holder
+from emu.build import probe_or_skip
 from vattr_ref import camera_rays, same_bits
 
 f32 = np.float32
@@ -20,21 +18,7 @@ MAPPINGS = ("sphere", "latlong")
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
 def build_probe(out_dir):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = os.path.join(str(out_dir), "libenv_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]      # as tests/emu/Makefile
-    except OSError:
-        pass
-    cs = os.path.join(ROOT, "micro_raytracer_amd", "csrc")
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-pthread", "-o", out, os.path.join(ROOT, "tests", "emu", "env_probe.cpp"),
-                           os.path.join(cs, "mrt_pack.cpp"), "-lpthread"])
-    L = C.CDLL(out)
+    L = probe_or_skip("env_probe", out_dir)
     fp, u32p, i32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32
     L.ev_error.restype = C.c_char_p
     L.ev_uv.argtypes = [u32, u32, C.c_float, u32, u32, fp, fp, u32p]

@@ -5,15 +5,12 @@ under a point light) and scene builders.  Packing, AOVs and whole renders with t
 tests/env_ref.py, whose entry points take any mrt_desc_ext."""
 import copy
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
 import env_ref as E
-from conftest import ROOT, make_holder
+from conftest import make_holder
+from emu.build import probe_or_skip
 from vattr_ref import camera_rays
 
 f32 = np.float32
@@ -24,19 +21,7 @@ BILINEAR_MAX = f32(2.0 ** 30)
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
 def build_probe(out_dir):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = os.path.join(str(out_dir), "libfilter_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]      # as tests/emu/Makefile
-    except OSError:
-        pass
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-o", out, os.path.join(ROOT, "tests", "emu", "filter_probe.cpp")])
-    L = C.CDLL(out)
+    L = probe_or_skip("filter_probe", out_dir, with_pack=False)
     fp, vp, u32 = C.POINTER(C.c_float), C.c_void_p, C.c_uint32
     L.fl_core.argtypes = [u32, u32, u32, vp, u32, u32, fp, fp]
     L.fl_core.restype = None

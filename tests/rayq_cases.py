@@ -363,27 +363,13 @@ def attributes(oracle_mod=None):
 
 # ---- running a case: the x86 probe, the oracle, the comparison rules ---------------------------------------------------------------
 def build_probe(out_dir):
-    """g++ build of tests/emu/rayq_probe.cpp (the flags of tests/emu/Makefile), loaded with ctypes."""
+    """tests/emu/rayq_probe.cpp, loaded with ctypes; None where there is no g++."""
     import ctypes as C
-    import os
-    import shutil
-    import subprocess
 
-    from conftest import ROOT
-    cxx = shutil.which("g++")
-    if cxx is None:
+    from emu.build import build_probe as build
+    L = build("rayq_probe", out_dir)
+    if L is None:
         return None
-    out = os.path.join(str(out_dir), "librayq_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]
-    except OSError:
-        pass
-    cs = os.path.join(ROOT, "micro_raytracer_amd", "csrc")
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-o", out, os.path.join(ROOT, "tests", "emu", "rayq_probe.cpp"), os.path.join(cs, "mrt_pack.cpp")])
-    L = C.CDLL(out)
     fp, u32p, vp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p
     L.rq_error.restype = C.c_char_p
     L.rq_pack.argtypes = [vp, vp, C.c_uint32, u32p]

@@ -3,26 +3,19 @@ restatement, bit for bit; the C ABI's argument handling; the header; the CLI's a
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from emu.build import probe_or_skip
 
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = str(tmp_path_factory.mktemp("adapt") / "libadapt_probe.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-o", out, os.path.join(ROOT, "tests", "emu", "adapt_probe.cpp")])
-    L = C.CDLL(out)
+    L = probe_or_skip("adapt_probe", tmp_path_factory.mktemp("adapt"), with_pack=False)
     fp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
     L.adapt_pixel_errors.argtypes = [fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, fp]
     L.adapt_tile_errors.argtypes = [fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, fp, u32p, u32p]

@@ -7,14 +7,12 @@ chooses its body itself) -- the packer's classification and table, single querie
 GPU: a Cornell-shaped frame through both launch shapes against MRT_AXIS_SCAN=0 and the oracle, and a camera that sits on a
 plane and looks along an axis (direction components of exactly 0: those wavefronts fall back to the generic body)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, make_holder
+from conftest import make_holder
+from emu.build import probe_or_skip
 
 f32 = np.float32
 TOL = 1e-4          # tests/test_gpu_parity.py: mean radiance against the oracle, per channel, L-inf
@@ -24,21 +22,7 @@ WIN_LO, WIN_HI, AXIS_MAX = f32(2.0 ** -40), f32(2.0 ** 40), f32(2.0 ** 38)
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = os.path.join(str(tmp_path_factory.mktemp("axis_probe")), "libaxis_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]      # as tests/emu/Makefile
-    except OSError:
-        pass
-    cs = os.path.join(ROOT, "micro_raytracer_amd", "csrc")
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-pthread", "-o", out, os.path.join(ROOT, "tests", "emu", "axis_probe.cpp"),
-                           os.path.join(cs, "mrt_pack.cpp"), "-lpthread"])
-    L = C.CDLL(out)
+    L = probe_or_skip("axis_probe", tmp_path_factory.mktemp("axis_probe"))
     fp, u32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32
     L.ax_error.restype = C.c_char_p
     L.ax_pack.argtypes = [vp, u32p, u32p, C.c_uint64]

@@ -3,34 +3,19 @@ against a numpy float32 restatement of the filter (DESIGN.md §13), bit for bit;
 hits; the filter's quality on an oracle render; the Python option and CLI helpers."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from emu.build import probe_or_skip
 
 f32 = np.float32
 K5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], f32)
 
 
 def build_probe(out_dir):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = os.path.join(str(out_dir), "libdenoise_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]      # as tests/emu/Makefile: the kernels' fused multiply-adds (cull margins) in hardware
-    except OSError:
-        pass
-    cs = os.path.join(ROOT, "micro_raytracer_amd", "csrc")
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-o", out, os.path.join(ROOT, "tests", "emu", "denoise_probe.cpp"),
-                           os.path.join(cs, "mrt_pack.cpp")])
-    L = C.CDLL(out)
+    L = probe_or_skip("denoise_probe", out_dir)
     fp, u32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
     L.dn_error.restype = C.c_char_p
     L.dn_aov.argtypes = [C.c_void_p, fp, fp, i32p, i32p]

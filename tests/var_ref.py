@@ -1,14 +1,10 @@
 """TEST INFRASTRUCTURE: the variance-guided denoiser mode restated in numpy float32, in the operation order of
 csrc/mrt_denoise_var.h, and the x86 build of that header (tests/emu/var_probe.cpp) behind ctypes."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import ROOT
+from emu.build import probe_or_skip
 
 f32 = np.float32
 K5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], f32)
@@ -18,19 +14,7 @@ INF = float("inf")
 
 
 def build_probe(out_dir):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = os.path.join(str(out_dir), "libvar_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]      # as tests/emu/Makefile
-    except OSError:
-        pass
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-o", out, os.path.join(ROOT, "tests", "emu", "var_probe.cpp")])
-    L = C.CDLL(out)
+    L = probe_or_skip("var_probe", out_dir, with_pack=False)
     fp, u32p, u32, f = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32, C.c_float
     L.dv_prep.argtypes = [fp, fp, u32p, fp, fp, u32, u32, u32, f, fp]
     L.dv_filter.argtypes = [fp, fp, u32p, fp, fp, u32, u32, u32, f, f, f, f, u32, fp, fp]

@@ -2,14 +2,10 @@
 (tests/emu/vattr_probe.cpp), the float32 numpy restatement of DESIGN.md §14, and float64 references that share no code with
 the kernels: brute-force closest hits of the lens-centre rays and the closed-form render of a one-segment path."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import ROOT
+from emu.build import probe_or_skip
 
 f32 = np.float32
 WARM = 0xFFFFFFFF      # deep_nodes value of the probe: the warm (F_COLD) lane code on the binary triangle BVHs
@@ -17,21 +13,7 @@ WARM = 0xFFFFFFFF      # deep_nodes value of the probe: the warm (F_COLD) lane c
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
 def build_probe(out_dir):
-    cxx = shutil.which("g++")
-    if cxx is None:
-        pytest.skip("no g++")
-    out = os.path.join(str(out_dir), "libvattr_probe.so")
-    fma = []
-    try:
-        if " fma " in " " + open("/proc/cpuinfo").read().replace("\n", " ") + " ":
-            fma = ["-mfma"]      # as tests/emu/Makefile
-    except OSError:
-        pass
-    cs = os.path.join(ROOT, "micro_raytracer_amd", "csrc")
-    subprocess.check_call([cxx, "-O2", *fma, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-                           "-Wno-unused-function", "-pthread", "-o", out, os.path.join(ROOT, "tests", "emu", "vattr_probe.cpp"),
-                           os.path.join(cs, "mrt_pack.cpp"), "-lpthread"])
-    L = C.CDLL(out)
+    L = probe_or_skip("vattr_probe", out_dir)
     fp, u32p, i32p, vp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p
     L.va_error.restype = C.c_char_p
     L.va_interp.argtypes = [C.c_uint32] + [fp] * 9
