@@ -359,7 +359,7 @@ int mrt_denoise(mrt_ctx *ctx, const mrt_denoise_opts *o, float *rgb, mrt_denoise
 int mrt_img_denoised(mrt_ctx *ctx, const mrt_denoise_opts *o, uint8_t *rgb8, mrt_denoise_info *info);
 
 /* Test hook, host only (no device needed): what mrt_create would stage in LDS for this scene and the workgroup shape of its
- * launches -- the policy of csrc/mrt_api.cpp as data, so that it can be checked where no GPU exists. */
+ * launches -- the policy of csrc/mrt_plan.cpp as data, so that it can be checked where no GPU exists. */
 typedef struct mrt_plan {
     uint32_t staging;        /* 0 whole scene | 1 warm: texels in global memory (mesh kernels: + a per-lane leaf queue) | 2 deep: only the first
                                 tbvh_hot_nodes nodes of the (level-ordered) triangle-BVH table staged, triangles in global

@@ -6,7 +6,6 @@
 #include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <chrono>
@@ -20,6 +19,7 @@
 #include "mrt_denoise.h"
 #include "mrt_kernels.h"
 #include "mrt_pack.h"
+#include "mrt_plan.h"
 #include "mrt_trace.h"
 
 using namespace mrt;
@@ -121,8 +121,6 @@ struct Rccl {
 Rccl g_rccl;
 constexpr int kNcclFloat = 7;                        // ncclFloat32, rccl.h:466
 
-constexpr size_t kLdsLimit = 160u * 1024u;          // LDS per CU on gfx950
-constexpr size_t kSmallScene = 6u * 1024u;          // <= this: launches of less than one sample chunk take the plain grid (no tile counter)
 // Sample-split until the launch has ~25 rounds of 32 waves per CU: shorter wavefronts balance the tail of a launch (tiles
 // differ in path length).  Measured on the 1080p x 1024 spp Cornell box (tests/gpu_shard_probe.py): whole frame 328 -> 315 ms
 // with 4 lanes per pixel, one shard of 8 GPUs 47.1 -> 42.4 ms with 16; round 3, persistent 256-thread workgroups: 1 / 2 / 4 / 8
@@ -133,13 +131,6 @@ constexpr unsigned long long kSplitTargetWaves = 200000ull;
 // boundaries are chunk boundaries, so the canonical accumulation order -- and every bit -- is unchanged.
 constexpr u32 kMaxChunksPerLaunch = 64u;
 constexpr size_t kPartialBudgetBytes = (size_t)4u << 30;
-
-// an environment switch is on when it holds a non-zero number ("MRT_DEFER=0" and an empty value are off)
-bool env_on(const char *name)
-{
-    const char *v = getenv(name);
-    return v && *v && strtol(v, nullptr, 10) != 0;
-}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for every instantiation: once per device, not per mrt_create.  A device counts
 // as configured only after a SUCCESSFUL pass, so a transient failure is retried by the next mrt_create instead of being
@@ -223,13 +214,8 @@ struct mrt_ctx {
     bool handed_out = false;                      // mrt_accum_device_ptr gave the raw device pointer away: sticky, the caller may read it at any time
     bool bound = false;                           // the accumulator lives in caller memory (a successful mrt_bind_accum)
     bool exposed() const { return handed_out || bound; }   // either way the memory is visible behind the library's back: no deferral
-    // test / experiment knobs, read from the environment ONCE in mrt_create (a thread-per-connection server calls
-    // mrt_execute per sample: no getenv on that path)
-    u32 knob_k_split = 0;                         // MRT_K_SPLIT: forced lanes per pixel (0: policy)
-    u32 knob_max_chunks = 0;                      // MRT_MAX_CHUNKS: chunks per launch (0: kMaxChunksPerLaunch)
-    size_t knob_partial_budget = 0;               // MRT_PARTIAL_LIMIT_BYTES (0: kPartialBudgetBytes)
-    bool knob_partial_fail = false;               // MRT_PARTIAL_FAIL_ALLOC: the chunk-plane allocation asks for an impossible size
-    bool debug_fallbacks = false;                 // MRT_DEBUG_FALLBACKS: mrt_get_stats prints the reference-walk fallbacks of the mesh queries
+    Knobs knobs;                                  // the environment as mrt_create found it (a thread-per-connection server calls
+                                                  // mrt_execute per sample: that path reads no environment)
     u32 pending = 0;                              // samples requested by deferred mrt_execute calls and not traced yet
     // look-ahead of the eager per-call path (the reference's callers run one Sampler::execute per sample): see run_lookahead
     bool la_enabled = false;                      // eager single-device context without MRT_FLAG_NO_LOOKAHEAD / MRT_LOOKAHEAD=0
@@ -251,11 +237,8 @@ struct mrt_ctx {
     std::vector<u32> row_of;                      // local row -> frame row
     DeviceMem<float> full;                        // [nh][nw][3]: a group's frame, or the full frame a sharded context received
     u32 full_count = 0;
-    u32 block_threads = 256;                      // workgroup size of the batched launches
-    bool small_plain_grid = false;                // launches of less than one sample chunk (the per-sample calls of the reference's callers) take
-                                                  // the plain grid, one workgroup per 2x2 wave tiles: no tile counter to reset and draw from
+    Plan plan;                                    // staging level, launch shape, kernel instantiation (mrt_plan.h): fixed by mrt_create
     u32 persist_grid = 0;                         // persistent grid of the batched shape
-    bool scene_in_lds = true;
     mrt_stats stats;
     std::unique_ptr<Group> group;
     bool adaptive = false;                        // the accumulator holds an adaptive render: per-tile counts, count = the smallest
@@ -329,142 +312,7 @@ int mrt_device_count(void)
     return n;
 }
 
-
-namespace {
-
-// What a context stages in LDS and the shape of its launches: a pure function of the packed scene (and of the experiment /
-// test knobs of the environment) -- no device involved, so that the policy can be checked without one (mrt_plan_launch).
-struct Plan {
-    bool in_lds = true;
-    u32 block_threads = 256;
-    bool small_plain_grid = false;
-    size_t staged_bytes = 0;
-};
-
-void plan_launch(const mrt_render_desc *desc, const mrt_desc_ext *ext, Packed &pk, Plan &pl)
-{
-    // ---- what is staged in LDS, and the launch shape -------------------------------------------------------------------
-    // LDS per workgroup = staged scene + lane stash (+ the mesh kernels' walk areas): pt_lds_bytes knows.  Staging levels:
-    //   all     the whole packed scene (minus the octree leaf lists);
-    //   warm    F_COLD: texels stay in global memory (touched at most once per shaded hit); mesh kernels get a per-lane walk area;
-    //   deep    F_COLD | F_DEEP: meshes beyond the LDS.  The triangle-BVH table is in level order, so as many of its first
-    //           nodes -- the top levels of every tree -- as fit next to the small tables are staged; deeper nodes and the
-    //           triangles are read from global memory too;
-    //   none    everything through L2 (the small tables themselves do not fit).
-    // Launch shape, chosen for resident wavefronts per CU (the kernel is VALU-issue bound and wants >= 16): the smallest
-    // workgroup that reaches 16 waves per CU wins (smaller workgroups balance better), else the shape with the most:
-    //   256 threads (2x2 wave tiles of 8x8 pixels) + 10 KB lane stash per copy of the scene (64-thread workgroups -- one
-    //   wavefront, its own 5.5 KB of LDS -- remain as a forced shape for the tests);
-    //   512 threads (4x2 tiles), no stash; 1024 threads (4x4 tiles) + 40 KB stash: one LDS copy serves 16 waves.
-    // Mesh kernels of the warm and deep levels own a per-lane walk area (Params.walk_cap entries, mrt_trace.h): the leaf queue
-    // of the binary walk (8 to 16 entries, warm: what the LDS has left), or node stack + leaf queue of the 4-wide walk (16
-    // entries, deep: the scene is packed again with 4-wide triangle BVHs).
-    // Environment (experiments, tests; read here, once): MRT_COLD=0/1 forbids / forces the warm level, MRT_DEEP_NODES=n forces
-    // the deep level with n staged nodes, MRT_SCENE_IN_L2 forces none, MRT_BLOCK_THREADS forces a workgroup size, MRT_WALK_CAP
-    // the entries of the deep level's walk area, MRT_AXIS_SCAN=0 switches the axis scan of mrt_trace.h off.
-    const bool no_lds = getenv("MRT_SCENE_IN_L2") != nullptr;
-    const char *force = getenv("MRT_BLOCK_THREADS");
-    const bool mesh_walk = pk.n_tbvh_nodes != 0u && (pk.features & 3u) == 3u;
-    u32 deep_cap = kWalkCapDefault;
-    if (const char *fw = getenv("MRT_WALK_CAP")) { const int v = atoi(fw); if (v >= 4 && v <= (int)kWalkCapMax) deep_cap = (u32)v; }
-    pk.P.walk_cap = mesh_walk ? kLeafQueue : 0u;         // (only kernels with a walk area count it: pt_lds_bytes)
-    auto lds_of = [&](u32 shape, u32 marker) { return pt_lds_bytes(pk.P, shape, true, (pk.features & 31u) | marker); };
-    auto fits = [&](u32 shape, u32 marker) { return lds_of(shape, marker) <= kLdsLimit; };
-    auto fits_any = [&](u32 marker) { return fits(256u, marker) || fits(512u, marker) || fits(1024u, marker); };
-    auto waves = [&](u32 shape, u32 marker) {            // resident wavefronts per CU of this shape, LDS-wise
-        const size_t l = lds_of(shape, marker);
-        return l > kLdsLimit ? (size_t)0 : (shape / 64u) * (kLdsLimit / (l ? l : 1));
-    };
-    constexpr u32 kWarm = 64u, kDeep = 64u | 128u;       // F_COLD, F_COLD | F_DEEP
-    const bool has_warm = pk.P.lds_words_warm < pk.P.lds_words || mesh_walk;     // (mesh kernels: the warm marker also buys the walk area)
-    u32 cold = 0u;
-    bool in_lds = !no_lds;
-    if (in_lds) {
-        const char *fc = getenv("MRT_COLD");
-        const char *fd = getenv("MRT_DEEP_NODES");
-        const bool warm_ok = has_warm && fits_any(kWarm) && !(fc && !atoi(fc));
-        const bool all_ok = fits_any(0u) && !(fc && atoi(fc) && warm_ok);
-        // a mesh scene takes the warm level when a 16-wave workgroup fits with stash and leaf queues (closest-hit walks in one
-        // round: VALU -8.5 %, time -2 % on the 967-triangle bench scene); everything else takes the whole scene when it fits;
-        // an instance-BVH scene whose texels alone force a single 1024-thread workgroup per CU takes the warm level too: its
-        // kernel is built for 6 waves per SIMD, which 256-thread workgroups around an LDS copy without the texels can supply
-        const bool bvh_no_mesh = (pk.features & 16u) != 0u && (pk.features & 2u) == 0u;
-        if (fd && mesh_walk) cold = kDeep;
-        else if (mesh_walk && warm_ok && fits(1024u, kWarm)) cold = kWarm;
-        else if (bvh_no_mesh && warm_ok && !fc && waves(256u, 0u) < 16u && waves(256u, kWarm) >= 24u) cold = kWarm;
-        else if (all_ok) cold = 0u;
-        else if (warm_ok) cold = kWarm;
-        else if (mesh_walk) cold = kDeep;
-        else in_lds = false;
-        if (cold == kDeep) {
-            // packed again with 4-wide triangle BVHs in level order; everything hot in front of the node table + lane stash +
-            // walk areas of one 1024-thread workgroup; the rest of the LDS holds the first nodes of the table
-            PackOpts po; po.tbvh_wide = true;
-            Packed again; std::string err2;
-            bool ok2 = pack_scene(desc, again, err2, po, ext) == MRT_OK && again.tbvh_wide;
-            const size_t fixed = (size_t)ST_SLOTS * 1024u * sizeof(float) + (size_t)deep_cap * 1024u * sizeof(u32) + 1024u;
-            const size_t front = ok2 ? (size_t)again.P.off_tbvh * 4 : 0;
-            ok2 = ok2 && front + fixed < kLdsLimit;
-            if (ok2) {
-                const size_t room = (kLdsLimit - fixed - front) / (B4_WORDS * 4);
-                size_t n = fd ? (size_t)strtoul(fd, nullptr, 10) : room;
-                if (n > room) n = room;
-                if (n > again.n_tbvh_nodes) n = again.n_tbvh_nodes;
-                const u32 n_mesh = (again.P.off_node - again.P.off_mesh) / MESH_WORDS;
-                ok2 = n >= n_mesh && n_mesh > 0u;            // every root is staged
-                if (ok2) {
-                    const u32 keep = pk.features;
-                    pk = again;
-                    pk.features = keep;
-                    pk.P.walk_cap = deep_cap;
-                    pk.P.n_tbvh_hot = (u32)n;
-                    pk.P.lds_words_hot = (pk.P.off_tbvh + (u32)n * B4_WORDS + 3u) & ~3u;
-                }
-            }
-            if (!ok2) { cold = 0u; in_lds = false; }
-        }
-    }
-    const size_t full_bytes = (size_t)pk.P.lds_words * 4;
-    const size_t blob_bytes = in_lds ? (size_t)staged_words_for(pk.P, cold) * 4 : full_bytes;
-    u32 want = 256u, marker = cold;
-    pl.small_plain_grid = false;
-    if (in_lds) {
-        const size_t w256 = waves(256u, cold), w512 = waves(512u, cold), w1024 = waves(1024u, cold);
-        // small scenes (<= 6 KB: ~29 single-wave workgroups per CU would fit): 256-thread workgroups all the same -- four waves
-        // around one LDS copy, so that 32 waves per CU fit: +4 % on the headline frame, +7 % with the 8-wave build of the plane /
-        // sphere kernel, +4 % on CornellBox2 -- persistent for batched launches, on the plain grid for launches of less than
-        // one sample chunk (a one-sample pass over the 1080p frame: persistent 0.56 ms, single-wave workgroups 0.39, this 0.37)
-        if (w256 >= 16u) { want = 256u; pl.small_plain_grid = blob_bytes <= kSmallScene && !cold; }
-        else if (w512 >= 16u) want = 512u;
-        else if (w1024 >= 16u) want = 1024u;
-        else if (w256 >= w512 && w256 >= 8u) want = 256u;
-        else if (!cold && fits(1024u, 32u)) { want = 1024u; marker |= 32u; }      // F_NOSTASH: one LDS copy for 16 waves, lane state in registers
-        else want = w1024 ? 1024u : (w512 ? 512u : 256u);
-    }
-    if (force && in_lds) {
-        const u32 f = (u32)atoi(force);
-        if ((f == 64u && !cold) || f == 256u || f == 512u || f == 1024u) { if (fits(f, cold)) { want = f; marker = cold; pl.small_plain_grid = false; } }
-    }
-    pk.features = (pk.features & (31u | F_VATTR | F_ENV)) | marker | (pk.all_ident ? (u32)F_IDENT : 0u);      // (pt_instantiation: which shapes have F_IDENT builds)
-    // MRT_AXIS_SCAN=0 (tests, A/B runs): the closest-hit scan of the plain F_IDENT kernel keeps its generic body for every query
-    if (const char *fa = getenv("MRT_AXIS_SCAN")) { if (!atoi(fa)) pk.P.axis_scan = 0u; }
-    // the leaf queue of the warm mesh kernels takes what the LDS has left while the workgroups per CU stay the same (967-triangle
-    // bench scene: 13 entries, +2 % over 8: fewer walks need a second round)
-    if (in_lds && marker == kWarm && mesh_walk && has_walk_area(pk.features)) {
-        const size_t w0 = waves(want, marker);
-        while (pk.P.walk_cap < kWalkCapMax) {
-            ++pk.P.walk_cap;
-            if (waves(want, marker) != w0) { --pk.P.walk_cap; break; }
-        }
-    }
-    pl.in_lds = in_lds;
-    pl.block_threads = want;
-    pl.staged_bytes = blob_bytes;
-}
-
-}  // namespace
-
-static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext)
+static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext, const Knobs &knobs)
 {
     const u32 shard_count = opts->shard_count ? opts->shard_count : 1;
     if (opts->shard_index >= shard_count) { fail(MRT_ERR_ARG, "mrt_create: shard_index %u >= shard_count %u", opts->shard_index, shard_count); return nullptr; }
@@ -473,8 +321,9 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts,
     std::string err;
     const int rc = pack_scene(desc, c->pk, err, PackOpts(), ext);
     if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); return nullptr; }
-    Plan plan;
-    plan_launch(desc, ext, c->pk, plan);          // may re-pack the scene (deep staging: 4-wide triangle BVHs), before anything is uploaded
+    c->knobs = knobs;
+    Plan &plan = c->plan;
+    plan_launch(desc, ext, knobs, c->pk, plan);   // may re-pack the scene (deep staging: 4-wide triangle BVHs), before anything is uploaded
     if (c->pk.tbvh_wide) {                   // the AOV kernel (scene through L2, no F_DEEP build) walks the binary triangle BVHs
         c->aov_pk.reset(new Packed());
         if (pack_scene(desc, *c->aov_pk, err, PackOpts(), ext) != MRT_OK) { fail(MRT_ERR_SCENE, "mrt_create: %s", err.c_str()); return nullptr; }
@@ -515,14 +364,9 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts,
     if ((e = c->segments.alloc(8)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc", e);
     if ((e = hipMemset(c->segments.p, 0, 8 * sizeof(unsigned long long))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
 
-    c->scene_in_lds = plan.in_lds;
-    c->small_plain_grid = plan.small_plain_grid;
-    const u32 want = plan.block_threads;
-    const size_t blob_bytes = plan.staged_bytes;
-    c->block_threads = want;
-    c->pk.P.tiles_x = want == 64u ? 1u : (want == 256u ? 2u : 4u);
-    c->pk.P.tiles_y = want == 64u ? 1u : (want == 1024u ? 4u : 2u);
-    if (c->scene_in_lds && (e = configure_pt_once(dev)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipFuncSetAttribute", e);
+    c->pk.P.tiles_x = plan.tiles_x;
+    c->pk.P.tiles_y = plan.tiles_y;
+    if (plan.in_lds && (e = configure_pt_once(dev)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipFuncSetAttribute", e);
 
     c->P = c->pk.P;
     c->P.local_rows = c->local_rows; c->P.shard_index = c->shard_index; c->P.shard_count = c->shard_count; c->P.shard_rows = c->shard_rows;
@@ -534,31 +378,23 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts,
         // wavefront then draws 8x8 tiles from a counter, so no CU waits for the slowest wavefront of a workgroup
         int n_cu = 0;
         if (!hip_tolerated(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device)) || n_cu <= 0) n_cu = 256;
-        const size_t lds = pt_lds_bytes(c->pk.P, c->block_threads, c->scene_in_lds, c->pk.features);
-        size_t per_cu = 32u / (c->block_threads / 64u);
+        const size_t lds = plan.lds_bytes;
+        size_t per_cu = 32u / (plan.block_threads / 64u);
         if (lds && kLdsLimit / lds < per_cu) per_cu = kLdsLimit / lds;
         if (per_cu < 1u) per_cu = 1u;
-        c->persist_grid = c->block_threads > 64u && !getenv("MRT_NO_PERSIST") ? (u32)(n_cu * per_cu) : 0u;
+        c->persist_grid = plan.block_threads > 64u && !knobs.no_persist ? (u32)(n_cu * per_cu) : 0u;
         c->P.persist_grid = c->persist_grid;
     }
     c->count_segments = (opts->flags & MRT_FLAG_COUNT_SEGMENTS) != 0;
     c->event_timing = (opts->flags & MRT_FLAG_NO_EVENT_TIMING) == 0;
     c->P.count_segments = c->count_segments ? 1u : 0u;
     memset(&c->stats, 0, sizeof c->stats);
-    c->stats.lds_bytes = (u32)pt_lds_bytes(c->pk.P, c->block_threads, c->scene_in_lds, c->pk.features);
-    c->stats.block_threads = c->block_threads;
-    c->stats.scene_bytes = (u32)blob_bytes;
-    c->stats.kernel_features = pt_instantiation(c->block_threads, c->scene_in_lds, c->pk.features);
-    c->stats.scene_in_lds = c->scene_in_lds ? 1u : 0u;
-    c->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || (env_on("MRT_DEFER") && opts->shard_count <= 1);
-    if (const char *f = getenv("MRT_K_SPLIT")) { const int v = atoi(f); c->knob_k_split = v < 1 ? 1u : (u32)v; }                        // experiments / tests
-    if (const char *f = getenv("MRT_MAX_CHUNKS")) { const int v = atoi(f); if (v > 0) c->knob_max_chunks = (u32)v; }                   // tests
-    if (const char *f = getenv("MRT_PARTIAL_LIMIT_BYTES")) c->knob_partial_budget = (size_t)strtoull(f, nullptr, 10);                  // tests
-    c->knob_partial_fail = getenv("MRT_PARTIAL_FAIL_ALLOC") != nullptr;                                                                // tests
-    c->debug_fallbacks = env_on("MRT_DEBUG_FALLBACKS");
+    fill_stats(plan, c->stats);
+    c->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || (knobs.defer && opts->shard_count <= 1);
     // (MRT_FLAG_COUNT_SEGMENTS: every call runs its own launch, so that mrt_stats.segments counts that call's paths)
     c->la_enabled = !c->defer && !c->count_segments && (opts->flags & MRT_FLAG_NO_LOOKAHEAD) == 0;
-    if (const char *f = getenv("MRT_LOOKAHEAD")) { const int v = atoi(f); if (v <= 1) c->la_enabled = false; else c->la_max = v > 64 ? 64u : (u32)v; }
+    if (knobs.lookahead_off) c->la_enabled = false;
+    if (knobs.lookahead_max) c->la_max = knobs.lookahead_max;
     {   // both plane sets together stay below 4 GiB (32 samples of a 1080p frame: 2 x 0.8 GB; a 4K frame gets 20 per launch)
         const size_t plane_bytes = plane_floats(c.get()) * sizeof(float);
         const size_t fit = plane_bytes ? ((size_t)2u << 30) / plane_bytes : 0;
@@ -570,7 +406,7 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts,
 
 // In-process multi-device context: n sharded sub-contexts (device r renders row blocks b = r mod n), one RCCL
 // ncclGather of the padded shard accumulators to device 0 per mrt_execute, rows placed into the frame by scatter_rows.
-static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext, u32 n)
+static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext, u32 n, const Knobs &knobs)
 {
     std::string err;
     if (!g_rccl.load(err)) { fail(MRT_ERR_DEVICE, "mrt_create: %s", err.c_str()); return nullptr; }
@@ -580,7 +416,8 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
     const int rc = pack_scene(desc, g->pk, err, PackOpts(), ext);
     if (rc != MRT_OK) { fail(rc, "mrt_create: %s", err.c_str()); return nullptr; }
     g->device = 0; g->seed = opts->seed;
-    g->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || env_on("MRT_DEFER");
+    g->knobs = knobs;
+    g->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || knobs.defer;
     g->shard_count = 1; g->shard_index = 0; g->shard_rows = opts->shard_rows ? opts->shard_rows : 8;
     g->local_rows = g->pk.nh; g->padded_rows = g->pk.nh;
     for (u32 y = 0; y < g->pk.nh; ++y) g->row_of.push_back(y);
@@ -590,7 +427,7 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
         mrt_opts o = *opts;
         o.n_devices = 0; o.device = (int)r; o.shard_index = r; o.shard_count = n; o.shard_rows = g->shard_rows;
         o.flags &= ~MRT_FLAG_DEFER;                   // the group defers, not its shards
-        gr.subs.emplace_back(create_single(desc, &o, ext));
+        gr.subs.emplace_back(create_single(desc, &o, ext, knobs));
         if (!gr.subs.back()) return nullptr;
     }
     auto bail = [&](const char *what, const char *why) { fail(MRT_ERR_DEVICE, "mrt_create: %s: %s", what, why); return (mrt_ctx *)nullptr; };
@@ -614,8 +451,7 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
     if (nrc != 0) return bail("ncclCommInitAll", g_rccl.GetErrorString(nrc));
     g->P = g->pk.P;
     memset(&g->stats, 0, sizeof g->stats);
-    g->stats.block_threads = gr.subs[0]->block_threads; g->stats.lds_bytes = gr.subs[0]->stats.lds_bytes; g->stats.scene_bytes = gr.subs[0]->stats.scene_bytes;
-    g->stats.kernel_features = gr.subs[0]->stats.kernel_features; g->stats.scene_in_lds = gr.subs[0]->stats.scene_in_lds;
+    fill_stats(gr.subs[0]->plan, g->stats);
     ok();
     return g.release();
 }
@@ -627,14 +463,13 @@ mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const
     g_err.clear();
     if (!desc || !opts) { fail(MRT_ERR_ARG, "mrt_create: null argument"); return nullptr; }
     if (opts->abi_version != MRT_ABI_VERSION) { fail(MRT_ERR_ARG, "mrt_create: ABI version %u, library has %u", opts->abi_version, MRT_ABI_VERSION); return nullptr; }
-    u32 n = opts->n_devices;
-    if (n == 0) if (const char *e = getenv("MRT_GPUS")) n = (u32)atoi(e);       // the Rust shim's knob
-    const bool force_group = getenv("MRT_FORCE_RCCL") != nullptr;               // tests: the group path on one device
-    if (n > 1 || (n == 1 && force_group)) {
+    const Knobs knobs = Knobs::from_env();
+    const u32 n = opts->n_devices ? opts->n_devices : knobs.gpus;               // MRT_GPUS: the Rust shim's knob
+    if (n > 1 || (n == 1 && knobs.force_rccl)) {                                 // MRT_FORCE_RCCL (tests): the group path on one device
         if (opts->shard_count > 1) { fail(MRT_ERR_ARG, "mrt_create: n_devices and shard_count are mutually exclusive"); return nullptr; }
-        return create_group(desc, opts, ext, n);
+        return create_group(desc, opts, ext, n, knobs);
     }
-    return create_single(desc, opts, ext);
+    return create_single(desc, opts, ext, knobs);
 }
 
 void mrt_destroy(mrt_ctx *ctx) { delete ctx; }
@@ -662,7 +497,7 @@ static int resolve_stats(mrt_ctx *c)
         HIP_TRY(hipMemcpy(&seg, c->segments.p, sizeof seg, hipMemcpyDeviceToHost));
         c->stats.segments = seg;
     }
-    if (c->debug_fallbacks) {
+    if (c->knobs.debug_fallbacks) {
         unsigned long long t[3] = {0, 0, 0};
         HIP_TRY(hipMemcpy(t, c->segments.p + 5, sizeof t, hipMemcpyDeviceToHost));
         fprintf(stderr, "[mrt fallbacks] since mrt_create: NaN directions (shortcut) %llu, walk area full %llu, rays the triangle BVH may not cull %llu\n", t[0], t[1], t[2]);
@@ -689,19 +524,19 @@ static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks,
     // to a second lane per pixel, 985 -> 1001 ms)
     const unsigned long long split_target = wave_tiles >= 100000ull ? 0ull : kSplitTargetWaves;
     while (k_split * 2u <= n_chunks && k_split < 16u && wave_tiles * k_split < split_target) k_split *= 2u;
-    if (c->knob_k_split) { k_split = c->knob_k_split; while (k_split > n_chunks) k_split /= 2u; }
+    if (c->knobs.k_split) { k_split = c->knobs.k_split; while (k_split > n_chunks) k_split /= 2u; }
     if (planes && k_split < 2u) k_split = 2u;
     const size_t plane = plane_floats(c);
     cap = kMaxChunksPerLaunch;                           // chunks per launch
-    if (c->knob_max_chunks) cap = c->knob_max_chunks;
+    if (c->knobs.max_chunks) cap = c->knobs.max_chunks;
     size_t budget = kPartialBudgetBytes;
-    if (c->knob_partial_budget) budget = c->knob_partial_budget;
+    if (c->knobs.partial_budget) budget = c->knobs.partial_budget;
     if (k_split > 1u) {
         if (cap < k_split) cap = k_split;
         while (cap > k_split && plane * cap * sizeof(float) > budget) cap /= 2u;
         const size_t need = plane * (n_chunks < cap ? n_chunks : cap);
         if (need * sizeof(float) > budget) k_split = 1u;                       // not even k_split planes fit: one lane per pixel
-        else if (need > c->partial.n && !hip_tolerated(c->partial.alloc(need, c->knob_partial_fail ? (size_t)1 << 60 : 0))) k_split = 1u;
+        else if (need > c->partial.n && !hip_tolerated(c->partial.alloc(need, c->knobs.partial_fail_alloc ? (size_t)1 << 60 : 0))) k_split = 1u;
     }
     if (planes && k_split < 2u) return fail(MRT_ERR_LIMIT, "mrt_execute_adaptive: no memory for the chunk planes of a round");
     return MRT_OK;
@@ -711,9 +546,9 @@ static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks,
 // the kernel time leaves the reset out), then ev0, launch_pt, ev1 (null events are not recorded).  tl: a tile-list launch.
 static int launch_trace(mrt_ctx *c, const Params &P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const TileList *tl)
 {
-    if (c->block_threads > 64u && P.persist_grid) HIP_TRY(hipMemsetAsync(P.tile_counter, 0, sizeof(u32), stream));
+    if (c->plan.block_threads > 64u && P.persist_grid) HIP_TRY(hipMemsetAsync(P.tile_counter, 0, sizeof(u32), stream));
     if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
-    HIP_TRY(launch_pt(P, c->block_threads, c->scene_in_lds, c->pk.features, stream, tl));
+    HIP_TRY(launch_pt(P, c->plan.block_threads, c->plan.in_lds, c->pk.features, stream, tl));
     if (ev1) HIP_TRY(hipEventRecord(ev1, stream));
     return MRT_OK;
 }
@@ -751,7 +586,7 @@ static int launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *
         if (ks > ks_max) ks_max = ks;
         while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { Event e; HIP_TRY(create(e)); c->evs.push_back(std::move(e)); }
         const Event *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
-        c->P.persist_grid = (c->small_plain_grid && stop - base < kChunk) ? 0u : c->persist_grid;
+        c->P.persist_grid = (c->plan.small_plain_grid && stop - base < kChunk) ? 0u : c->persist_grid;
         if ((rc = launch_trace(c, c->P, c->stream.get(), ev ? ev[0].get() : nullptr, ev ? ev[1].get() : nullptr, tl))) return rc;
         if (ks > 1u) {
             if (tl) HIP_TRY(launch_reduce_chunks_listed(c->d_accum, half, c->partial.p, tl->tiles, tl->n, c->pk.nw, c->pk.nh, plane, nc, c->stream.get()));
@@ -781,9 +616,6 @@ static int exec_launch(mrt_ctx *c, uint32_t n_samples)
     if (c->count_segments) HIP_TRY(hipMemsetAsync(c->segments.p, 0, sizeof(unsigned long long), c->stream.get()));
     u32 ks_max = 0;                                  // (the uniform path reports the policy's k_split)
     if ((rc = launch_batch(c, c->count, n_samples, nullptr, nullptr, false, c->stats.k_split, ks_max))) return rc;
-    c->stats.block_threads = c->block_threads;
-    c->stats.lds_bytes = (u32)pt_lds_bytes(c->P, c->block_threads, c->scene_in_lds, c->pk.features);
-    c->stats.kernel_features = pt_instantiation(c->block_threads, c->scene_in_lds, c->pk.features);
     return MRT_OK;
 }
 
@@ -913,7 +745,7 @@ static int la_launch(mrt_ctx *c, int i, u32 base, u32 n)
     P.count_segments = 0u;
     // small scenes: the plain grid (their persistent grid fills every wave slot of the chip and would keep the folds out until
     // the launch has ended); larger ones leave slots free and keep their persistent workgroups, with a tile counter of their own
-    P.persist_grid = c->small_plain_grid ? 0u : c->persist_grid;
+    P.persist_grid = c->plan.small_plain_grid ? 0u : c->persist_grid;
     P.tile_counter = la.counter.p;
     const int rc = launch_trace(c, P, la.stream.get(), la.ev0[i].get(), la.ev1[i].get(), nullptr);
     if (rc) return rc;
@@ -953,7 +785,6 @@ static int run_lookahead(mrt_ctx *c)
     reset_exec_stats(c);
     c->stats.launches = 1u; c->stats.k_split = 1u;
     c->stats.samples = (uint64_t)c->local_rows * c->pk.nw;
-    c->stats.block_threads = c->block_threads;
     if (c->event_timing) {
         float ms = 0;
         if (hip_tolerated(hipEventElapsedTime(&ms, la.ev0[s].get(), la.ev1[s].get()))) c->stats.kernel_ms = (double)ms / (double)la.n[s];   // this sample's share of its launch
@@ -1418,9 +1249,7 @@ static int aov_compute(mrt_ctx *c, bool &cached, double &ms)
     HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     { float t = 0.0f; HIP_TRY(hipEventElapsedTime(&t, a.ev[0].get(), a.ev[1].get())); ms = t; }
-    // instances are flattened renderer by renderer in description order (mrt_pack.cpp): the first flat index of each renderer
-    a.inst_first.assign(ap.P.n_rend, 0u);
-    for (u32 i = ap.P.n_inst; i-- > 0;) a.inst_first[ap.blob[ap.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    a.inst_first = inst_first(ap);
     c->aov_ready = true;
     return MRT_OK;
 }
@@ -1567,18 +1396,8 @@ int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mr
     if (rc != MRT_OK) return fail(rc, "mrt_plan_launch: %s", err.c_str());
     const u32 n_nodes = pk.n_tbvh_nodes;
     Plan pl;
-    plan_launch(desc, ext, pk, pl);
-    memset(out, 0, sizeof *out);
-    out->staging = !pl.in_lds ? 3u : ((pk.features & 128u) ? 2u : ((pk.features & 64u) ? 1u : 0u));
-    out->block_threads = pl.block_threads;
-    out->lds_bytes = (uint32_t)pt_lds_bytes(pk.P, pl.block_threads, pl.in_lds, pk.features);
-    out->staged_bytes = pl.in_lds ? (uint32_t)pl.staged_bytes : 0u;
-    out->scene_bytes = pk.P.lds_words * 4u;
-    out->kernel_features = pt_instantiation(pl.block_threads, pl.in_lds, pk.features);
-    out->tbvh_nodes = n_nodes;
-    out->tbvh_hot_nodes = !pl.in_lds ? 0u : ((pk.features & 128u) ? pk.P.n_tbvh_hot : n_nodes);
-    out->small_plain_grid = pl.small_plain_grid ? 1u : 0u;
-    out->walk_cap = pk.P.walk_cap;
+    plan_launch(desc, ext, Knobs::from_env(), pk, pl);
+    fill_plan(pl, pk, n_nodes, *out);
     ok();
     return MRT_OK;
 }
@@ -1615,10 +1434,11 @@ int mrt_selftest_trace(mrt_ctx *c, size_t n, const float *orig, const float *dir
     if (n == 0 || n >= ((size_t)1 << 31)) return fail(MRT_ERR_ARG, "mrt_selftest_trace: n = %zu", n);
     if (c->group) return fail(MRT_ERR_STATE, "mrt_selftest_trace: multi-device context");
     if (c->shard_count > 1) return fail(MRT_ERR_STATE, "mrt_selftest_trace: sharded context");
-    const u32 inst = pt_instantiation(256u, c->scene_in_lds, c->pk.features);
-    if (!rayq_has(c->scene_in_lds, inst))
-        return fail(MRT_ERR_STATE, "mrt_selftest_trace: no ray-query kernel for FEAT %u with the scene in %s", inst, c->scene_in_lds ? "LDS" : "L2");
-    const size_t lds = pt_lds_bytes(c->P, 256u, c->scene_in_lds, c->pk.features);
+    const bool in_lds = c->plan.in_lds;
+    const u32 inst = pt_instantiation(256u, in_lds, c->pk.features);
+    if (!rayq_has(in_lds, inst))
+        return fail(MRT_ERR_STATE, "mrt_selftest_trace: no ray-query kernel for FEAT %u with the scene in %s", inst, in_lds ? "LDS" : "L2");
+    const size_t lds = pt_lds_bytes(c->P, 256u, in_lds, c->pk.features);
     if (lds > kLdsLimit) return fail(MRT_ERR_STATE, "mrt_selftest_trace: FEAT %u needs %zu bytes of LDS at 256 threads", inst, lds);
     int rc;
     if ((rc = set_device(c))) return rc;
@@ -1638,16 +1458,14 @@ int mrt_selftest_trace(mrt_ctx *c, size_t n, const float *orig, const float *dir
     P.count_segments = 0u;
     P.segments = d_seg.p;
     P.tile_counter = nullptr; P.accum = nullptr; P.partial = nullptr;
-    HIP_TRY(launch_rayq(P, c->scene_in_lds, inst, lds, (u32)n, d_o.p, d_d.p, d_out.p, c->stream.get()));
+    HIP_TRY(launch_rayq(P, in_lds, inst, lds, (u32)n, d_o.p, d_d.p, d_out.p, c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     HIP_TRY(hipMemcpy(out, d_out.p, n * MRT_TRACE_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
-    // flat instance index -> index within its renderer's inst list (instances are flattened renderer by renderer, mrt_pack.cpp)
-    const Packed &pk = c->pk;
-    std::vector<u32> inst_first(pk.P.n_rend, 0u);
-    for (u32 i = pk.P.n_inst; i-- > 0;) inst_first[pk.blob[pk.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    // flat instance index -> index within its renderer's inst list
+    const std::vector<u32> first = inst_first(c->pk);
     for (size_t i = 0; i < n; ++i) {
         uint32_t *q = out + i * MRT_TRACE_WORDS;
-        if (q[0] && q[2] < pk.P.n_rend) q[3] -= inst_first[q[2]];
+        if (q[0] && q[2] < first.size()) q[3] -= first[q[2]];
     }
     ok();
     return MRT_OK;

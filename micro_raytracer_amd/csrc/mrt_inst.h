@@ -1,6 +1,6 @@
-// mrt_inst.h — which pt_megakernel instantiation serves a scene: the one host-side statement of the rule.  Plain C++ with no HIP
-// dependency, so that the launchers (mrt_kernels.hip, mrt_denoise.hip), mrt_api.cpp and the x86 builds of tests/emu all call the
-// same function.
+// mrt_inst.h — which pt_megakernel instantiation serves a scene, and the LDS a workgroup of it needs: the one host-side statement
+// of both rules.  Plain C++ with no HIP dependency, so that the launchers (mrt_kernels.hip, mrt_denoise.hip), the kernels
+// (mrt_pt_kernel.h), the launch policy (mrt_plan.cpp), mrt_api.cpp and the x86 builds of tests/emu all call the same functions.
 #pragma once
 #include "mrt_trace.h"
 
@@ -37,6 +37,29 @@ inline u32 pt_instantiation(u32 block_threads, bool scene_in_lds, u32 features)
     if (block_threads == 256u && (features & F_IDENT) && (need & (F_TRI | F_MAPS)) == 0u) return need | F_IDENT;
     if (block_threads == 64u || block_threads == 256u) return need;
     return big | nostash;
+}
+
+// The per-path LDS stash (mrt_trace.h) is used by every launch shape that has room for it next to the scene: the
+// 64- and 256-thread workgroups with the scene in LDS.  It moves 7-25 VGPRs of rarely touched state out of the loop.
+constexpr bool lds_stash_for(bool scene_in_lds, int block_threads, u32 feat)
+{
+#ifdef MRT_NO_STASH
+    return false;
+#else
+    (void)scene_in_lds;      // scenes read through L2 keep the stash too: the LDS is otherwise empty
+    return block_threads != 512 && !(feat & F_NOSTASH);
+#endif
+}
+
+// LDS bytes per workgroup of a launch: staged scene + lane stash + the mesh kernels' walk areas
+inline size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 features)
+{
+    const u32 inst = pt_instantiation(block_threads, scene_in_lds, features);      // what the kernel itself sees as FEAT
+    size_t lds = scene_in_lds ? (size_t)staged_words_for(P, inst) * 4u : 0u;
+    lds = (lds + 15u) & ~(size_t)15u;
+    if (lds_stash_for(scene_in_lds, (int)block_threads, inst)) lds += (size_t)stash_slots_for(inst, block_threads) * block_threads * sizeof(float);
+    if (has_walk_area(inst)) lds += (size_t)P.walk_cap * block_threads * sizeof(u32);
+    return lds;
 }
 
 }  // namespace mrt

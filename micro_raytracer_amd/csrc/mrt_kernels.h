@@ -2,13 +2,12 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include "mrt_inst.h"      // pt_instantiation: FEAT template argument of the kernel launch_pt picks
+#include "mrt_inst.h"      // pt_instantiation: FEAT template argument of the kernel launch_pt picks; pt_lds_bytes
 #include "mrt_scene.h"
 
 namespace mrt {
 
 hipError_t configure_pt(size_t max_lds_bytes);
-size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 features);
 hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream, const TileList *list = nullptr);
 // mrt_adapt.hip: the tile-list instantiations (launch_pt with a list), their LDS attributes (configure_pt)
 hipError_t launch_pt_list(const Params &P, const TileList &TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst, hipStream_t stream);

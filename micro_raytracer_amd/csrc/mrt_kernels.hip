@@ -154,17 +154,7 @@ __global__ void __launch_bounds__(256) math_sweep(int op, unsigned long long fir
     }
 }
 
-// ---- launchers (declared in mrt_kernels.h); the instantiations: mrt_megakernel.h, which of them serves a scene: mrt_inst.h ----
-size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 features)
-{
-    const u32 inst = pt_instantiation(block_threads, scene_in_lds, features);      // what the kernel itself sees as FEAT
-    size_t lds = scene_in_lds ? (size_t)staged_words_for(P, inst) * 4u : 0u;
-    lds = (lds + 15u) & ~(size_t)15u;
-    if (lds_stash_for(scene_in_lds, (int)block_threads, inst)) lds += (size_t)stash_slots_for(inst, block_threads) * block_threads * sizeof(float);
-    if (has_walk_area(inst)) lds += (size_t)P.walk_cap * block_threads * sizeof(u32);
-    return lds;
-}
-
+// ---- launchers (declared in mrt_kernels.h); the instantiations: mrt_megakernel.h, which of them serves a scene and its LDS: mrt_inst.h ----
 hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream, const TileList *TL)
 {
     if (block_threads != P.tiles_x * P.tiles_y * 64u) return hipErrorInvalidConfiguration;

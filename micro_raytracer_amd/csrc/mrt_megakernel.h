@@ -1,8 +1,9 @@
-// mrt_megakernel.h — launch bounds and LDS stash policy of the path-tracing kernel (pt_megakernel in mrt_kernels.hip,
+// mrt_megakernel.h — launch bounds of the path-tracing kernel (pt_megakernel in mrt_kernels.hip,
 // pt_megakernel_list in mrt_adapt.hip: mrt_pt_kernel.h) and the list of its instantiations.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mrt_inst.h"      // lds_stash_for
 #include "mrt_trace.h"
 
 namespace mrt {
@@ -14,17 +15,6 @@ namespace mrt {
 // VALU-issue bound, so the light variants (planes / spheres / boxes, no maps, no lights, no triangles) are squeezed to
 // 6 waves per SIMD (80 VGPRs, a few spills: measured +14 % on the Cornell box); the heavier variants lose more to
 // spills than they gain from occupancy and keep the compiler's choice.  MRT_WAVES_PER_EU overrides (experiments).
-// The per-path LDS stash (mrt_trace.h) is used by every launch shape that has room for it next to the scene: the
-// 64- and 256-thread workgroups with the scene in LDS.  It moves 7-25 VGPRs of rarely touched state out of the loop.
-constexpr bool lds_stash_for(bool scene_in_lds, int block_threads, u32 feat)
-{
-#ifdef MRT_NO_STASH
-    return false;
-#else
-    (void)scene_in_lds;      // scenes read through L2 keep the stash too: the LDS is otherwise empty
-    return block_threads != 512 && !(feat & F_NOSTASH);
-#endif
-}
 #ifndef MRT_BVH_WAVES
 #define MRT_BVH_WAVES 6
 #endif

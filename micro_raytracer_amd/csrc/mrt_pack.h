@@ -34,6 +34,15 @@ struct PackOpts {
 // (mrt.h mrt_desc_ext), NULL = none.
 int pack_scene(const mrt_render_desc *desc, Packed &out, std::string &err, const PackOpts &opts = PackOpts(), const mrt_desc_ext *ext = nullptr);
 
+// Instances are flattened renderer by renderer in description order: the flat index of each renderer's first instance (a flat
+// instance index less this is the index within the renderer's inst list)
+inline std::vector<u32> inst_first(const Packed &pk)
+{
+    std::vector<u32> first(pk.P.n_rend, 0u);
+    for (u32 i = pk.P.n_inst; i-- > 0;) first[pk.blob[pk.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    return first;
+}
+
 // Flattened octree of one mesh in the layout of mrt_scene.h (exposed for tests).
 struct OctreeFlat {
     std::vector<float> nodes;     // NODE_WORDS words each (stored as raw words in a float vector)

@@ -162,8 +162,7 @@ inline int aov_frame(Packing &k, u32 inst, float *guide, float *albedo, int32_t 
 {
     unsigned long long seg[8] = {0};
     k.P.segments = seg;
-    std::vector<u32> first(k.P.n_rend, 0u);
-    for (u32 i = k.P.n_inst; i-- > 0;) first[k.pk.blob[k.P.off_instx + i * INSTX_WORDS + INSTX_REND]] = i;
+    const std::vector<u32> first = inst_first(k.pk);
     const bool known = with_feat(inst, [&](auto feat) {
         for (u32 y = 0; y < k.pk.nh; ++y)
             for (u32 x = 0; x < k.pk.nw; ++x) {

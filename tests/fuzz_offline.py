@@ -9,6 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 from conftest import make_holder  # noqa: E402
+from micro_raytracer_amd._abi import F_BVH
 from test_fuzz_scenes import random_scene, crowd_scene, _check  # noqa: E402
 
 
@@ -29,7 +30,7 @@ def main():
         ref, _ = o.accum()
         got, _ = emu_mod.render(h, seed, spp)
         import ctypes as C
-        n_bvh += bool(emu_mod.lib().emu_features(C.cast(h.ptr(), C.c_void_p)) & 16)
+        n_bvh += bool(emu_mod.lib().emu_features(C.cast(h.ptr(), C.c_void_p)) & F_BVH)
         try:
             _check(got, ref, spp)
             o.set_accum(got, spp)

@@ -8,7 +8,8 @@ import copy
 import numpy as np
 
 f32 = np.float32
-F_BOX, F_TRI, F_MAPS, F_LIGHTS, F_ALL, F_BVH, F_COLD, F_DEEP, F_IDENT, F_VATTR, F_ENV = 1, 2, 4, 8, 15, 16, 64, 128, 256, 512, 1024
+from micro_raytracer_amd._abi import F_ALL, F_BOX, F_BVH, F_COLD, F_DEEP, F_ENV, F_IDENT, F_LIGHTS, F_MAPS, F_TRI, F_VATTR  # noqa: F401
+
 FN = F_ALL & ~F_TRI
 WIN_LO, WIN_HI = f32(2.0 ** -40), f32(2.0 ** 40)
 

@@ -10,6 +10,7 @@ import pytest
 
 import env_ref as E
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_ALL, F_ENV, F_VATTR
 
 f32 = np.float32
 
@@ -91,7 +92,7 @@ def test_packing_leaves_the_staged_scene_alone(probe):
     _, h0 = make_holder(base)
     # no environment: the blob and the kernel's parameter block are those of a scene packed without the ext's env field
     info0, p0, b0 = E.x86_pack(probe, h0)
-    assert info0["off_env"] == 0 and not info0["features"] & 1024
+    assert info0["off_env"] == 0 and not info0["features"] & F_ENV
     for plain in (scenes.cornell_box(res=(32, 32)), scenes.default_scene(res=(32, 32))):
         _, hp = make_holder(plain)
         assert hp.ext is None
@@ -107,7 +108,7 @@ def test_packing_leaves_the_staged_scene_alone(probe):
     for tex in (one, big):
         r, h = make_holder(E.with_env(scenes.smooth_mesh_scene(res=(64, 48), sample=4, n_tris=300), tex, "latlong", 0.25))
         info, params, blob = E.x86_pack(probe, h)
-        assert info["features"] & 1024 and info["features"] & 512 and info["off_env"] >= info["lds_words"]
+        assert info["features"] & F_ENV and info["features"] & F_VATTR and info["off_env"] >= info["lds_words"]
         for k in ("lds_words", "lds_words_warm", "lds_words_hot", "walk_cap"):
             assert info[k] == info0[k], k
         assert np.array_equal(blob[:info0["lds_words"]], b0[:info0["lds_words"]])          # everything a kernel may stage
@@ -118,8 +119,8 @@ def test_packing_leaves_the_staged_scene_alone(probe):
         plans.append(_lib.plan_launch(h))
     for k in ("staging", "staged_bytes", "scene_bytes", "walk_cap", "block_threads", "lds_bytes"):
         assert plans[0][k] == plans[1][k], (k, plans)
-    assert plans[1]["kernel_features"] & 1024 and (plans[1]["kernel_features"] & 15) == 15
-    assert not _lib.plan_launch(h0)["kernel_features"] & 1024
+    assert plans[1]["kernel_features"] & F_ENV and (plans[1]["kernel_features"] & F_ALL) == F_ALL
+    assert not _lib.plan_launch(h0)["kernel_features"] & F_ENV
     # texels that are all k/255 take the RGB8 layout
     u8 = {"w": 5, "h": 3, "dat": (rng.integers(0, 256, (15, 3)).astype(f32) / f32(255.0))}
     _, h = make_holder(E.with_env(scenes.cornell_box(res=(32, 32)), u8))
@@ -244,10 +245,10 @@ def test_api_rejections_name_the_field():
     h = holder(mapping="latlong", rot=0.5)
     assert not h.ext.attrs
     h.ext.n_renderer = 77
-    assert _lib.plan_launch(h)["kernel_features"] & 1024
+    assert _lib.plan_launch(h)["kernel_features"] & F_ENV
     # negative zero is a legal texel, so is HDR
     t = E.const_env(1.0); t["dat"][0, 0] = -0.0; t["dat"][1, 1] = 6e4
-    assert _lib.plan_launch(holder(t))["kernel_features"] & 1024
+    assert _lib.plan_launch(holder(t))["kernel_features"] & F_ENV
     # layout of mrt_desc_ext: env takes the first two words of what was reserved[4]
     assert C.sizeof(_abi.DescExt) == 32 and _abi.DescExt.env.offset == 16 and _abi.DescExt.reserved.offset == 24
     assert C.sizeof(_abi.Env) == 40

@@ -11,6 +11,7 @@ import pytest
 import env_ref as E
 import filter_ref as F
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_ALL, F_BVH, F_ENV, F_VATTR
 
 f32 = np.float32
 SIZES = [(1, 1), (1, 7), (7, 1), (61, 31), (1024, 512)]
@@ -189,10 +190,10 @@ def test_packing_sets_two_flags_and_nothing_else(probe, env_probe):
 
     for make in (_mesh, lambda: scenes.minecraft_like(res=(40, 24), ssaa=1, sample=8), spheres_too, lambda: F.lit_scene("sphere", None)):
         _, h0, i0, p0, b0, pl0 = _pack(env_probe, make())
-        assert h0.desc.scene.n_textures > 0 and not i0["features"] & 1024
+        assert h0.desc.scene.n_textures > 0 and not i0["features"] & F_ENV
         _, h1, i1, p1, b1, pl1 = _pack(env_probe, F.with_filters(make(), tex="bilinear"))
         assert h1.ext.tex_filter == 1
-        assert i1["features"] == i0["features"] | 1024 | 512 and i1["off_env"] == 0
+        assert i1["features"] == i0["features"] | F_ENV | F_VATTR and i1["off_env"] == 0
         assert {k: v for k, v in i1.items() if k != "features"} == {k: v for k, v in i0.items() if k != "features"}
         assert np.array_equal(p0, p1)
         idx, has = mats(p0, b0)
@@ -205,11 +206,11 @@ def test_packing_sets_two_flags_and_nothing_else(probe, env_probe):
         assert all(b0[w] == 0 for w in idx) and all(b1[w] == ((3 if sp else 1) if m else 0) for w, m, sp in zip(idx, has, sphere))
         # the plan: what is staged and the launch shape stay; the LDS total holds the lane stash too, whose size belongs to the
         # kernel family (the Minecraft-shaped scene gives up the 16-slot stash of its 6-wave kernel for the full set's 7 slots)
-        full = (pl0["kernel_features"] & 15) == 15
+        full = (pl0["kernel_features"] & F_ALL) == F_ALL
         assert all(pl0[k] == pl1[k] for k in plan_keys if k != "lds_bytes" or full), (pl0, pl1)
         assert pl1["lds_bytes"] <= pl0["lds_bytes"]
-        assert pl1["kernel_features"] & 1024 and (pl1["kernel_features"] & 15) == 15 and not pl0["kernel_features"] & 1024
-        assert (pl1["kernel_features"] & 16) == (pl0["kernel_features"] & 16)
+        assert pl1["kernel_features"] & F_ENV and (pl1["kernel_features"] & F_ALL) == F_ALL and not pl0["kernel_features"] & F_ENV
+        assert (pl1["kernel_features"] & F_BVH) == (pl0["kernel_features"] & F_BVH)
     assert mixed                  # some scene has a material without maps, whose word stays 0
     # (c) both
     _, _, i0, p0, b0, pl0 = _pack(env_probe, E.with_env(_mesh(), tex))
@@ -236,7 +237,7 @@ def test_a_filter_with_nothing_to_act_on_is_no_request(env_probe):
         _, h1, i1, p1, b1, pl1 = _pack(env_probe, make(), ask)
         assert h1.ext.tex_filter == 1 and i0 == i1 and np.array_equal(p0, p1) and np.array_equal(b0, b1) and pl0 == pl1
         if h0.ext is None:
-            assert not pl1["kernel_features"] & 1024 and not i1["features"] & 1024
+            assert not pl1["kernel_features"] & F_ENV and not i1["features"] & F_ENV
     # Python does not even build an ext for it
     r, h = make_holder(F.with_filters(scenes.cornell_box(res=(32, 32)), tex="bilinear"))
     assert r.scene.tex_filter == "bilinear" and h.ext is None
@@ -286,7 +287,7 @@ def test_one_texel_textures_render_the_same_bytes_when_filtered(env_probe, name)
     d1["rt"]["bounce"] = 8
     (_, h0), (_, h1) = make_holder(d0), make_holder(d1)
     i0, i1 = E.x86_pack(env_probe, h0)[0], E.x86_pack(env_probe, h1)[0]
-    assert not i0["features"] & 1024 and i1["features"] & 1024 and i1["off_env"] == 0
+    assert not i0["features"] & F_ENV and i1["features"] & F_ENV and i1["off_env"] == 0
     for seed in (1, 2):
         base = E.x86_render(env_probe, h0, seed, 8)
         assert base.max() > 0
@@ -358,7 +359,7 @@ def test_api_rejections_name_the_field():
         assert e.value.code == code and all(w in e.value.msg for w in words), (e.value.code, e.value.msg)
 
     h = holder()
-    assert h.ext.tex_filter == 1 and h.ext.env.contents.filter == 1 and _lib.plan_launch(h)["kernel_features"] & 1024
+    assert h.ext.tex_filter == 1 and h.ext.env.contents.filter == 1 and _lib.plan_launch(h)["kernel_features"] & F_ENV
     for bad in (2, 7, 0xffffffff):
         h = holder(); h.ext.env.contents.filter = bad
         expect(h, _abi.MRT_ERR_SCENE, "env.filter")

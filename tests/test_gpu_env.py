@@ -6,6 +6,7 @@ import pytest
 
 import env_ref as E
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_ALL, F_BVH, F_COLD, F_DEEP, F_ENV, F_VATTR
 from test_gpu_vattr import LEVELS
 
 pytestmark = pytest.mark.gpu
@@ -80,8 +81,8 @@ def test_gpu_equals_x86_at_every_staging_level(probe, monkeypatch, mapping, crow
             for k in env:
                 monkeypatch.delenv(k)
             kf = st["kernel_features"]
-            assert kf & 1024 and kf & 512 and (kf & 15) == 15 and bool(kf & 16) == crowd, (env, kf)
-            assert (kf & 192) == markers and bool(st["scene_in_lds"]) == ("MRT_SCENE_IN_L2" not in env), (env, st)
+            assert kf & F_ENV and kf & F_VATTR and (kf & F_ALL) == F_ALL and bool(kf & F_BVH) == crowd, (env, kf)
+            assert (kf & (F_COLD | F_DEEP)) == markers and bool(st["scene_in_lds"]) == ("MRT_SCENE_IN_L2" not in env), (env, st)
             if "MRT_BLOCK_THREADS" in env:
                 assert st["block_threads"] == int(env["MRT_BLOCK_THREADS"]), (env, st)
             seen.add((kf, st["block_threads"], st["scene_in_lds"]))
@@ -122,14 +123,14 @@ def test_gpu_ones_and_twos_render_the_constant_sky(name):
     for seed in (1, 2):
         s = _gpu(build(), 8, seed)
         base = s.accum()[0]
-        assert not s.stats()["kernel_features"] & 1024
+        assert not s.stats()["kernel_features"] & F_ENV
         s.close()
         for mapping in E.MAPPINGS:
             for rot in (0.0, 0.37):
                 for label, r in (("ones", build(E.const_env(1.0), mapping, rot)), ("twos", build(E.const_env(2.0), mapping, rot, half))):
                     s = _gpu(r, 8, seed)
                     got = s.accum()[0]
-                    assert s.stats()["kernel_features"] & 1024
+                    assert s.stats()["kernel_features"] & F_ENV
                     s.close()
                     err = float(np.abs(got - base).max()) / 8
                     print(f"{name} seed {seed} {mapping} rot {rot} {label}: L-inf {err:.2e}, bits equal: {_same(got, base)}")
@@ -144,7 +145,7 @@ def test_gpu_mirror_sphere_equals_the_closed_form(mapping):
     for seed in (1, 2):
         s = _gpu(render, 4, seed)
         acc, cnt = s.accum()
-        assert cnt == 4 and s.stats()["kernel_features"] & 1024
+        assert cnt == 4 and s.stats()["kernel_features"] & F_ENV
         s.close()
         if first is None:
             E.check_closed_form(acc / f32(4), render, "GPU 256x256")
@@ -165,7 +166,7 @@ def test_gpu_adaptive_on_the_environment_scene():
     thr = float(np.median(et[np.isfinite(et)]))
     s = Sampler(seed=3, device=0)
     info = s.execute_adaptive(render, thr, min_samples=32, max_samples=96, step=16)
-    assert s.stats()["kernel_features"] & 1024
+    assert s.stats()["kernel_features"] & F_ENV
     A, _ = s.accum()
     counts = s.sample_counts()
     stops = sorted(set(np.unique(counts).tolist()))
@@ -209,7 +210,7 @@ def test_gpu_two_row_shards_assemble_to_the_frame():
     parts = np.zeros_like(whole)
     for i in (0, 1):
         s = _gpu(render, 16, 5, shard_index=i, shard_count=2)
-        assert s.stats()["kernel_features"] & 1024
+        assert s.stats()["kernel_features"] & F_ENV
         part, rows = s.accum_local()
         parts[rows] = part
         s.close()
@@ -235,7 +236,7 @@ def test_gpu_environment_at_the_texel_limit(probe):
     want = E.x86_render(probe, holder, 1, 1)
     s = _gpu(render, 1, 1)
     got, cnt = s.accum()
-    assert s.stats()["kernel_features"] & 1024
+    assert s.stats()["kernel_features"] & F_ENV
     s.close()
     err = float(np.abs(got - want).max())
     print(f"8192 x 4096 environment: L-inf {err:.2e}, bits equal: {_same(got, want)}")

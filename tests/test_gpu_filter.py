@@ -9,6 +9,7 @@ import pytest
 import env_ref as E
 import filter_ref as F
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_ALL, F_BVH, F_COLD, F_DEEP, F_ENV, F_VATTR
 from test_gpu_vattr import LEVELS
 
 pytestmark = pytest.mark.gpu
@@ -73,8 +74,8 @@ def test_gpu_equals_x86_at_every_staging_level(probe, monkeypatch, crowd):
         for k in env:
             monkeypatch.delenv(k)
         kf = st["kernel_features"]
-        assert kf & 1024 and kf & 512 and (kf & 15) == 15 and bool(kf & 16) == crowd, (env, kf)
-        assert (kf & 192) == markers and bool(st["scene_in_lds"]) == ("MRT_SCENE_IN_L2" not in env), (env, st)
+        assert kf & F_ENV and kf & F_VATTR and (kf & F_ALL) == F_ALL and bool(kf & F_BVH) == crowd, (env, kf)
+        assert (kf & (F_COLD | F_DEEP)) == markers and bool(st["scene_in_lds"]) == ("MRT_SCENE_IN_L2" not in env), (env, st)
         seen.add((kf, st["block_threads"], st["scene_in_lds"]))
         err = float(np.abs(got - want).max()) / spp
         print(f"crowd {crowd} {env}: features {kf}, {st['block_threads']} threads, L-inf {err:.2e}, bits equal: {_same(got, want)}")
@@ -98,7 +99,7 @@ def test_gpu_each_filter_alone_equals_x86(probe, which):
     got, _ = s.accum()
     st, aov = s.stats(), s.aov()
     s.close()
-    assert st["kernel_features"] & 1024
+    assert st["kernel_features"] & F_ENV
     print(f"{which} alone: L-inf {float(np.abs(got - want).max()) / 16:.2e}, bits equal: {_same(got, want)}")
     assert _same(got, want)
     ref = E.x86_aov(probe, holder)
@@ -132,7 +133,7 @@ def test_gpu_constant_environments_render_the_same_bytes_filtered(name):
         for filt in ("nearest", "bilinear"):
             s = _gpu(build(tex, color, filt), 8, 1)
             out[filt] = s.accum()[0]
-            assert s.stats()["kernel_features"] & 1024
+            assert s.stats()["kernel_features"] & F_ENV
             s.close()
         assert _same(out["bilinear"], out["nearest"]), (name, label)
         err = float(np.abs(out["bilinear"] - base).max()) / 8
@@ -158,14 +159,14 @@ def test_gpu_one_texel_textures_render_the_unfiltered_scene(probe, name):
     st, aov = s.stats(), s.aov()
     den, raw = s.denoise(), s.denoise(passes=0)
     s.close()
-    assert st["kernel_features"] & 1024 and _same(got, want)
+    assert st["kernel_features"] & F_ENV and _same(got, want)
     ref = E.x86_aov(probe, h1)
     _check_aov(aov, ref)
     miss = ref[0][..., 7] == 0
     assert (aov["albedo"][miss] == 0).all()
     s = _gpu(r0, 8, 1)
     base, _ = s.accum()
-    assert not s.stats()["kernel_features"] & 1024
+    assert not s.stats()["kernel_features"] & F_ENV
     den0 = s.denoise()
     s.close()
     err = float(np.abs(got - base).max()) / 8
@@ -186,7 +187,7 @@ def test_gpu_mirror_sphere_under_a_filtered_environment(mapping):
     def run(render, holder):
         s = _gpu(render, 4, 1)
         acc, cnt = s.accum()
-        assert cnt == 4 and s.stats()["kernel_features"] & 1024
+        assert cnt == 4 and s.stats()["kernel_features"] & F_ENV
         s.close()
         return acc / f32(4)
     check_mirror(run, mapping, (256, 256), "GPU 256x256")
@@ -199,7 +200,7 @@ def test_gpu_textured_surface_under_a_point_light(kind):
     def run(render, holder):
         s = _gpu(render, 2, 1)
         acc, _ = s.accum()
-        assert bool(s.stats()["kernel_features"] & 1024) == (render.scene.tex_filter == "bilinear")
+        assert bool(s.stats()["kernel_features"] & F_ENV) == (render.scene.tex_filter == "bilinear")
         s.close()
         return acc / f32(2)
     check_lit(run, kind, (256, 256), "GPU 256x256")
@@ -218,7 +219,7 @@ def test_gpu_adaptive_with_both_filters():
     thr = float(np.median(et[np.isfinite(et)]))
     s = Sampler(seed=3, device=0)
     info = s.execute_adaptive(render, thr, min_samples=32, max_samples=96, step=16)
-    assert s.stats()["kernel_features"] & 1024
+    assert s.stats()["kernel_features"] & F_ENV
     A, _ = s.accum()
     counts = s.sample_counts()
     s.close()
@@ -266,7 +267,7 @@ def test_gpu_filtered_environment_at_the_texel_limit(probe):
     want = E.x86_render(probe, holder, 1, 1)
     s = _gpu(render, 1, 1)
     got, cnt = s.accum()
-    assert s.stats()["kernel_features"] & 1024
+    assert s.stats()["kernel_features"] & F_ENV
     s.close()
     print(f"8192 x 4096 filtered environment: L-inf {float(np.abs(got - want).max()):.2e}, bits equal: {_same(got, want)}")
     assert cnt == 1 and _same(got, want)

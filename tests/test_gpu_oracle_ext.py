@@ -7,11 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_BVH, F_ENV, F_VATTR
 from test_oracle_ext import SCENES, compare, oracle_render
 
 pytestmark = pytest.mark.gpu
 
-F_BVH, F_VATTR, F_ENV = 16, 512, 1024
 ENV_FAMILY = {n for n in SCENES if n.startswith("env_")} | {"maps_bilinear", "matfilter_noenv"}      # an environment, or filtered maps
 
 

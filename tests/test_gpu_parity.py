@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_COLD, F_DEEP
 
 pytestmark = pytest.mark.gpu
 
@@ -204,7 +205,7 @@ def test_every_launch_shape_gives_the_same_bits(monkeypatch):
 
 
 def test_every_staging_level_gives_the_same_bits(monkeypatch):
-    """What a workgroup stages in LDS is a layout choice (csrc/mrt_api.cpp): the whole scene, the warm prefix (membership
+    """What a workgroup stages in LDS is a layout choice (csrc/mrt_plan.cpp): the whole scene, the warm prefix (membership
     tables and texels read from global memory; the mesh kernels queue every leaf of a closest-hit walk), the deep level (the
     triangle-BVH table in level order, only its first nodes staged, triangles in global memory), nothing (all through L2).
     Every level must give the same accumulator bits, for every workgroup size it admits."""
@@ -217,7 +218,7 @@ def test_every_staging_level_gives_the_same_bits(monkeypatch):
         monkeypatch.setenv("MRT_COLD", "0")
         base = _gpu_render(render, spp)
         ref = base.accum()[0]
-        assert base.stats()["kernel_features"] & 64 == 0
+        assert base.stats()["kernel_features"] & F_COLD == 0
         monkeypatch.delenv("MRT_COLD")
         seen = set()
         levels = [{"MRT_COLD": "1"}] + ([{"MRT_DEEP_NODES": "3"}, {"MRT_DEEP_NODES": "40"}, {"MRT_DEEP_NODES": "100000"}] if has_mesh else [])
@@ -230,12 +231,12 @@ def test_every_staging_level_gives_the_same_bits(monkeypatch):
                 s = _gpu_render(render, spp)
                 got = s.accum()[0]
                 st = s.stats()
-                seen.add((st["kernel_features"] & 192, st["block_threads"]))
+                seen.add((st["kernel_features"] & (F_COLD | F_DEEP), st["block_threads"]))
                 s.close()
                 for k in list(env) + ["MRT_BLOCK_THREADS"]:
                     monkeypatch.delenv(k, raising=False)
-                assert st["kernel_features"] & 64, (env, threads, st)
-                assert bool(st["kernel_features"] & 128) == ("MRT_DEEP_NODES" in env), (env, st)
+                assert st["kernel_features"] & F_COLD, (env, threads, st)
+                assert bool(st["kernel_features"] & F_DEEP) == ("MRT_DEEP_NODES" in env), (env, st)
                 assert np.array_equal(ref.view(np.uint32), got.view(np.uint32)), (env, threads)
         assert len(seen) >= (6 if has_mesh else 3), seen
 

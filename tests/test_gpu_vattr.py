@@ -6,6 +6,7 @@ import pytest
 
 import vattr_ref as V
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_ALL, F_BVH, F_COLD, F_DEEP, F_VATTR
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -39,8 +40,8 @@ def _same(a, b):
 
 
 LEVELS = [({"MRT_COLD": "0", "MRT_BLOCK_THREADS": t}, 0) for t in ("64", "256", "512", "1024")] + \
-         [({"MRT_COLD": "1", "MRT_BLOCK_THREADS": t}, 64) for t in ("256", "512", "1024")] + \
-         [({"MRT_DEEP_NODES": n, "MRT_BLOCK_THREADS": t}, 192) for n, t in (("3", "256"), ("40", "512"), ("100000", "1024"))] + \
+         [({"MRT_COLD": "1", "MRT_BLOCK_THREADS": t}, F_COLD) for t in ("256", "512", "1024")] + \
+         [({"MRT_DEEP_NODES": n, "MRT_BLOCK_THREADS": t}, F_COLD | F_DEEP) for n, t in (("3", "256"), ("40", "512"), ("100000", "1024"))] + \
          [({"MRT_SCENE_IN_L2": "1"}, 0)]
 
 
@@ -74,8 +75,8 @@ def test_gpu_equals_x86_at_every_staging_level(probe, monkeypatch, crowd):
             for k in env:
                 monkeypatch.delenv(k)
             kf = st["kernel_features"]
-            assert kf & 512 and (kf & 15) == 15 and bool(kf & 16) == crowd, (env, kf)
-            assert (kf & 192) == markers and bool(st["scene_in_lds"]) == ("MRT_SCENE_IN_L2" not in env), (env, st)
+            assert kf & F_VATTR and (kf & F_ALL) == F_ALL and bool(kf & F_BVH) == crowd, (env, kf)
+            assert (kf & (F_COLD | F_DEEP)) == markers and bool(st["scene_in_lds"]) == ("MRT_SCENE_IN_L2" not in env), (env, st)
             if "MRT_BLOCK_THREADS" in env:
                 assert st["block_threads"] == int(env["MRT_BLOCK_THREADS"]), (env, st)
             seen.add((kf, st["block_threads"], st["scene_in_lds"]))
@@ -100,7 +101,7 @@ def test_gpu_equals_x86_at_every_staging_level(probe, monkeypatch, crowd):
     plain, _ = make_holder(scenes.mesh_scene(res=(96, 54), sample=16, n_tris=600))
     if not crowd:
         s = _gpu(plain, spp, 2)
-        assert not s.stats()["kernel_features"] & 512 and not _same(s.accum()[0], first)
+        assert not s.stats()["kernel_features"] & F_VATTR and not _same(s.accum()[0], first)
         s.close()
 
 
@@ -112,7 +113,7 @@ def test_gpu_bounce0_render_equals_the_closed_form():
     for seed in (1, 2):
         s = _gpu(render, 4, seed)
         acc, cnt = s.accum()
-        assert s.stats()["kernel_features"] & 512
+        assert s.stats()["kernel_features"] & F_VATTR
         s.close()
         if seed == 1:
             check_closed_form(acc / f32(4), render, "GPU 256x256")
@@ -158,7 +159,7 @@ def test_gpu_adaptive_and_denoise_on_the_smooth_mesh():
     thr = float(np.median(et[np.isfinite(et)]))
     s = Sampler(seed=3, device=0)
     info = s.execute_adaptive(render, thr, min_samples=32, max_samples=96, step=16)
-    assert s.stats()["kernel_features"] & 512
+    assert s.stats()["kernel_features"] & F_VATTR
     A, _ = s.accum()
     counts = s.sample_counts()
     stops = sorted(set(np.unique(counts).tolist()))

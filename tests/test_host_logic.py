@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, make_holder
+from micro_raytracer_amd._abi import F_ALL, F_BOX, F_BVH, F_COLD, F_DEEP, F_IDENT, F_LIGHTS, F_MAPS
 
 
 def test_library_exports_every_declared_symbol():
@@ -130,7 +131,7 @@ def test_instance_bvh_is_built_only_for_many_instances(emu_mod):
         info = (C.c_uint32 * 8)()
         assert L.emu_pack(C.cast(h.ptr(), C.c_void_p), None, None, None, info) == 0
         feats = L.emu_features(C.cast(h.ptr(), C.c_void_p))
-        assert bool(feats & 16) == want
+        assert bool(feats & F_BVH) == want
 
 
 def test_packer_texture_formats_and_sizes(emu_mod):
@@ -432,7 +433,7 @@ def test_level_ordered_triangle_bvh_walk_equals_the_depth_first_one(emu_mod):
 
 
 def test_launch_plan_staging_levels_and_shapes(monkeypatch):
-    """The launch policy of csrc/mrt_api.cpp as data (mrt_plan_launch: host only): which part of the scene a workgroup stages
+    """The launch policy of csrc/mrt_plan.cpp as data (mrt_plan_launch: host only): which part of the scene a workgroup stages
     in LDS and the workgroup size, for the scenes of the BASELINE configs and the meshes beyond the LDS."""
     from micro_raytracer_amd import _lib, load_render, scenes
     LDS = 160 * 1024
@@ -441,29 +442,29 @@ def test_launch_plan_staging_levels_and_shapes(monkeypatch):
         monkeypatch.delenv(k, raising=False)
     # small scenes: the whole scene, four waves around one copy, 8 workgroups per CU; one-sample launches on the plain grid
     # (256 = F_IDENT: every instance untransformed; CornellBox2 has a rotated box)
-    for d, feat in ((scenes.cornell_box(res=(1920, 1080)), 0 | 256), (scenes.cornell_box2(res=(1920, 1080)), 1), (scenes.default_scene(), 8 | 256)):
+    for d, feat in ((scenes.cornell_box(res=(1920, 1080)), 0 | F_IDENT), (scenes.cornell_box2(res=(1920, 1080)), F_BOX), (scenes.default_scene(), F_LIGHTS | F_IDENT)):
         p = plan(d)
         assert (p["staging"], p["block_threads"], p["kernel_features"], p["small_plain_grid"]) == ("all", 256, feat, 1), p
         assert p["staged_bytes"] == p["scene_bytes"] < 6 * 1024 and 8 * p["lds_bytes"] <= LDS
     # the 967-triangle mesh scene: warm (texels and octree leaf lists out), one 1024-thread workgroup with stash and walk areas
     p = plan(scenes.mesh_scene())
-    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("warm", 1024, 15 | 64), p
+    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("warm", 1024, F_ALL | F_COLD), p
     # triangles and membership tables staged; the leaf queue of the binary walk: 8 entries + what the LDS has left
     assert p["walk_cap"] == 9 and p["scene_bytes"] - p["staged_bytes"] < 13 * 1024        # (only the octree leaf lists stay out)
     assert p["staged_bytes"] < p["scene_bytes"] and p["lds_bytes"] == p["staged_bytes"] + 1024 * 4 * (7 + 9) <= LDS < p["lds_bytes"] + 4096
     assert p["tbvh_hot_nodes"] == p["tbvh_nodes"] > 1000            # binary nodes
     # the Minecraft-shaped scene: warm, 256-thread workgroups (6-wave kernel: six of them per CU), texels out of LDS
     p = plan(scenes.minecraft_like())
-    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("warm", 256, 29 | 64), p
+    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("warm", 256, F_BOX | F_MAPS | F_LIGHTS | F_BVH | F_COLD), p
     assert p["scene_bytes"] - p["staged_bytes"] > 70 * 1024 and 6 * p["lds_bytes"] <= LDS < 7 * p["lds_bytes"]
     # meshes beyond the LDS: deep -- 4-wide triangle BVH in level order, as many top nodes as fit, triangles out
     for n in (5120, 20480):
         p = plan(scenes.mesh_scene(res=(64, 36), n_tris=n))
-        assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("deep", 1024, 15 | 64 | 128), p
+        assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("deep", 1024, F_ALL | F_COLD | F_DEEP), p
         assert 300 < p["tbvh_hot_nodes"] < p["tbvh_nodes"] and LDS - 4096 < p["lds_bytes"] <= LDS and p["walk_cap"] == 16
     # 1000 instances, no texels: nothing to leave out, one copy for a 1024-thread workgroup
     p = plan(scenes.instance_grid())
-    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("all", 1024, 8 | 16 | 256), p      # (256: all untransformed)
+    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("all", 1024, F_LIGHTS | F_BVH | F_IDENT), p      # (256: all untransformed)
     # the knobs of the tests
     monkeypatch.setenv("MRT_SCENE_IN_L2", "1")
     p = plan(scenes.mesh_scene())
@@ -471,13 +472,13 @@ def test_launch_plan_staging_levels_and_shapes(monkeypatch):
     monkeypatch.delenv("MRT_SCENE_IN_L2")
     monkeypatch.setenv("MRT_COLD", "0")
     p = plan(scenes.minecraft_like())
-    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("all", 1024, 29), p
+    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("all", 1024, F_BOX | F_MAPS | F_LIGHTS | F_BVH), p
     p = plan(scenes.mesh_scene())
-    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("all", 1024, 15), p
+    assert (p["staging"], p["block_threads"], p["kernel_features"]) == ("all", 1024, F_ALL), p
     monkeypatch.delenv("MRT_COLD")
     monkeypatch.setenv("MRT_DEEP_NODES", "5")
     p = plan(scenes.mesh_scene(res=(64, 36), n_tris=300))
-    assert (p["staging"], p["tbvh_hot_nodes"], p["kernel_features"] & 192) == ("deep", 5, 192), p
+    assert (p["staging"], p["tbvh_hot_nodes"], p["kernel_features"] & (F_COLD | F_DEEP)) == ("deep", 5, F_COLD | F_DEEP), p
     monkeypatch.delenv("MRT_DEEP_NODES")
     monkeypatch.setenv("MRT_BLOCK_THREADS", "64")
     p = plan(scenes.cornell_box())

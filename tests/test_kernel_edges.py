@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_BVH, F_COLD, F_DEEP, F_IDENT
 from test_fuzz_scenes import _check, crowd_scene, mesh_fuzz_scene
 
 TOP = 0xffffffff
@@ -43,7 +44,7 @@ def test_sample_indices_at_the_top_of_the_range_on_x86(name, oracle_mod, emu_mod
     desc = _top_scenes()[name]
     render, h = make_holder(desc)
     if name == "crowd":
-        assert emu_mod.layout(h)["features"] & 16, "the crowd scene must take the instance-BVH kernels"
+        assert emu_mod.layout(h)["features"] & F_BVH, "the crowd scene must take the instance-BVH kernels"
     for base, n in TOP_CASES:
         o, ref = _oracle_at(oracle_mod, h, 11, base, n)
         got, _ = emu_mod.render(h, 11, n, sample_base=base)
@@ -225,12 +226,12 @@ def test_deep_walk_and_walk_area_overflow_gpu(seed, oracle_mod, monkeypatch, cap
         monkeypatch.delenv(k, raising=False)
     # the whole-scene kernels: from LDS where the scene fits, through L2 where it does not (MRT_COLD=0 takes the deep level then)
     monkeypatch.setenv("MRT_COLD", "0")
-    if _lib.plan_launch(h)["kernel_features"] & 192:
+    if _lib.plan_launch(h)["kernel_features"] & (F_COLD | F_DEEP):
         monkeypatch.setenv("MRT_SCENE_IN_L2", "1")
     s = Sampler(seed=seed)
     s.execute(render, n_samples=spp)
     base, _ = s.accum()
-    assert s.stats()["kernel_features"] & 192 == 0
+    assert s.stats()["kernel_features"] & (F_COLD | F_DEEP) == 0
     s.close()
     monkeypatch.delenv("MRT_COLD")
     monkeypatch.delenv("MRT_SCENE_IN_L2", raising=False)
@@ -256,7 +257,7 @@ def test_deep_walk_and_walk_area_overflow_gpu(seed, oracle_mod, monkeypatch, cap
                 st = s.stats()
                 err = capfd.readouterr().err
                 what = (hot, cap, threads, st["kernel_features"], st["block_threads"])
-                assert st["kernel_features"] & 192 == 192, what
+                assert st["kernel_features"] & (F_COLD | F_DEEP) == (F_COLD | F_DEEP), what
                 if threads:
                     assert st["block_threads"] == int(threads), what
                 assert _same_bits(got, base), what
@@ -288,7 +289,7 @@ def test_ident_kernels_share_the_transform_bit_for_bit(emu_mod):
         verdict[name] = all_ident
         if all_ident:
             assert bad == 0, (name, bad)
-        assert bool(_lib.plan_launch(load_render(desc))["kernel_features"] & 256) == all_ident, name
+        assert bool(_lib.plan_launch(load_render(desc))["kernel_features"] & F_IDENT) == all_ident, name
     # the mixed scene really has identities that differ on such vectors, and is kept off the F_IDENT kernels
     _, h = make_holder(ec["ident_zero_signs_mixed"])
     assert emu_mod.ident_xf(h)[1] > 0 and not verdict["mixed"]

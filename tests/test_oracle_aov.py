@@ -18,6 +18,7 @@ import pytest
 import env_ref as E
 import test_denoise_host as D
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_BVH
 
 f32 = np.float32
 THREADS = min(16, os.cpu_count() or 1)
@@ -302,7 +303,7 @@ def test_oracle_aov_equals_x86_on_several_instanced_renderers(oracle_mod, probes
     render, holder, ref, got, _ = check_scene("multi_crowd", oracle_mod, probes, multi_crowd())
     check_multi_crowd_ids(ref)
     info, _, _ = E.x86_pack(probes[1], holder, with_ext=False)
-    assert info["features"] & 16                          # F_BVH: the instance BVH
+    assert info["features"] & F_BVH                          # F_BVH: the instance BVH
 
 
 def test_env_ref_helpers_size_their_frames_by_the_supersampled_frame(probes, oracle_mod):

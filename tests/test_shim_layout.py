@@ -126,3 +126,14 @@ def test_extern_block_matches_header_and_library():
         assert len(c_args) == len(r_args), (name, c_args, r_args)
     # the ABI version the shim passes is the library's
     assert re.search(r"abi_version:\s*(\d+)", src).group(1) == str(L.mrt_abi_version())
+
+
+def test_feature_bit_names_match_the_kernel_header():
+    """The F_* constants of micro_raytracer_amd/_abi.py are the enum of csrc/mrt_trace.h: same names, same values."""
+    from micro_raytracer_amd import _abi
+    src = open(os.path.join(ROOT, "micro_raytracer_amd", "csrc", "mrt_trace.h")).read()
+    body = re.search(r"enum\s*:\s*u32\s*\{(\s*F_BOX\b.*?)\};", src, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    header = {name: int(value) for name, value in re.findall(r"\b(F_[A-Z]+)\s*=\s*(\d+)u\b", body)}
+    python = {name: getattr(_abi, name) for name in dir(_abi) if re.fullmatch(r"F_[A-Z]+", name)}
+    assert len(header) == 12 and header == python, (header, python)

@@ -11,6 +11,7 @@ import pytest
 
 import vattr_ref as V
 from conftest import make_holder
+from micro_raytracer_amd._abi import F_ALL, F_VATTR
 
 f32 = np.float32
 
@@ -336,7 +337,7 @@ def test_plan_without_attributes_is_unchanged():
         attrs = (_abi.TriAttrs * len(render.scene.renderer))()
         ext.n_renderer, ext.attrs = len(render.scene.renderer), C.cast(attrs, C.POINTER(_abi.TriAttrs))
         assert _plan(L, holder, C.cast(C.byref(ext), C.c_void_p)) == base, name
-        assert not base["kernel_features"] & 512
+        assert not base["kernel_features"] & F_VATTR
 
 
 @pytest.mark.parametrize("n_tris", [967, 5120, 20480])
@@ -354,8 +355,8 @@ def test_plan_with_attributes_differs_in_kernel_features_only(monkeypatch, n_tri
         a, b = _lib.plan_launch(plain), _lib.plan_launch(smooth)
         kf_a, kf_b = a.pop("kernel_features"), b.pop("kernel_features")
         assert a == b, (kw, a, b)
-        assert kf_b & 512 and not kf_a & 512 and (kf_b & 15) == 15
-        assert (kf_b & ~(512 | 15)) == (kf_a & ~(512 | 15)), (kf_a, kf_b)         # same shape markers, same instance-BVH bit
+        assert kf_b & F_VATTR and not kf_a & F_VATTR and (kf_b & F_ALL) == F_ALL
+        assert (kf_b & ~(F_VATTR | F_ALL)) == (kf_a & ~(F_VATTR | F_ALL)), (kf_a, kf_b)         # same shape markers, same instance-BVH bit
 
 
 def test_packed_scene_without_attributes_is_the_same_bytes(probe):
@@ -365,10 +366,10 @@ def test_packed_scene_without_attributes_is_the_same_bytes(probe):
     render, smooth = make_holder(scenes.smooth_mesh_scene(res=(64, 48), uv=False))
     i0, b0 = V.x86_pack(probe, plain)
     i1, b1 = V.x86_pack(probe, smooth, with_ext=False)        # the same scene, its attributes not passed
-    assert i0 == i1 and np.array_equal(b0, b1) and i0["n_vattr_rows"] == 0 and not i0["features"] & 512
+    assert i0 == i1 and np.array_equal(b0, b1) and i0["n_vattr_rows"] == 0 and not i0["features"] & F_VATTR
     i2, b2 = V.x86_pack(probe, smooth)
     # with attributes: the table is appended behind everything else; of the old words only the renderer's flag and offset change
-    assert i2["features"] == i0["features"] | 512 and i2["n_vattr_rows"] == 967
+    assert i2["features"] == i0["features"] | F_VATTR and i2["n_vattr_rows"] == 967
     assert i2["off_vattr"] >= i0["blob_words"] - 3 and i2["blob_words"] == i2["off_vattr"] + 967 * VATTR_WORDS
     for key in ("lds_words", "lds_words_warm", "lds_words_hot", "off_rend"):
         assert i2[key] == i0[key]
