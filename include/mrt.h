@@ -192,7 +192,7 @@ typedef struct mrt_stats {
     double   img_ms;         /* HIP-event time of the kernels of the last mrt_img / mrt_img_ss (tone map + resize) */
     double   reduce_ms;      /* HIP-event time of reduce_chunks after the path-tracing kernel (0 when k_split == 1) */
     uint32_t kernel_features; /* which instantiation of the path-tracing kernel serves this context: its FEAT template argument
-                                 (csrc/mrt_trace.h F_* bits), i.e. pt_megakernel<scene_in_lds, block_threads, kernel_features> */
+                                 (csrc/mrt_scene.h F_* bits), i.e. pt_megakernel<scene_in_lds, block_threads, kernel_features> */
     uint32_t scene_in_lds;   /* 1: every workgroup stages the packed scene in LDS; 0: it is read through L2 */
 } mrt_stats;
 

@@ -17,7 +17,7 @@ KIND_IDS = {"sphere": KIND_SPHERE, "plane": KIND_PLANE, "box": KIND_BOX, "triang
 MRT_OK, MRT_ERR_ARG, MRT_ERR_SCENE, MRT_ERR_DEVICE, MRT_ERR_LIMIT, MRT_ERR_STATE = 0, -1, -2, -3, -4, -5
 TRACE_WORDS = 9          # MRT_TRACE_WORDS: words per ray of mrt_selftest_trace
 FLAG_COUNT_SEGMENTS, FLAG_NO_EVENT_TIMING, FLAG_DEFER, FLAG_NO_LOOKAHEAD = 1, 2, 4, 8
-# the F_* bits of csrc/mrt_trace.h, as mrt_stats.kernel_features and mrt_plan.kernel_features report them: scene features
+# the F_* bits of csrc/mrt_scene.h, as mrt_stats.kernel_features and mrt_plan.kernel_features report them: scene features
 # (F_ALL = the first four), the instance BVH, the launch-shape markers, then F_IDENT, F_VATTR, F_ENV
 F_BOX, F_TRI, F_MAPS, F_LIGHTS, F_ALL, F_BVH = 1, 2, 4, 8, 15, 16
 F_NOSTASH, F_COLD, F_DEEP, F_IDENT, F_VATTR, F_ENV = 32, 64, 128, 256, 512, 1024

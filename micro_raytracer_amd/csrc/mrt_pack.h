@@ -15,7 +15,7 @@ struct Packed {
     u32 nw = 0, nh = 0;
     u32 res_w = 0, res_h = 0;
     float gamma = 0, exp = 0;
-    u32 features = 0;            // F_* bits of mrt_trace.h the scene needs
+    u32 features = 0;            // F_* bits of mrt_scene.h the scene needs
     bool all_ident = false;      // every instance untransformed (TAG_IDENT): mrt_create adds F_IDENT to the features
     bool axis_scan = false;      // the scene has the AXIS table of mrt_scene.h (P.off_axis, P.axis_scan): all_ident, planes and spheres
                                  // only, every plane axis-aligned, every coordinate bounded

@@ -209,6 +209,47 @@ struct Params {
 };
 static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, axis_scan) + 4 == sizeof(Params), "Params has no tail padding");
 
+// Scene features a kernel instantiation is compiled for; the host picks the smallest set that covers the
+// scene, so e.g. a Cornell box of planes and spheres carries no octree walker, texture fetch or shadow-ray code.
+enum : u32 {
+    F_BOX = 1u,       // boxes or meshes present: rays need the patched reciprocal direction (src/rt.rs:303-316)
+    F_TRI = 2u,       // triangle / mesh renderers present
+    F_MAPS = 4u,      // some material has a texture map
+    F_LIGHTS = 8u,    // the scene has lights (shadow rays + direct term)
+    F_ALL = 15u,
+    F_BVH = 16u,      // many instances: a BVH over them replaces most of the linear scan (only built with F_ALL)
+    F_NOSTASH = 32u,  // launch-shape marker, not a scene feature: 1024-thread workgroup whose scene leaves no LDS for the lane stash
+    F_COLD = 64u,     // launch-shape marker: texels are read from global memory, not staged in LDS (mesh kernels: with a per-lane walk area)
+                      // (Params.lds_words_warm)
+    F_DEEP = 128u,    // with F_COLD, meshes beyond the LDS: triangles stay in global memory too (Params.lds_words_hot) and of the
+                      // (level-ordered) triangle-BVH table only the first Params.n_tbvh_hot nodes -- the top levels of every
+                      // tree -- are staged
+    F_IDENT = 256u,   // EVERY instance of the scene is untransformed (default `dir`: both matrices the identity as values): the
+                      // per-instance identity test of the tag and the transform's address are compiled out of the linear scan --
+                      // ~30 of ~220 cycles per instance on the Cornell box (8236 -> 8700 Msamples/s).  Exists for the plain
+                      // 256-thread kernels of planes / spheres / boxes with and without lights; rays whose shifted origin has a
+                      // zero, infinite or NaN component still take the reference's two mat-vecs (xf_vec)
+                      // AXIS SCAN (F_IDENT alone: planes and spheres, no lights, closest hit): a scene whose planes all lie along an
+                      // axis carries the AXIS table of mrt_scene.h (Params.axis_scan), and a query whose whole wavefront has every
+                      // direction component inside the division window and every origin component within kAxisMax scans it with
+                      // a second body (trace, "axis scan"): the three refined reciprocals of the direction once per ray, a plane
+                      // from the ONE component its normal selects.  Same bits; any other query, the shadow
+                      // query and every other kernel take the generic body
+    F_ENV = 1024u,    // the sky has an environment texture (mrt.h mrt_env): env_uv / env_color at the two miss sites of
+                      // render_pixel -- or the scene filters its textures: the bilinear lookups live in this
+                      // family only, and a scene without an environment (Params.off_env == 0) takes the constant sky.  Like F_VATTR it exists with the full feature set only, and always together with F_VATTR
+                      // (F_ALL | F_VATTR | F_ENV plus the shape markers and F_BVH)
+    F_VATTR = 512u    // some triangle / mesh renderer carries per-corner normals or UVs (mrt.h mrt_desc_ext):
+                      // the interpolation of hit_normal / hit_uv.  Exists with the full feature set only (F_ALL | F_VATTR plus the
+                      // shape markers and F_BVH)
+};
+constexpr u32 plain_feat(u32 feat) { return feat & ~(u32)F_IDENT; }
+// words of the packed scene a kernel instantiation stages in LDS
+MRT_HD u32 staged_words_for(const Params &P, u32 feat) { return (feat & F_DEEP) ? P.lds_words_hot : ((feat & F_COLD) ? P.lds_words_warm : P.lds_words); }
+// Mesh kernels that leave the cold tables out of LDS spend it on a per-lane WALK AREA (behind the lane stash), Params.walk_cap
+// entries per lane: the leaf queue of the binary walk (kLeafQueue entries), or (F_DEEP) node stack + leaf queue of the 4-wide walk.
+constexpr bool has_walk_area(u32 feat) { return (feat & F_TRI) && (feat & F_BOX) && (feat & F_COLD); }
+
 // Tile-list launches (adaptive sampling, mrt_execute_adaptive): only the n 8x8 wave tiles tiles[i] = ty * n_tx + tx are traced.
 // A kernel argument of its own (pt_megakernel_list), not a Params field: the ordinary launches keep their argument block.
 struct TileList {

@@ -483,3 +483,117 @@ def test_launch_plan_staging_levels_and_shapes(monkeypatch):
     monkeypatch.setenv("MRT_BLOCK_THREADS", "64")
     p = plan(scenes.cornell_box())
     assert (p["block_threads"], p["small_plain_grid"]) == (64, 0), p
+
+
+def _rejection_rows():
+    """(name, base scene, edit of the built holder, MRT_ERR_* code, fragment of the message) -- one row per rejection of pack_scene."""
+    from micro_raytracer_amd import _abi
+    ARG, SCENE, LIMIT = _abi.MRT_ERR_ARG, _abi.MRT_ERR_SCENE, _abi.MRT_ERR_LIMIT
+    fp = C.POINTER(C.c_float)
+
+    def rend(h, kind=None):                       # the first renderer (of that kind)
+        sc = h.desc.scene
+        return next(r for r in range(sc.n_renderer) if kind is None or sc.renderer[r].kind == kind)
+
+    def mat(h, **kw):
+        for k, v in kw.items():
+            setattr(h.desc.scene.renderer[0].mat, k, v)
+
+    def texture(h, w, ht, value):                 # the scene's only texture: w x ht texels of `value` (at least one is allocated)
+        dat = np.full(max(1, w * ht) * 3, value, np.float32)
+        t = (_abi.Texture * 1)()
+        t[0].w, t[0].h, t[0].dat = w, ht, dat.ctypes.data_as(fp)
+        h.keep += [dat, t]
+        h.desc.scene.textures, h.desc.scene.n_textures = C.cast(t, C.POINTER(_abi.Texture)), 1
+
+    def reserved(h, k, v):                        # an ext of its own where the scene has none
+        h.ext = h.ext or _abi.DescExt()
+        h.ext.reserved[k] = v
+
+    def env(h, w=3, ht=2, texels=None, null=False, bad=None, **kw):       # texels: how many are allocated (w x ht unless given)
+        e = _abi.Env()
+        a = np.ones(max(1, w * ht if texels is None else texels) * 3, np.float32)
+        if bad is not None:
+            a[bad] = -1.0
+        e.tex.w, e.tex.h, e.tex.dat = w, ht, None if null else a.ctypes.data_as(fp)
+        for k, v in kw.items():
+            setattr(e, k, v)
+        h.ext = h.ext or _abi.DescExt()
+        h.keep += [a, e]
+        h.ext.env = C.pointer(e)
+
+    def no_lights(h): h.desc.scene.n_light, h.desc.scene.light = 1, None
+    def one_more_attr(h): h.ext.n_renderer += 1
+    def ssaa(h): h.desc.frame.ssaa = 0.01
+    def huge(h): h.desc.frame.res_w = h.desc.frame.res_h = 65535
+    def bounce(h): h.desc.rt.bounce = 0x10000000
+    def kind(h): h.desc.scene.renderer[0].kind = 5
+    def no_inst(h): h.desc.scene.renderer[0].n_inst, h.desc.scene.renderer[0].inst = 1, None
+    def no_tris(h): h.desc.scene.renderer[rend(h, 4)].tris = None
+    def map_on_mesh(h): texture(h, 2, 2, 0.5); h.desc.scene.renderer[rend(h, 4)].mat.tex = 0
+
+    def attrs_on_sphere(h):
+        h.ext.attrs[next(r for r in range(h.desc.scene.n_renderer) if h.desc.scene.renderer[r].kind < 3)].vn = h.ext.attrs[rend(h, 4)].vn
+
+    def nan_uv(h): h.ext.attrs[rend(h, 4)].uv[7] = float("nan")
+
+    def tiny_mesh(h):                             # every coordinate +-2^-149: the octree's boxes round to a point at the origin
+        t = np.full(9, 1e-45, np.float32) * np.array([1, 1, 1, -1, 1, 1, 1, -1, 1], np.float32)
+        h.keep.append(t)
+        o = h.desc.scene.renderer[rend(h, 4)]
+        o.tris, o.n_tris = t.ctypes.data_as(fp), 1
+
+    def light_kind(h): h.desc.scene.light[0].kind = 2
+
+    return [
+        ("null array", "default", no_lights, ARG, "null array with non-zero count"),
+        ("attrs count", "smooth", one_more_attr, SCENE, "attributes for "),
+        ("reserved[1]", "cornell", lambda h: reserved(h, 1, 1), ARG, "ext.reserved[1] is 1, not 0"),
+        ("tex_filter", "cornell", lambda h: reserved(h, 0, 5), SCENE, "ext.reserved[0] (tex_filter) 5 unknown"),
+        ("empty frame", "cornell", ssaa, SCENE, "empty frame (res * ssaa truncates to 0)"),
+        ("2^30 pixels", "cornell", huge, LIMIT, "more than 2^30 supersampled pixels"),
+        ("bounce", "cornell", bounce, LIMIT, "bounce too large"),
+        ("env 0 texels", "cornell", lambda h: env(h, w=0), SCENE, "env.tex: 0x2 texels"),
+        ("env null dat", "cornell", lambda h: env(h, null=True), SCENE, "env.tex.dat is null"),
+        ("env mapping", "cornell", lambda h: env(h, mapping=2), SCENE, "env.mapping 2 unknown"),
+        ("env rot", "cornell", lambda h: env(h, rot=float("inf")), SCENE, "env.rot is not finite"),
+        ("env filter", "cornell", lambda h: env(h, filter=2), SCENE, "env.filter 2 unknown"),
+        ("env 2^25", "cornell", lambda h: env(h, w=8192, ht=4097, texels=1), LIMIT, "env.tex: 8192x4097 is more than 2^25 texels"),     # (never read)
+        ("env texel", "cornell", lambda h: env(h, bad=4), SCENE, "env.tex: texel (1, 0) is negative or not finite"),
+        ("texture size", "cornell", lambda h: texture(h, 0, 4, 0.5), SCENE, "texture 0: 0x4 texels"),
+        ("kind", "cornell", kind, SCENE, "renderer 0: unknown kind 5"),
+        ("null inst", "cornell", no_inst, ARG, "null instance array"),
+        ("null tris", "mesh", no_tris, ARG, "null triangle array"),
+        ("map index", "cornell", lambda h: mat(h, rmap=99), SCENE, "renderer 0: map 1 index out of range"),
+        ("map on mesh", "mesh", map_on_mesh, SCENE, "texture maps on a triangle/mesh hit todo!()"),
+        ("attrs on sphere", "smooth", attrs_on_sphere, SCENE, "per-corner attributes on a renderer that is neither a triangle nor a mesh"),
+        ("uv", "smooth", nan_uv, SCENE, "non-finite uv"),
+        ("emit", "cornell", lambda h: mat(h, emit=1.5), SCENE, "renderer 0: emit 1.5 outside [0,1]"),
+        ("opacity", "cornell", lambda h: mat(h, opacity=1.25), SCENE, "renderer 0: opacity 1.25 > 1"),
+        ("emap texel", "cornell", lambda h: texture(h, 2, 2, 2.0) or mat(h, emap=0), SCENE, "emap texel outside [0,1]"),
+        ("omap texel", "cornell", lambda h: texture(h, 2, 2, 1.5) or mat(h, omap=0), SCENE, "omap texel > 1"),
+        ("empty octree", "mesh", tiny_mesh, SCENE, "mesh octree is empty"),
+        ("light kind", "default", light_kind, SCENE, "unknown light kind"),
+    ]
+
+
+def test_every_rejection_of_the_packer_by_code_and_message():
+    """One row per rejection path of pack_scene (csrc/mrt_pack.cpp) that a mrt_render_desc and a mrt_desc_ext can reach, through
+    mrt_plan_launch (host only): the MRT_ERR_* code and a fragment of the message, both as the packer gave them before its stages
+    were cut apart.  28 of the 32 paths; left out are the null description (mrt_plan_launch answers that itself), more than
+    2^28 / XF_WORDS distinct instance directions ("too many distinct instance directions"), 2^24 nodes of 4-wide triangle BVHs
+    ("triangle BVHs too large") and a packed scene beyond 32-bit texel offsets ("env.tex: the packed scene is too large"),
+    whose inputs are gigabytes.  Every base scene plans without an error when it is left alone."""
+    from micro_raytracer_amd import MrtError, _lib, scenes
+    bases = {"cornell": scenes.cornell_box(res=(16, 16)), "default": scenes.default_scene(res=(16, 16)),
+             "mesh": scenes.mesh_scene(res=(16, 12), n_tris=300), "smooth": scenes.smooth_mesh_scene(res=(16, 12), n_tris=300)}
+    for d in bases.values():
+        _lib.plan_launch(make_holder(d)[1])
+    rows = _rejection_rows()
+    assert len(rows) == 28 and len({r[4] for r in rows}) == 28
+    for name, base, edit, code, fragment in rows:
+        h = make_holder(bases[base])[1]
+        edit(h)
+        with pytest.raises(MrtError) as e:
+            _lib.plan_launch(h)
+        assert e.value.code == code and fragment in e.value.msg, (name, e.value.code, e.value.msg)

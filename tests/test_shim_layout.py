@@ -129,9 +129,9 @@ def test_extern_block_matches_header_and_library():
 
 
 def test_feature_bit_names_match_the_kernel_header():
-    """The F_* constants of micro_raytracer_amd/_abi.py are the enum of csrc/mrt_trace.h: same names, same values."""
+    """The F_* constants of micro_raytracer_amd/_abi.py are the enum of csrc/mrt_scene.h: same names, same values."""
     from micro_raytracer_amd import _abi
-    src = open(os.path.join(ROOT, "micro_raytracer_amd", "csrc", "mrt_trace.h")).read()
+    src = open(os.path.join(ROOT, "micro_raytracer_amd", "csrc", "mrt_scene.h")).read()
     body = re.search(r"enum\s*:\s*u32\s*\{(\s*F_BOX\b.*?)\};", src, re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)
     header = {name: int(value) for name, value in re.findall(r"\b(F_[A-Z]+)\s*=\s*(\d+)u\b", body)}
