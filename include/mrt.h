@@ -453,6 +453,13 @@ int mrt_selftest_math(int device, int op, const float *a, const float *b, float 
 #define MRT_TRACE_WORDS 9u
 int mrt_selftest_trace(mrt_ctx *ctx, size_t n, const float *orig /*[n][3]*/, const float *dir /*[n][3]*/, uint32_t *out /*[n][MRT_TRACE_WORDS]*/);
 
+/* Test hook, host only (no device needed, like mrt_plan_launch): the list of the path-tracing kernel's compiled instantiations, one
+ * row per (workgroup size, scene staged in LDS or read through L2, FEAT template argument = mrt_stats.kernel_features), expanded
+ * from the same lists the launchers dispatch over; every row exists once as the full-frame kernel and once as the tile-list kernel
+ * of mrt_execute_adaptive.  Writes the first min(count, cap) rows to threads[], scene_in_lds[] (0 / 1) and feat[] (each may be NULL)
+ * and returns the count, whatever cap is. */
+uint32_t mrt_selftest_instantiations(uint32_t *threads, uint32_t *scene_in_lds, uint32_t *feat, uint32_t cap);
+
 /* Test hook: compare, on the device, the fast correctly rounded cores of the math contract (sqrt, 1/x, a/b and the
  * 1/sqrt(m) of Vec3f::norm, src/lin.rs:60-66) with the compiler's full IEEE expansions, on `count` inputs generated
  * from the indices first .. first+count-1: op 0 sqrt and op 1 recip take the index as the f32 bit pattern (first = 0,

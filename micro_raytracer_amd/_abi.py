@@ -19,6 +19,7 @@ TRACE_WORDS = 9          # MRT_TRACE_WORDS: words per ray of mrt_selftest_trace
 FLAG_COUNT_SEGMENTS, FLAG_NO_EVENT_TIMING, FLAG_DEFER, FLAG_NO_LOOKAHEAD = 1, 2, 4, 8
 # the F_* bits of csrc/mrt_scene.h, as mrt_stats.kernel_features and mrt_plan.kernel_features report them: scene features
 # (F_ALL = the first four), the instance BVH, the launch-shape markers, then F_IDENT, F_VATTR, F_ENV
+# (_lib.selftest_instantiations() lists the combinations that exist as kernels: mrt_selftest_instantiations)
 F_BOX, F_TRI, F_MAPS, F_LIGHTS, F_ALL, F_BVH = 1, 2, 4, 8, 15, 16
 F_NOSTASH, F_COLD, F_DEEP, F_IDENT, F_VATTR, F_ENV = 32, 64, 128, 256, 512, 1024
 

@@ -18,7 +18,7 @@ SYMBOLS = (
     "mrt_execute_adaptive", "mrt_sample_counts", "mrt_adapt_half",
     "mrt_aov", "mrt_denoise", "mrt_img_denoised",
     "mrt_create_ext", "mrt_plan_launch_ext",
-    "mrt_selftest_trace",
+    "mrt_selftest_trace", "mrt_selftest_instantiations",
 )
 
 
@@ -85,6 +85,8 @@ def lib():
     L.mrt_selftest_math.argtypes = [C.c_int, C.c_int, f32p, f32p, f32p, C.c_size_t]
     L.mrt_selftest_sweep.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, u32, C.POINTER(C.c_uint64), f32p]
     L.mrt_selftest_trace.argtypes = [vp, C.c_size_t, f32p, f32p, u32p]
+    L.mrt_selftest_instantiations.argtypes = [u32p, u32p, u32p, u32]
+    L.mrt_selftest_instantiations.restype = u32
     _LIB = L
     return L
 
@@ -148,6 +150,19 @@ def selftest_trace(sampler_or_ctx, orig, dir):
     check(lib().mrt_selftest_trace(ctx, n, orig.ctypes.data_as(f32p), dir.ctypes.data_as(f32p), w.ctypes.data_as(C.POINTER(C.c_uint32))))
     return {"hit": w[:, 0] != 0, "any": w[:, 1] != 0, "renderer": w[:, 2].astype(np.int32), "instance": w[:, 3].astype(np.int32),
             "t0": w[:, 4].view(np.float32), "t1": w[:, 5].view(np.float32), "normal": w[:, 6:9].view(np.float32), "words": w}
+
+
+def selftest_instantiations():
+    """mrt_selftest_instantiations: the compiled instantiations of the path-tracing kernel as a list of
+    (block_threads, scene_in_lds, kernel_features) in the order of the launchers' lists.  Host only."""
+    import numpy as np
+    L = lib()
+    n = L.mrt_selftest_instantiations(None, None, None, 0)
+    t, l, f = (np.zeros(n, np.uint32) for _ in range(3))
+    p = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+    if L.mrt_selftest_instantiations(p(t), p(l), p(f), n) != n:
+        raise MrtError(_abi.MRT_ERR_STATE, "selftest_instantiations: the count changed between two calls")
+    return [(int(a), bool(b), int(c)) for a, b, c in zip(t, l, f)]
 
 
 def save_image(path, rgb8):

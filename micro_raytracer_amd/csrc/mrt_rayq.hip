@@ -109,3 +109,26 @@ bool rayq_has(bool scene_in_lds, u32 inst)
 }
 
 }  // namespace mrt
+
+// ---- mrt_selftest_instantiations (include/mrt.h): host only, no device ----
+// The rows are the expansion of the MRT_SHAPES_* lists of mrt_megakernel.h, the text launch_pt_inst (mrt_pt_kernel.h) dispatches
+// over: one row per (block_threads, scene_in_lds, FEAT) that exists as pt_megakernel and pt_megakernel_list.
+extern "C" uint32_t mrt_selftest_instantiations(uint32_t *threads, uint32_t *scene_in_lds, uint32_t *feat, uint32_t cap)
+{
+    using namespace mrt;
+    uint32_t n = 0;
+    auto row = [&](u32 t, u32 l, u32 f) {
+        if (n < cap) {
+            if (threads) threads[n] = t;
+            if (scene_in_lds) scene_in_lds[n] = l;
+            if (feat) feat[n] = f;
+        }
+        ++n;
+    };
+#define MRT_CASE(T, F) row((T), 1u, (u32)(F));
+#define MRT_CASE_L2(F) row(256u, 0u, (u32)(F));
+    MRT_SHAPES_64 MRT_SHAPES_256 MRT_SHAPES_512 MRT_SHAPES_1024 MRT_SHAPES_L2
+#undef MRT_CASE
+#undef MRT_CASE_L2
+    return n;
+}

@@ -179,29 +179,32 @@ def test_persistent_workgroups_change_no_bit(monkeypatch):
 def test_every_launch_shape_gives_the_same_bits(monkeypatch):
     """The launch shape (64 / 256 / 512 / 1024 threads, scene in LDS or read through L2, persistent or not) is a pure
     scheduling choice: the same scene must give the same accumulator bits through every kernel instantiation."""
-    from micro_raytracer_amd import scenes
+    from micro_raytracer_amd import _lib, scenes
     for desc in (scenes.cornell_box(res=(96, 64), sample=32), scenes.kitchen_sink(res=(80, 48), sample=16),
                  scenes.minecraft_like(res=(64, 40), ssaa=1, sample=16)):
         render, _ = make_holder(desc)
         spp = render.rt.sample
         ref = None
-        seen = set()
+        seen, planned = set(), set()
         for threads, l2 in ((None, False), ("64", False), ("256", False), ("512", False), ("1024", False), (None, True)):
             if threads:
                 monkeypatch.setenv("MRT_BLOCK_THREADS", threads)
             if l2:
                 monkeypatch.setenv("MRT_SCENE_IN_L2", "1")
+            pl = _lib.plan_launch(render)                 # (host only: what a context created under these switches launches)
+            planned.add((pl["block_threads"], pl["staging"] != "none", pl["kernel_features"]))
             s = _gpu_render(render, spp)
             got, _ = s.accum()
             st = s.stats()
-            seen.add((st["block_threads"], st["lds_bytes"] > 0))
+            seen.add((st["block_threads"], st["scene_in_lds"] != 0, st["kernel_features"]))
             s.close()
             monkeypatch.delenv("MRT_BLOCK_THREADS", raising=False)
             monkeypatch.delenv("MRT_SCENE_IN_L2", raising=False)
             if ref is None:
                 ref = got
             assert np.array_equal(ref.view(np.uint32), got.view(np.uint32)), (threads, l2)
-        assert len(seen) >= 3          # the shapes really differed (big scenes refuse the small workgroups)
+        # exactly the instantiations plan_launch predicts, and the shapes really differed (big scenes refuse the small workgroups)
+        assert seen == planned and len({(t, l) for t, l, _ in seen}) >= 3, (seen, planned)
 
 
 def test_every_staging_level_gives_the_same_bits(monkeypatch):
@@ -209,7 +212,7 @@ def test_every_staging_level_gives_the_same_bits(monkeypatch):
     tables and texels read from global memory; the mesh kernels queue every leaf of a closest-hit walk), the deep level (the
     triangle-BVH table in level order, only its first nodes staged, triangles in global memory), nothing (all through L2).
     Every level must give the same accumulator bits, for every workgroup size it admits."""
-    from micro_raytracer_amd import scenes
+    from micro_raytracer_amd import _lib, scenes
     for desc in (scenes.kitchen_sink(res=(80, 48), sample=16), scenes.mesh_scene(res=(96, 54), sample=8, n_tris=600),
                  scenes.minecraft_like(res=(64, 40), ssaa=1, sample=8)):
         render, _ = make_holder(desc)
@@ -220,7 +223,7 @@ def test_every_staging_level_gives_the_same_bits(monkeypatch):
         ref = base.accum()[0]
         assert base.stats()["kernel_features"] & F_COLD == 0
         monkeypatch.delenv("MRT_COLD")
-        seen = set()
+        seen, planned = set(), set()
         levels = [{"MRT_COLD": "1"}] + ([{"MRT_DEEP_NODES": "3"}, {"MRT_DEEP_NODES": "40"}, {"MRT_DEEP_NODES": "100000"}] if has_mesh else [])
         for env in levels:
             for threads in (None, "256", "512", "1024"):
@@ -228,17 +231,20 @@ def test_every_staging_level_gives_the_same_bits(monkeypatch):
                     monkeypatch.setenv(k, v)
                 if threads:
                     monkeypatch.setenv("MRT_BLOCK_THREADS", threads)
+                pl = _lib.plan_launch(render)             # (host only: what a context created under these switches launches)
+                planned.add((pl["kernel_features"], pl["block_threads"]))
                 s = _gpu_render(render, spp)
                 got = s.accum()[0]
                 st = s.stats()
-                seen.add((st["kernel_features"] & (F_COLD | F_DEEP), st["block_threads"]))
+                seen.add((st["kernel_features"], st["block_threads"]))
                 s.close()
                 for k in list(env) + ["MRT_BLOCK_THREADS"]:
                     monkeypatch.delenv(k, raising=False)
                 assert st["kernel_features"] & F_COLD, (env, threads, st)
                 assert bool(st["kernel_features"] & F_DEEP) == ("MRT_DEEP_NODES" in env), (env, st)
                 assert np.array_equal(ref.view(np.uint32), got.view(np.uint32)), (env, threads)
-        assert len(seen) >= (6 if has_mesh else 3), seen
+        # exactly the instantiations plan_launch predicts, in as many (level, shape) pairs as before
+        assert seen == planned and len({(f & (F_COLD | F_DEEP), t) for f, t in seen}) >= (6 if has_mesh else 3), (seen, planned)
 
 
 def test_shards_reassemble_to_whole_frame():
