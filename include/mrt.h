@@ -433,6 +433,47 @@ typedef struct mrt_desc_ext {
 mrt_ctx *mrt_create_ext(const mrt_render_desc *desc, const mrt_opts *opts, const mrt_desc_ext *ext);
 int mrt_plan_launch_ext(const mrt_render_desc *desc, const mrt_desc_ext *ext, mrt_plan *out);
 
+/* ---- radiance along caller-supplied rays: custom cameras, probes, baking ----
+ * mrt_radiance path-traces ray i (origin orig[i], direction dir[i]) n_samples times, exactly as a frame's pixel is sampled, but
+ * for the primary ray: it is traced as given -- no shift of the origin, no normalisation (the shading assumes unit length) -- and
+ * the two lens draws are not taken; every later draw sits at its usual slot.  key[i] stands where the frame's pixel index
+ * y * nw + x stands in the hash key (pix_key = mix32 of key_i + seed_lo, xor seed_hi), sample s of the ray has the path key of
+ * sample s of that pixel.  rgb[i] receives the SUM of the samples in the canonical order: aligned chunks of 16 global sample
+ * indices, each summed from 0, the chunk sums added in chunk order to 0.  With sample_base == 0, key == NULL and the rays of
+ * mrt_camera_rays on a scene with aprt == 0 that is, bit for bit, the accumulator of a fresh context after an execute of
+ * n_samples.  A primary miss contributes the raw sky colour (or the environment's texel), as in a frame.
+ * The call observes and changes nothing of the context: accumulator, counts, samples booked under MRT_FLAG_DEFER, the adaptive
+ * state and cached AOVs stay as they are.  Ray i is thread i of 256-thread workgroups (lane i % 64 of wavefront i / 64).  The
+ * kernel carries the full feature set the scene-through-L2 kernels carry; it stages the scene in LDS when the context stages
+ * the whole scene and that takes at most a quarter of the LDS, and reads it through L2 otherwise; info says what ran.
+ * A sharded context serves the rays it is given (a rank passes its slice of a batch and the keys of that slice).
+ * MRT_ERR_ARG: a null pointer (key may be NULL), n == 0 or n >= 2^30, n_samples == 0, sample_base + n_samples > 2^32 - 1, an
+ * unknown flag, a non-zero reserved word; MRT_ERR_STATE: a multi-device context (n_devices > 1). */
+#define MRT_RAYS_DEVICE 1u     /* orig, dir, key and rgb are device pointers on the context's device */
+typedef struct mrt_rays {
+    size_t n;                  /* 1 .. 2^30 - 1 */
+    const float *orig;         /* [n][3] */
+    const float *dir;          /* [n][3] */
+    const uint32_t *key;       /* [n] or NULL: ray i takes key i */
+    uint32_t sample_base, n_samples;   /* global sample indices [sample_base, sample_base + n_samples) */
+    uint32_t flags;            /* MRT_RAYS_* */
+    uint32_t reserved[3];      /* 0 */
+} mrt_rays;
+typedef struct mrt_rays_info {
+    double kernel_ms;          /* HIP-event time of the kernel */
+    uint64_t samples;          /* n * n_samples */
+    uint64_t segments;         /* path segments traced */
+    uint32_t kernel_features;  /* FEAT of the kernel that ran */
+    uint32_t scene_in_lds;     /* 1: scene staged in LDS, 0: read through L2 */
+    uint32_t lds_bytes;        /* LDS per workgroup */
+    uint32_t reserved;
+} mrt_rays_info;
+int mrt_radiance(mrt_ctx *ctx, const mrt_rays *r, float *rgb /*[n][3]*/, mrt_rays_info *info /*may be NULL*/);
+
+/* The lens-centre camera ray of every supersampled pixel, row-major: the ray of the depth AOV and, when aprt == 0, of every sample
+ * of the pixel.  Either output may be NULL.  Host pointers.  MRT_ERR_STATE: a multi-device context. */
+int mrt_camera_rays(mrt_ctx *ctx, float *orig /*[nh][nw][3]*/, float *dir /*[nh][nw][3]*/);
+
 /* Test hook: run one device math-contract function elementwise on the GPU.
  * op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 pow(a,b), 5 1/a, 6 sqrt(a), 7 a/b, 12 the first component of norm(a, b, 0.25);
  * 16 the longitude 0.5 + 0.5 atan2(a, -b) / pi and 17 the latitude acos(clamp(a, -1, 1)) / pi of the texture lookups, 18 / 19 the

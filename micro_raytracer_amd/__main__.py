@@ -5,7 +5,7 @@
                                   [--denoise [--denoise-passes N] [--denoise-mode atrous|variance] [--denoise-sigma-var S]
                                    [--denoise-firefly F]] [--aov PREFIX]
                                   [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS] [--sky-filter nearest|bilinear]
-                                  [--tex-filter nearest|bilinear]
+                                  [--tex-filter nearest|bilinear] [--camera pinhole|equirect [--pano-yaw TURNS]]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
 --adaptive renders with a per-tile noise threshold instead (Sampler.execute_adaptive), --sample being the cap.
@@ -17,6 +17,8 @@ render, so --sample must be a multiple of 32.  --denoise-sigma-var and --denoise
 --sky-tex / --sky-map / --sky-rot override the description's environment texture (an image file or a Radiance .hdr), its
 mapping and its rotation about +z; --sky-filter / --tex-filter choose the filter of the environment texture and of the material
 textures (nearest texel, or bilinear).
+--camera equirect renders the frame's supersampled grid as a full lat-long panorama from cam.pos through Sampler.radiance
+(cameras.render_equirect), turned by --pano-yaw; cam.dir, fov and aprt are ignored.
 """
 import argparse
 import sys
@@ -24,7 +26,7 @@ import time
 
 import numpy as np
 
-from . import _abi, _lib, load_render
+from . import _abi, _lib, cameras, load_render
 from .sampler import Sampler
 from .scene import Texture
 
@@ -81,7 +83,17 @@ def main(argv=None):
     ap.add_argument("--sky-rot", type=float, metavar="TURNS", help="rotation of the environment about +z, in turns")
     ap.add_argument("--sky-filter", choices=("nearest", "bilinear"), help="filter of the environment texture")
     ap.add_argument("--tex-filter", choices=("nearest", "bilinear"), help="filter of the material textures")
+    ap.add_argument("--camera", choices=("pinhole", "equirect"), default="pinhole",
+                    help="equirect: the frame's supersampled grid as a 360 x 180 degree panorama from cam.pos; the description's "
+                         "cam.dir, fov and aprt are ignored")
+    ap.add_argument("--pano-yaw", type=float, metavar="TURNS", help="--camera equirect: the centre column looks along +y turned by TURNS")
     a = ap.parse_args(argv)
+    if a.camera == "equirect":
+        for name, on in (("--adaptive", a.adaptive is not None), ("--denoise", a.denoise), ("--aov", a.aov is not None), ("--update", a.update)):
+            if on:
+                ap.error(f"--camera equirect cannot be combined with {name}")
+    elif a.pano_yaw is not None:
+        ap.error("--pano-yaw needs --camera equirect")
     if not 0 <= a.denoise_passes <= 8:
         ap.error(f"--denoise-passes {a.denoise_passes} is not in 0..8")
     variance = a.denoise and a.denoise_mode == "variance"
@@ -122,7 +134,9 @@ def main(argv=None):
         render.scene.tex_filter = a.tex_filter
     s = Sampler(seed=a.seed)
     t0 = time.perf_counter()
-    if a.adaptive is not None:
+    if a.camera == "equirect":
+        cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0)
+    elif a.adaptive is not None:
         info = s.execute_adaptive(render, a.adaptive, min_samples=a.min_sample, max_samples=render.rt.sample, step=a.step)
         uniform = s.nw * s.nh * render.rt.sample
         print(f"adaptive: {info['samples']} samples traced of {uniform} uniform ({info['samples'] / uniform:.1%}), "

@@ -86,6 +86,19 @@ class Stats(C.Structure):
                 ("reduce_ms", C.c_double), ("kernel_features", C.c_uint32), ("scene_in_lds", C.c_uint32)]
 
 
+RAYS_DEVICE = 1          # MRT_RAYS_DEVICE: the rays, keys and sums of mrt_radiance are device pointers
+
+
+class Rays(C.Structure):
+    _fields_ = [("n", C.c_size_t), ("orig", C.c_void_p), ("dir", C.c_void_p), ("key", C.c_void_p),
+                ("sample_base", C.c_uint32), ("n_samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class RaysInfo(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("samples", C.c_uint64), ("segments", C.c_uint64), ("kernel_features", C.c_uint32),
+                ("scene_in_lds", C.c_uint32), ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Plan(C.Structure):
     _fields_ = [("staging", C.c_uint32), ("block_threads", C.c_uint32), ("lds_bytes", C.c_uint32), ("staged_bytes", C.c_uint32),
                 ("scene_bytes", C.c_uint32), ("kernel_features", C.c_uint32), ("tbvh_nodes", C.c_uint32), ("tbvh_hot_nodes", C.c_uint32),

@@ -19,6 +19,7 @@ SYMBOLS = (
     "mrt_aov", "mrt_denoise", "mrt_img_denoised",
     "mrt_create_ext", "mrt_plan_launch_ext",
     "mrt_selftest_trace", "mrt_selftest_instantiations",
+    "mrt_radiance", "mrt_camera_rays",
 )
 
 
@@ -86,6 +87,8 @@ def lib():
     L.mrt_selftest_sweep.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, u32, C.POINTER(C.c_uint64), f32p]
     L.mrt_selftest_trace.argtypes = [vp, C.c_size_t, f32p, f32p, u32p]
     L.mrt_selftest_instantiations.argtypes = [u32p, u32p, u32p, u32]
+    L.mrt_radiance.argtypes = [vp, C.POINTER(_abi.Rays), vp, C.POINTER(_abi.RaysInfo)]
+    L.mrt_camera_rays.argtypes = [vp, f32p, f32p]
     L.mrt_selftest_instantiations.restype = u32
     _LIB = L
     return L

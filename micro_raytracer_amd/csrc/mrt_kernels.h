@@ -35,6 +35,11 @@ hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw
 // out [n][MRT_TRACE_WORDS].  rayq_has: that instantiation exists
 hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream);
 bool rayq_has(bool scene_in_lds, u32 inst);
+// mrt_rays.hip: mrt_radiance's kernel pt_rays<scene_in_lds, inst> on n rays (inst: pt_instantiation(256, false, features)), adding
+// into P.accum [n][3]; the LDS bytes a workgroup of it takes; mrt_camera_rays' kernel (either output may be null)
+hipError_t launch_rays(const Params &P, bool scene_in_lds, u32 inst, u32 n, const float *orig, const float *dir, const u32 *key, hipStream_t stream);
+size_t rays_lds_bytes(const Params &P, bool scene_in_lds, u32 inst);
+hipError_t launch_camera_rays(const Params &P, float *orig, float *dir, hipStream_t stream);
 hipError_t launch_math_selftest(int op, const float *a, const float *b, float *out, size_t n, hipStream_t stream);
 // ops 16..19 of mrt_selftest_math, in the test hook's translation unit (mrt_rayq.hip)
 hipError_t launch_math_selftest_ext(int op, const float *a, const float *b, float *out, size_t n, hipStream_t stream);

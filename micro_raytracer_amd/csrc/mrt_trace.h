@@ -1585,15 +1585,28 @@ struct LaneJob {
                            // written in place); partial[chunk * partial_stride + word ..] receives chunk sums otherwise
 };
 
+// Where a path's primary ray comes from (render_pixel's last template argument).  CameraRays: the reference's camera -- the
+// pixel's focus point in the stash, a lens position per sample, the camera matrices at the shared normalisation.  SuppliedRay
+// (mrt_radiance, mrt_rays.h): every sample of the lane starts on the ray (o, d) as given -- no shift of the origin, no
+// normalisation, no lens draws -- and `key` stands where the pixel index stands in the hash key; x and y are not read.
+struct CameraRays { static constexpr bool supplied = false; };
+struct SuppliedRay {
+    static constexpr bool supplied = true;
+    V3 o, d;
+    u32 key;
+};
+
 // All samples of one supersampled pixel: Sampler::execute's per-pixel body, n_samples times
 // (src/sampler.rs:45-70 calling RayTracer::iter / reduce_light, src/rt.rs:937-994, whose iterator
 // is RaytraceIterator::next, src/rt.rs:1014-1066).
-template <u32 FEAT, class Stash>
-MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &job, u32 &segments, unsigned long long *ticks = nullptr)
+template <u32 FEAT, class Stash, class Prim = CameraRays>
+MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &job, u32 &segments, unsigned long long *ticks = nullptr,
+                         const Prim &prim = Prim())
 {
     MRT_TICK_DECL;
     const Params &P = *S.P;
-    const u32 pixel = y * P.nw + x;
+    u32 pixel;
+    if constexpr (Prim::supplied) pixel = prim.key; else pixel = y * P.nw + x;
     const u32 pix_key = mix32(pixel + P.seed_lo) ^ P.seed_hi;      // path_key = mix32(pix_key + sample * kGold)
     const V3 sky_init = v3(P.sky_init[0], P.sky_init[1], P.sky_init[2]);
     const u32 s_base = P.sample_base, s_stop = P.sample_base + P.n_samples;
@@ -1603,7 +1616,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
     // goes to a plane of its own -- plane j holds sample s_base + j -- and the accumulator is not touched
     const bool planes1 = P.to_planes != 0u;
     const bool direct = P.k_split == 1u && !planes1;
-    st_put3(st, ST_FOCUS, pixel_focus(P, (float)x, (float)y));
+    if constexpr (!Prim::supplied) st_put3(st, ST_FOCUS, pixel_focus(P, (float)x, (float)y));
 
     // chunk bookkeeping and the pixel's hash key are only needed when a path starts or a chunk ends: stashed too
     st.put(ST_PIXKEY, u2f(pix_key));
@@ -1636,7 +1649,8 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
     if (alive) {                                 // first sample of this lane: every lane of the wavefront is here
         pk = mix32(pix_key + s * kGold);
         if constexpr (kHit) st.put(ST_PK, u2f(pk));
-        camera_ray(P, S.F + P.off_cam, st_get3(st, ST_FOCUS), pk, o, d);
+        if constexpr (Prim::supplied) { o = prim.o; d = prim.d; }
+        else camera_ray(P, S.F + P.off_cam, st_get3(st, ST_FOCUS), pk, o, d);
     }
 
     // ONE flat loop: an iteration traces one segment; a lane whose path ends draws its next sample's lens position in
@@ -1811,8 +1825,10 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
                 MRT_PROBE(PH_REGEN);
                 pk = mix32(f2u(st.get(ST_PIXKEY)) + s * kGold);
                 if constexpr (kHit) st.put(ST_PK, u2f(pk));
-                base = lens_pos(P, pk);
-                X = sub(st_get3(st, ST_FOCUS), base);               // new_dir before .norm()
+                if constexpr (!Prim::supplied) {
+                    base = lens_pos(P, pk);
+                    X = sub(st_get3(st, ST_FOCUS), base);           // new_dir before .norm()
+                }
                 setT(v3(1.0f, 1.0f, 1.0f)); setL(v3(0.0f, 0.0f, 0.0f));
                 pwr = 1.0f; b = 0;
                 from_camera = true;
@@ -1823,6 +1839,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
         if (from_camera && !(P.cam_ident && nzfin3(nd))) nd = m3mul(S.F + P.off_cam + 9, m3mul(S.F + P.off_cam, nd));   // rot_y * (look * new_dir), src/rt.rs:930
         o = add(base, muls(nd, kE));
         d = nd;
+        if constexpr (Prim::supplied) { if (from_camera) { o = prim.o; d = prim.d; } }      // the supplied ray again, as given
     }
     segments = seg;
     (void)ticks;

@@ -253,6 +253,66 @@ class Sampler:
             info["mode"] = int(di.reserved[0])
         return out
 
+    # -- radiance along caller-supplied rays (mrt_radiance) --------------------
+    def camera_rays(self, render: Render):
+        """(orig, dir), float32 [nh][nw][3]: the lens-centre camera ray of every supersampled pixel (mrt_camera_rays) -- with
+        aprt == 0 the ray of every sample of the pixel."""
+        self._ensure(render)
+        o, d = (np.empty((self.nh, self.nw, 3), np.float32) for _ in range(2))
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.lib().mrt_camera_rays(self._ctx, o.ctypes.data_as(fp), d.ctypes.data_as(fp)))
+        return o, d
+
+    def radiance(self, render: Render, orig, dir, n_samples: int, *, sample_base: int = 0, key=None, info=None):
+        """Path-trace caller-supplied rays (mrt_radiance): orig and dir of shape [..., 3] -> the f32 SUM of samples
+        [sample_base, sample_base + n_samples) of every ray in the canonical order, in the rays' shape.  Rays are traced as given
+        (no shift of the origin, no normalisation).  key (uint32, the rays' shape without the 3; default: the ray's flat index)
+        stands where a frame's pixel index stands in the random numbers.  Numpy arrays go through the host; torch tensors on the
+        context's device are read and written in place on the device and a tensor comes back.  info: a dict that receives
+        mrt_rays_info.  Nothing of the context changes."""
+        self._ensure(render)
+        r = _abi.Rays()
+        r.sample_base, r.n_samples = int(sample_base), int(n_samples)
+        if type(orig).__module__.split(".")[0] == "torch":
+            import torch
+            if not (orig.is_cuda and getattr(dir, "is_cuda", False)) or (key is not None and not getattr(key, "is_cuda", False)):
+                raise ValueError("radiance: orig, dir and key are all tensors on the context's device, or all host arrays")
+            if orig.shape != dir.shape or orig.shape[-1] != 3:
+                raise ValueError("radiance: orig and dir are [..., 3]")
+            o, d = orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous()
+            out = torch.empty_like(o)
+            keep = (o, d, out)
+            r.n, r.orig, r.dir, r.flags = o.numel() // 3, o.data_ptr(), d.data_ptr(), _abi.RAYS_DEVICE
+            if key is not None:
+                words = (torch.int32, getattr(torch, "uint32", torch.int32))          # the same 32 bits either way
+                k = (key if key.dtype in words else key.to(torch.int64).to(torch.int32)).contiguous()
+                if k.numel() != r.n:
+                    raise ValueError("radiance: one key per ray")
+                keep += (k,)
+                r.key = k.data_ptr()
+            torch.cuda.synchronize(o.device)          # the library launches on a stream of its own
+            out_ptr = out.data_ptr()
+        else:
+            o, d = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
+            if o.shape != d.shape or o.shape[-1] != 3:
+                raise ValueError("radiance: orig and dir are [..., 3]")
+            out = np.empty_like(o)
+            keep = (o, d, out)
+            r.n, r.orig, r.dir = o.size // 3, o.ctypes.data, d.ctypes.data
+            if key is not None:
+                k = np.ascontiguousarray(key, np.uint32)
+                if k.size != r.n:
+                    raise ValueError("radiance: one key per ray")
+                keep += (k,)
+                r.key = k.ctypes.data
+            out_ptr = out.ctypes.data
+        ri = _abi.RaysInfo()
+        _lib.check(_lib.lib().mrt_radiance(self._ctx, C.byref(r), C.c_void_p(out_ptr), C.byref(ri)))
+        del keep
+        if info is not None:
+            info.update({k: getattr(ri, k) for k, _ in ri._fields_ if k != "reserved"})
+        return out
+
     # -- extras of the C ABI -----------------------------------------------------------------
     def _need(self):
         if self._ctx is None:
