@@ -12,7 +12,7 @@
 
 namespace mrt {
 
-// 1/n as the tone map forms it for a count n (mrt_api.cpp img_tonemap: 1.0f / (float)count)
+// 1/n as the tone map forms it for a count n (mrt_accum.cpp img_tonemap: 1.0f / (float)count)
 MRT_HD float adapt_recip(u32 n) { return 1.0f / (float)n; }
 
 // e_pixel of one pixel: a, h = its three A and H words; rc = adapt_recip(n), rh = adapt_recip(n / 2)

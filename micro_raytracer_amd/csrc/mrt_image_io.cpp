@@ -11,13 +11,13 @@
 #include <errno.h>
 
 #include "../../include/mrt.h"
+#include "mrt_err.h"                                  // sets mrt_last_error / mrt_last_status
 
-int mrt_internal_fail(int code, const char *msg);     // mrt_api.cpp: sets mrt_last_error / mrt_last_status
-void mrt_internal_ok();
+using namespace mrt::api;
 
 namespace {
 
-int failf(int code, const std::string &msg) { return mrt_internal_fail(code, msg.c_str()); }
+int failf(int code, const std::string &msg) { return fail(code, "%s", msg.c_str()); }
 
 struct CrcTable {
     uint32_t t[256];
@@ -87,6 +87,6 @@ extern "C" int mrt_save_image(const char *path, const uint8_t *rgb8, uint32_t w,
     const size_t wr = fwrite(out.data(), 1, out.size(), f);
     const int werr = errno;
     if (fclose(f) != 0 || wr != out.size()) return failf(MRT_ERR_STATE, std::string("mrt_save_image: short write to '") + path + "': " + strerror(werr ? werr : errno));
-    mrt_internal_ok();
+    ok();
     return MRT_OK;
 }

@@ -1,6 +1,6 @@
 // mrt_inst.h — which pt_megakernel instantiation serves a scene, and the LDS a workgroup of it needs: the one host-side statement
 // of both rules.  Plain C++ with no HIP dependency, so that the launchers (mrt_kernels.hip, mrt_denoise.hip), the kernels
-// (mrt_pt_kernel.h), the launch policy (mrt_plan.cpp), mrt_api.cpp and the x86 builds of tests/emu all call the same functions.
+// (mrt_pt_kernel.h), the launch policy (mrt_plan.cpp), the host units (mrt_hooks.cpp, mrt_radiance.cpp) and the x86 builds of tests/emu all call the same functions.
 #pragma once
 #include "mrt_trace.h"
 

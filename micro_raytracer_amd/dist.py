@@ -18,7 +18,7 @@ DEFAULT_SHARD_ROWS = 8
 
 
 def shard_row_index(nh: int, rank: int, world: int, shard_rows: int = DEFAULT_SHARD_ROWS) -> np.ndarray:
-    """Frame rows owned by `rank`, in local order (same rule as mrt_create, csrc/mrt_api.cpp)."""
+    """Frame rows owned by `rank`, in local order (same rule as mrt_create, csrc/mrt_create.cpp)."""
     y = np.arange(nh)
     return y[(y // shard_rows) % world == rank].astype(np.int64)
 

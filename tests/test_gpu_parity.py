@@ -442,7 +442,7 @@ def test_per_call_loop_equals_one_batched_call():
 
 def test_look_ahead_serves_the_per_call_loop_bit_for_bit():
     """The eager per-call loop (one mrt_execute per sample, src/cli.rs:162-170) is served from look-ahead launches from the
-    third consecutive one-sample call on (csrc/mrt_api.cpp run_lookahead): the accumulator holds exactly the requested
+    third consecutive one-sample call on (csrc/mrt_execute.cpp run_lookahead): the accumulator holds exactly the requested
     samples at EVERY return, bit for bit what the plain one-sample launches leave there; a batched call, a reset or a restored
     accumulator in the middle drops what was traced ahead and changes nothing."""
     from micro_raytracer_amd import Sampler, _abi, scenes

@@ -196,6 +196,38 @@ def test_cached_aovs_survive_a_radiance_call():
     assert all(np.array_equal(before[k].view(np.uint32), after[k].view(np.uint32)) for k in ("depth", "normal", "albedo"))
 
 
+@pytest.mark.parametrize("level", ["deep", "all"])
+def test_radiance_and_aov_share_the_flat_scene_in_either_order(oracle_mod, monkeypatch, level):
+    """mrt_radiance and the AOV pass read the scene as a kernel without F_DEEP reads it, through one accessor of the context: on a
+    deep-staged context the binary-BVH packing, uploaded by whichever call comes first; on a context that stages everything its
+    own blob.  Either order: the radiance is the frame's bits, the AOVs are the oracle's (bit-equal planes, equal ids)."""
+    import test_oracle_aov as A
+    from micro_raytracer_amd import _lib
+    (render, holder), env = _recipe_case(level)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    assert _lib.plan_launch(holder)["staging"] == level
+    frame, _ = _frame_bits(render)
+    ref = A.oracle_aov(oracle_mod, holder)
+
+    def run(rays_first):
+        s = _sampler().create(render)
+        o, d = s.camera_rays(render)
+        aov = None if rays_first else s.aov()
+        got = s.radiance(render, o, d, Y.SPP)
+        aov = aov or s.aov()
+        s.close()
+        return got, aov
+
+    (r1, a1), (r2, a2) = run(True), run(False)
+    assert Y.same(r1, r2) and Y.same(r1, frame), int((Y.bits(r1) != Y.bits(frame)).any(-1).sum())
+    assert set(a1) == set(a2) == {"depth", "normal", "albedo", "renderer", "instance"}
+    for k in a1:
+        assert np.array_equal(a1[k].view(np.uint32), a2[k].view(np.uint32)), k
+    A.compare_aov(f"{level}, radiance then aov", a1, ref)
+    A.compare_aov(f"{level}, aov then radiance", a2, ref)
+
+
 # ---- 10: device pointers ------------------------------------------------------------------------------------------------------
 _DEVICE_SCRIPT = r"""
 import sys

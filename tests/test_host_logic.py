@@ -25,6 +25,22 @@ def test_library_exports_every_declared_symbol():
     assert L.mrt_abi_version() == 3
 
 
+def test_library_exports_no_undeclared_c_symbol():
+    """The other direction: every unmangled mrt_* symbol the library defines is declared in include/mrt.h (the test hooks
+    mrt_plan_launch* and mrt_selftest_* are declared there too), so no internal helper of one host unit leaks into the ABI."""
+    import shutil
+    import subprocess
+    from micro_raytracer_amd import _lib
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    assert nm, "no nm to list the library's dynamic symbols with"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("mrt_")}
+    hdr = open(os.path.join(ROOT, "include", "mrt.h")).read()
+    declared = set(re.findall(r"\b(mrt_[a-z_0-9]+)\s*\(", hdr))
+    assert {"mrt_plan_launch", "mrt_selftest_math", "mrt_selftest_trace"} <= declared
+    assert exported == declared, exported ^ declared
+
+
 def test_no_device_fails_loudly_not_silently():
     """Without a GPU mrt_create must fail with MRT_ERR_DEVICE: there is no CPU fallback."""
     from micro_raytracer_amd import MrtError, Sampler, _lib, load_render, scenes
