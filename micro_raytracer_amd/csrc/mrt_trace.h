@@ -1115,7 +1115,10 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
     //   dot + d == d, or a zero numerator and a miss on both routes), so -(ro.n^ + d) / rd.n^ == -(ro_k + s d) / rd_k as real
     //   numbers, and both divisions round correctly: the same tt.  Here tt is finite, a hit is tt > 0, and for a positive float
     //   total_key is its bit pattern: `0 < bits < best_key` is the miss test and the key comparison at once.
-    // Spheres: the generic arithmetic.  Order, strict comparison, prefetch and the t0-from-key recovery are the generic scan's.
+    // Spheres: the generic arithmetic on the shifted origin pos + (o - pos), without the identity test of xf_vec: o - pos is finite
+    //   here, so the shortcut and the reference's two identity mat-vecs can differ only in the sign of a zero component, and
+    //   pos_k + (+-0) is pos_k for pos_k != 0 and +0 on both routes for pos_k == +-0 (a -0 difference needs o_k == -0 and
+    //   pos_k == +0).  Order, strict comparison, prefetch and the t0-from-key recovery are the generic scan's.
     bool scanned = false;
     if constexpr (!ANY && FEAT == F_IDENT && MRT_T0_FROM_KEY) {
         const V3 o = ray_.o, d = ray_.d;
@@ -1156,7 +1159,7 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
                 else if (code == 3u) plane(i, o.z, d.z, r.z, ia.z, ax.y);
                 else {
                     const V3 pos = v3(ia.x, ia.y, ia.z);
-                    const V3 ro = add(pos, xf_vec(X0, true, sub(o, pos)));
+                    const V3 ro = add(pos, sub(o, pos));          // (no identity test: see above)
                     float t0 = 0.0f, t1 = 0.0f;
                     if (sphere_isect(ia.w, sub(ro, pos), d, ray_.dd, t0, t1)) {
                         const i32 key = total_key(t0);
