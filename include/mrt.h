@@ -474,6 +474,45 @@ int mrt_radiance(mrt_ctx *ctx, const mrt_rays *r, float *rgb /*[n][3]*/, mrt_ray
  * of the pixel.  Either output may be NULL.  Host pointers.  MRT_ERR_STATE: a multi-device context. */
 int mrt_camera_rays(mrt_ctx *ctx, float *orig /*[nh][nw][3]*/, float *dir /*[nh][nw][3]*/);
 
+/* ---- linear float image at the output resolution (not in the reference) ----
+ * mrt_img tone-maps, truncates to u8 and only then resizes, as the reference does; mrt_img_hdr resamples the mean radiance itself,
+ * in f32 on the device, with no tone map and no quantisation: rgb[res_h][res_w][3], linear, >= 0.
+ *   mean       m = sum * (1.0f / count): the context's count, after mrt_execute_adaptive the count of the pixel's 8x8 tile
+ *              (the means mrt_img and mrt_denoise form); with denoise != NULL the filtered means of mrt_denoise under those options
+ *   resize     vertical pass, then horizontal pass, f32, unfused, each sum from +0 with its taps in index order
+ *   output     u > 0 ? u : 0: negative filter lobes and NaN give 0, +inf stays.  nw == res_w and nh == res_h: the clamped means.
+ * MRT_RESIZE_LANCZOS3 uses the taps of mrt_img, bit for bit.  MRT_RESIZE_BOX is the area average: on the common grid source pixel
+ * i covers [i*dst, (i+1)*dst) and output o covers [o*src, (o+1)*src); the weight of i in o is their overlap / src, rounded once to
+ * f32 -- no negative lobe, hence no ringing around a sun or an emitter; exact at integer ratios; the same rule upsamples.
+ * An observation exactly like mrt_img: booked samples are traced first; needs the whole frame (unsharded, or after mrt_set_accum*)
+ * and at least one sample, else MRT_ERR_STATE (and the MRT_ERR_STATEs of mrt_denoise with denoise != NULL); nothing of the context
+ * changes and mrt_stats.img_ms stays as it was.  NULL options: Lanczos3 of the means.  MRT_ERR_ARG: ctx or rgb NULL, an unknown
+ * filter, a non-zero reserved word, denoise options mrt_denoise would refuse. */
+#define MRT_RESIZE_LANCZOS3 0u   /* the taps of mrt_img */
+#define MRT_RESIZE_BOX      1u
+typedef struct mrt_hdr_opts {
+    uint32_t filter;                  /* MRT_RESIZE_*; another value: MRT_ERR_ARG */
+    uint32_t reserved0;               /* 0 */
+    const mrt_denoise_opts *denoise;  /* NULL: the means; else the filtered means, rules of mrt_denoise */
+    uint32_t reserved[4];             /* 0, else MRT_ERR_ARG */
+} mrt_hdr_opts;
+typedef struct mrt_hdr_info {
+    double resize_ms;                 /* HIP-event time of this call's kernels; 0 under MRT_FLAG_NO_EVENT_TIMING */
+    mrt_denoise_info dn;              /* zeroed when denoise == NULL */
+    uint32_t reserved[2];
+} mrt_hdr_info;
+int mrt_img_hdr(mrt_ctx *ctx, const mrt_hdr_opts *o /*NULL: defaults*/, float *rgb /*[res_h][res_w][3]*/, mrt_hdr_info *info /*may be NULL*/);
+
+/* Write a float image rgb[h][w][3]; host only, like mrt_save_image.  The format follows the extension, any other: MRT_ERR_ARG.
+ *   .pfm   "PF\n<w> <h>\n-1.0\n", then the rows bottom to top as little-endian f32 RGB, the values as given
+ *   .hdr   Radiance RGBE: "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y <h> +X <w>\n", scanlines new-style run-length coded for
+ *          8 <= w <= 32767 and flat otherwise.  Per pixel: NaN and negative components count as 0, +inf as FLT_MAX; with
+ *          v = max(r, g, b) = f * 2^E, f in [0.5, 1): four zero bytes for v < 2^-127, else mantissas floor(c * 2^(8-E) + 0.5) (E + 1 when
+ *          the largest reaches 256) and the exponent byte E + 128, saturated at 255 with mantissas capped at 255.  Rounding to
+ *          nearest, because readers decode b * 2^(e-136): below the saturation a component errs by at most 2^(E-9) <= v / 256.
+ * MRT_ERR_ARG: a NULL pointer, w == 0 or h == 0; MRT_ERR_STATE: the file cannot be written. */
+int mrt_save_image_f32(const char *path, const float *rgb, uint32_t w, uint32_t h);
+
 /* Test hook: run one device math-contract function elementwise on the GPU.
  * op: 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 pow(a,b), 5 1/a, 6 sqrt(a), 7 a/b, 12 the first component of norm(a, b, 0.25);
  * 16 the longitude 0.5 + 0.5 atan2(a, -b) / pi and 17 the latitude acos(clamp(a, -1, 1)) / pi of the texture lookups, 18 / 19 the

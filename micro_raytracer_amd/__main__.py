@@ -6,6 +6,7 @@
                                    [--denoise-firefly F]] [--aov PREFIX]
                                   [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS] [--sky-filter nearest|bilinear]
                                   [--tex-filter nearest|bilinear] [--camera pinhole|equirect [--pano-yaw TURNS]]
+                                  [--resize lanczos3|box]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
 --adaptive renders with a per-tile noise threshold instead (Sampler.execute_adaptive), --sample being the cap.
@@ -19,6 +20,10 @@ mapping and its rotation about +z; --sky-filter / --tex-filter choose the filter
 textures (nearest texel, or bilinear).
 --camera equirect renders the frame's supersampled grid as a full lat-long panorama from cam.pos through Sampler.radiance
 (cameras.render_equirect), turned by --pano-yaw; cam.dir, fov and aprt are ignored.
+-o out.hdr / out.pfm saves the linear float image (Sampler.img_hdr: the mean radiance at the output resolution, no tone map, no
+quantisation; with --denoise the filtered means) as a Radiance picture or a PFM; --resize chooses its filter, Lanczos3 with the
+taps of the 8-bit image or the box (area) average a light probe wants.  A panorama written with --camera equirect -o probe.hdr is
+what --sky-tex probe.hdr --sky-map latlong loads.
 """
 import argparse
 import sys
@@ -31,10 +36,22 @@ from .sampler import Sampler
 from .scene import Texture
 
 
+def is_float_output(path):
+    return path.lower().endswith((".hdr", ".pfm"))
+
+
 def image(s, a):
+    dn = dict(passes=a.denoise_passes, mode=a.denoise_mode, sigma_var=a.denoise_sigma_var, firefly=a.denoise_firefly)
+    if is_float_output(a.output):
+        return s.img_hdr(filter=a.resize or "lanczos3", denoise=dn if a.denoise else None)
     if not a.denoise:
         return s.img()
-    return s.img_denoised(passes=a.denoise_passes, mode=a.denoise_mode, sigma_var=a.denoise_sigma_var, firefly=a.denoise_firefly)
+    return s.img_denoised(**dn)
+
+
+def save(path, img):
+    """uint8 images through mrt_save_image (.png, .ppm), float32 ones through mrt_save_image_f32 (.hdr, .pfm)"""
+    (_lib.save_image_f32 if img.dtype == np.float32 else _lib.save_image)(path, img)
 
 
 def aov_images(aov):
@@ -59,7 +76,7 @@ def save_aov(s, prefix):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m micro_raytracer_amd")
     ap.add_argument("full", help="full render description (JSON, the reference's schema)")
-    ap.add_argument("-o", "--output", default="out.png", help=".png or .ppm")
+    ap.add_argument("-o", "--output", default="out.png", help=".png or .ppm; .hdr or .pfm: the linear float image")
     ap.add_argument("--sample", type=int)
     ap.add_argument("--bounce", type=int)
     ap.add_argument("--seed", type=int, default=1)
@@ -87,7 +104,10 @@ def main(argv=None):
                     help="equirect: the frame's supersampled grid as a 360 x 180 degree panorama from cam.pos; the description's "
                          "cam.dir, fov and aprt are ignored")
     ap.add_argument("--pano-yaw", type=float, metavar="TURNS", help="--camera equirect: the centre column looks along +y turned by TURNS")
+    ap.add_argument("--resize", choices=sorted(_abi.RESIZE_FILTERS), help="filter of a .hdr / .pfm output's resize (default lanczos3)")
     a = ap.parse_args(argv)
+    if a.resize is not None and not is_float_output(a.output):
+        ap.error("--resize needs a .hdr or .pfm output: the 8-bit image is resized as the reference resizes it")
     if a.camera == "equirect":
         for name, on in (("--adaptive", a.adaptive is not None), ("--denoise", a.denoise), ("--aov", a.aov is not None), ("--update", a.update)):
             if on:
@@ -149,10 +169,10 @@ def main(argv=None):
     elif a.update:
         for _ in range(render.rt.sample):
             s.execute(render)
-            _lib.save_image(a.output, image(s, a))
+            save(a.output, image(s, a))
     else:
         s.execute(render, n_samples=render.rt.sample)
-    _lib.save_image(a.output, image(s, a))
+    save(a.output, image(s, a))
     if a.aov:
         save_aov(s, a.aov)
     st = s.stats()

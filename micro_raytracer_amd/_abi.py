@@ -181,6 +181,19 @@ def denoise_opts(passes=DENOISE_PASSES, sigma_color=None, sigma_normal=None, sig
     return o
 
 
+# resize filters of mrt_img_hdr (MRT_RESIZE_*)
+RESIZE_LANCZOS3, RESIZE_BOX = 0, 1
+RESIZE_FILTERS = {"lanczos3": RESIZE_LANCZOS3, "box": RESIZE_BOX}
+
+
+class HdrOpts(C.Structure):
+    _fields_ = [("filter", C.c_uint32), ("reserved0", C.c_uint32), ("denoise", C.POINTER(DenoiseOpts)), ("reserved", C.c_uint32 * 4)]
+
+
+class HdrInfo(C.Structure):
+    _fields_ = [("resize_ms", C.c_double), ("dn", DenoiseInfo), ("reserved", C.c_uint32 * 2)]
+
+
 STAGING = ("all", "warm", "deep", "none")
 MAP_SLOTS = ("tex", "rmap", "mmap", "gmap", "omap", "emap")
 

@@ -20,6 +20,7 @@ SYMBOLS = (
     "mrt_create_ext", "mrt_plan_launch_ext",
     "mrt_selftest_trace", "mrt_selftest_instantiations",
     "mrt_radiance", "mrt_camera_rays",
+    "mrt_img_hdr", "mrt_save_image_f32",
 )
 
 
@@ -90,6 +91,8 @@ def lib():
     L.mrt_radiance.argtypes = [vp, C.POINTER(_abi.Rays), vp, C.POINTER(_abi.RaysInfo)]
     L.mrt_camera_rays.argtypes = [vp, f32p, f32p]
     L.mrt_selftest_instantiations.restype = u32
+    L.mrt_img_hdr.argtypes = [vp, C.POINTER(_abi.HdrOpts), f32p, C.POINTER(_abi.HdrInfo)]
+    L.mrt_save_image_f32.argtypes = [C.c_char_p, f32p, u32, u32]
     _LIB = L
     return L
 
@@ -173,3 +176,13 @@ def save_image(path, rgb8):
     import numpy as np
     a = np.ascontiguousarray(rgb8, np.uint8)
     check(lib().mrt_save_image(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]))
+
+
+def save_image_f32(path, rgb):
+    """A float image [h][w][3] as a Radiance .hdr (RGBE, rounded to nearest) or a .pfm (the f32 values as given):
+    mrt_save_image_f32."""
+    import numpy as np
+    a = np.ascontiguousarray(rgb, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"save_image_f32: expected [h][w][3], got {a.shape}")
+    check(lib().mrt_save_image_f32(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[1], a.shape[0]))

@@ -81,8 +81,9 @@ static int denoise_opts(const mrt_denoise_opts *o, const char *fn, DnOpts &r)
     return MRT_OK;
 }
 
-// The filtered means of the accumulator into the context's output plane (*out, on the device); an observation like mrt_img
-static int denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *info, const char *fn, const float **out)
+// The filtered means of the accumulator into the context's output plane (*out, on the device); an observation like mrt_img.
+// mrt_img_hdr (mrt_hdr.cpp) calls it too: mrt_ctx.h declares it.
+int mrt::api::denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *info, const char *fn, const float **out)
 {
     DnOpts d;
     Frame f;

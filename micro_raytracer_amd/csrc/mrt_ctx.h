@@ -93,6 +93,14 @@ struct Image {
     DeviceMem<unsigned char> out;
     u32 vcap = 0, hcap = 0;
 };
+// the linear float image (mrt_img_hdr), created whole by the first call: the box taps of both passes (the Lanczos3
+// taps are the Image's own), the vertical pass's output, the image, the events around the call's kernels
+struct Hdr {
+    DeviceMem<u32> vl, vc, hl, hc;
+    DeviceMem<float> vw, hw, tmp, out;            // tmp [res_h][nw][3], out [res_h][res_w][3]
+    u32 vcap = 0, hcap = 0;
+    Event ev[2];
+};
 // first-hit AOVs and the denoiser (mrt_aov, mrt_denoise: DESIGN.md §13), on the context's device; the AOVs depend on scene and
 // camera only and survive mrt_reset
 struct Aov {
@@ -163,6 +171,7 @@ struct mrt_ctx {
     bool adaptive = false;                        // the accumulator holds an adaptive render: per-tile counts, count = the smallest
     std::unique_ptr<mrt::api::Adaptive> ad;
     std::unique_ptr<mrt::api::Image> img;
+    std::unique_ptr<mrt::api::Hdr> hdr;
     bool aov_ready = false;                       // the AOVs have been computed
     std::unique_ptr<mrt::api::Aov> aov;
     // The sub-contexts and the RCCL comms go first; then this context's own resources on its device -- the look-ahead planes
@@ -252,6 +261,11 @@ int img_prepare(mrt_ctx *c);
 // differs (image 0.24 resize copies when the dimensions match); then close the timing of the image kernels, wait for them and
 // copy the image out
 int img_finish(mrt_ctx *c, uint8_t *rgb8, bool resize);
+
+// mrt_aov.cpp
+// The filtered means of the accumulator into the context's output plane (*out [nh][nw][3], on the device); an observation like
+// mrt_img, with its own enter()
+int denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *info, const char *fn, const float **out);
 
 }  // namespace api
 }  // namespace mrt

@@ -31,6 +31,14 @@ hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh
                             const float *weight, u32 cap, hipStream_t stream);
 hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count,
                             const float *weight, u32 cap, hipStream_t stream);
+// mrt_hdr.hip: the linear float image (mrt_img_hdr): the means sums * rc (per-tile counts when tile_count is not null) through the
+// vertical pass into dst [dh][sw][3], that through the horizontal pass and the clamp at 0 into dst [dh][dw][3]; without a resize
+// the clamped means [nh][nw][3]
+hipError_t launch_hdr_v(const float *sums, float rc, const u32 *tile_count, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,
+                        const float *weight, u32 cap, hipStream_t stream);
+hipError_t launch_hdr_h(const float *src, float *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count, const float *weight, u32 cap,
+                        hipStream_t stream);
+hipError_t launch_hdr_copy(const float *sums, float rc, const u32 *tile_count, float *dst, u32 nw, u32 nh, hipStream_t stream);
 // mrt_rayq.hip: the ray-query test hook (mrt_selftest_trace), instantiation `inst` at 256 threads with `lds` bytes of LDS; n rays,
 // out [n][MRT_TRACE_WORDS].  rayq_has: that instantiation exists
 hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream);

@@ -381,6 +381,33 @@ void lanczos3_taps(u32 src, u32 dst, ResampleTaps &out)
     }
 }
 
+// Exact integer arithmetic in u64: source pixel i covers [i*dst, (i+1)*dst), output o covers [o*src, (o+1)*src); the weight is
+// the overlap over the footprint, rounded once to f32 and not renormalised (exact at an integer ratio; the same rule upsamples)
+void box_taps(u32 src, u32 dst, ResampleTaps &out)
+{
+    typedef unsigned long long u64;
+    std::vector<u32> right(dst, 0);
+    out.left.assign(dst, 0);
+    out.count.assign(dst, 0);
+    out.cap = 0;
+    for (u32 o = 0; o < dst; ++o) {
+        out.left[o] = (u32)(((u64)o * src) / dst);
+        right[o] = (u32)((((u64)o + 1u) * src + dst - 1u) / dst);
+        out.count[o] = right[o] - out.left[o];
+        if (out.count[o] > out.cap) out.cap = out.count[o];
+    }
+    out.weight.assign((size_t)dst * out.cap, 0.0f);
+    for (u32 o = 0; o < dst; ++o) {
+        const u64 a = (u64)o * src, b = a + src;
+        float *w = out.weight.data() + (size_t)o * out.cap;
+        for (u32 k = 0; k < out.count[o]; ++k) {
+            const u64 i = (u64)out.left[o] + k;
+            const u64 lo = i * dst > a ? i * dst : a, hi = (i + 1u) * dst < b ? (i + 1u) * dst : b;
+            w[k] = (float)((double)(hi - lo) / (double)src);
+        }
+    }
+}
+
 namespace {
 
 inline float min_num(float a, float b) { if (a != a) return b; if (b != b) return a; return b < a ? b : a; }

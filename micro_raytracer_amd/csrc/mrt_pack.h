@@ -64,5 +64,8 @@ struct ResampleTaps {
     u32 cap = 0;
 };
 void lanczos3_taps(u32 src, u32 dst, ResampleTaps &out);
+// Box (area-average) taps of one axis, in the same tables: output o averages the source pixels its footprint [o*src, (o+1)*src)
+// overlaps on the common grid of src*dst cells, each weighted by its share of the footprint; cap = the largest count.
+void box_taps(u32 src, u32 dst, ResampleTaps &out);
 
 }  // namespace mrt

@@ -253,6 +253,30 @@ class Sampler:
             info["mode"] = int(di.reserved[0])
         return out
 
+    def img_hdr(self, filter="lanczos3", denoise=None, info=None) -> np.ndarray:
+        """The linear float image (mrt_img_hdr), float32 [res_h][res_w][3]: the mean radiance resampled in f32 to the
+        output resolution, no tone map, no quantisation, clamped at 0.  filter "lanczos3" (the taps of img()) or "box" (area
+        average, no ringing around a sun: what a light probe wants).  denoise: None for the means, or a dict of denoise()
+        arguments for the filtered means.  info: a dict that receives resize_ms and, with denoise, mrt_denoise_info."""
+        self._need()
+        if filter not in _abi.RESIZE_FILTERS:
+            raise ValueError(f"resize filter `{filter}`: expected one of {sorted(_abi.RESIZE_FILTERS)}")
+        o = _abi.HdrOpts()
+        o.filter = _abi.RESIZE_FILTERS[filter]
+        dn = None
+        if denoise is not None:
+            dn = _abi.denoise_opts(**denoise)
+            o.denoise = C.pointer(dn)
+        out = np.empty((self.res[1], self.res[0], 3), np.float32)
+        hi = _abi.HdrInfo()
+        _lib.check(_lib.lib().mrt_img_hdr(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(hi)))
+        if info is not None:
+            info["resize_ms"] = hi.resize_ms
+            if dn is not None:
+                info.update({k: getattr(hi.dn, k) for k, _ in hi.dn._fields_ if k != "reserved"})
+                info["mode"] = int(hi.dn.reserved[0])
+        return out
+
     # -- radiance along caller-supplied rays (mrt_radiance, DESIGN.md §18) --------------------
     def camera_rays(self, render: Render):
         """(orig, dir), float32 [nh][nw][3]: the lens-centre camera ray of every supersampled pixel (mrt_camera_rays) -- with

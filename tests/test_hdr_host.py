@@ -1,0 +1,233 @@
+"""The linear float image (mrt_img_hdr) without a GPU: the x86 build of the kernels' per-element bodies
+(csrc/mrt_hdr.h) and of the tap tables against the numpy restatement of tests/hdr_ref.py, bit for bit; box_taps against the integer
+rule; the .pfm and .hdr writers through the library (host only); the ABI mirror and the CLI's argument checks."""
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import hdr_ref as H
+from conftest import ROOT
+from emu.build import probe_or_skip
+
+f32 = np.float32
+BOX_PAIRS = ((6, 3), (9, 6), (7, 5), (520, 260), (3, 6), (1, 1))
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    L = probe_or_skip("hdr_probe", tmp_path_factory.mktemp("hdr"))
+    fp, u32p, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32
+    L.hd_taps.restype = u32
+    L.hd_taps.argtypes = [u32, u32, u32, u32p, u32p, fp, u32]
+    L.hd_img.argtypes = [fp, C.c_float, u32p, u32, u32, u32, u32, u32, u32, fp]
+    return L
+
+
+def x86_taps(probe, filter, src, dst):
+    cap = probe.hd_taps(H.FILTERS.index(filter), src, dst, None, None, None, 0)
+    left, count, w = np.zeros(dst, np.uint32), np.zeros(dst, np.uint32), np.zeros((dst, cap), f32)
+    p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    assert probe.hd_taps(H.FILTERS.index(filter), src, dst, p(left, C.c_uint32), p(count, C.c_uint32), p(w, C.c_float), cap) == cap
+    assert count.max() <= cap
+    return [(int(l), w[o, :n].copy()) for o, (l, n) in enumerate(zip(left, count))]
+
+
+def x86_img(probe, sums, count, res, filter, rows=4, tiles=None):
+    sums = np.ascontiguousarray(sums, f32)
+    nh, nw, _ = sums.shape
+    out = np.full((res[1], res[0], 3), -1.0, f32)
+    tc = None if tiles is None else np.ascontiguousarray(tiles, np.uint32)
+    rc = float(f32(1.0) / f32(count))
+    assert probe.hd_img(sums.ctypes.data_as(C.POINTER(C.c_float)), rc, None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                        nw, nh, res[0], res[1], H.FILTERS.index(filter), rows, out.ctypes.data_as(C.POINTER(C.c_float))) == 0
+    return out
+
+
+# ---- 1. the taps ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("src,dst", BOX_PAIRS)
+def test_box_taps_equal_the_integer_rule(probe, src, dst):
+    got, want = x86_taps(probe, "box", src, dst), H.box_taps(src, dst)
+    assert len(got) == len(want) == dst
+    for (gl, gw), (wl, ww) in zip(got, want):
+        assert gl == wl and H.same(gw, ww), (src, dst, gl, wl, gw, ww)
+    if (src, dst) == (6, 3):
+        assert all(l == 2 * o and w.tolist() == [0.5, 0.5] for o, (l, w) in enumerate(got))
+    if (src, dst) == (3, 6):                       # an upsample: every output lies inside one source pixel
+        assert all(l == o // 2 and w.tolist() == [1.0] for o, (l, w) in enumerate(got))
+    if (src, dst) == (1, 1):
+        assert got[0][0] == 0 and got[0][1].tolist() == [1.0]
+    assert all((w > 0).all() for _, w in got)      # no negative lobe anywhere
+
+
+def test_lanczos_taps_are_those_of_the_image_path(probe, oracle_mod):
+    """The probe's Lanczos3 table is lanczos3_taps of the host packer, which mrt_img uploads: equal to the oracle's weights."""
+    for src, dst in ((16, 8), (9, 6), (4, 8), (520, 260), (24, 12)):
+        for (gl, gw), (wl, ww) in zip(x86_taps(probe, "lanczos3", src, dst), H.lanczos_taps(oracle_mod, src, dst)):
+            assert gl == wl and H.same(gw, ww), (src, dst)
+
+
+# ---- 2. the bodies ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("res,ssaa", H.SHAPES, ids=lambda v: str(v))
+def test_bodies_equal_the_restatement_bit_for_bit(probe, oracle_mod, res, ssaa):
+    """Every content of hdr_ref.contents on this frame, both filters, one and four output rows per call of the vertical body;
+    then per-tile counts.  The spike shows that the clamp and the box claim are exercised."""
+    nw, nh = H.ss_dims(res, ssaa)
+    resized = (nw, nh) != tuple(res)
+    for name, sums, count in H.contents(nh, nw, seed=nw * 7 + nh):
+        m = H.mean(sums, count)
+        for filt in H.FILTERS:
+            want = H.img_hdr(oracle_mod, m, res, filt)
+            for rows in (1, 4):
+                got = x86_img(probe, sums, count, res, filt, rows)
+                assert H.same(got, want), (res, ssaa, name, filt, rows, np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4])
+            assert (want >= 0).all() and not np.isnan(want).any()
+        if name == "spike" and resized and ssaa > 1:
+            assert H.img_hdr(oracle_mod, m, res, "lanczos3", pre_clamp=True).min() < 0
+            assert H.img_hdr(oracle_mod, m, res, "box", pre_clamp=True).min() >= 0
+        if name == "inf":
+            assert np.isinf(H.img_hdr(oracle_mod, m, res, "box")).any()
+    rng = np.random.default_rng(nw)
+    tiles = rng.choice(np.array([1, 32, 37, 48], np.uint32), ((nh + 7) // 8, (nw + 7) // 8))
+    per_pixel = np.repeat(np.repeat(tiles, 8, 0), 8, 1)[:nh, :nw]
+    sums = (rng.random((nh, nw, 3), dtype=f32) * f32(40.0)).astype(f32)
+    for filt in H.FILTERS:
+        want = H.img_hdr(oracle_mod, H.mean(sums, per_pixel), res, filt)
+        assert H.same(x86_img(probe, sums, 1, res, filt, 4, tiles), want), (res, ssaa, filt)
+    assert np.array_equal(H.tile_counts(per_pixel), tiles)
+
+
+# ---- 3. the writers ----------------------------------------------------------------------------------------------------------------
+def _writer_cases():
+    fm = H.FLT_MAX
+    px = [[0, 0, 0], [1e-30, 0, 0], [0.999, 0.5, 0.25], [1.0, 1.0, 1.0], [255.5 / 256 * 8, 1.0, 0.0], [255.5 / 256, 255.4 / 256, 0.1],
+          [1e30, 1e29, 1.0], [fm, 1.0, fm / 2], [np.inf, 1.0, 0.0], [np.nan, 2.0, 3.0], [-1.0, 0.5, -np.inf], [-0.0, 3e-39, 1e-39],
+          [2.0 ** -127, 0, 0], [2.0 ** -128, 0, 0], [1.6e38, 1.7e38, 1.0], [65504.0, 1e-3, 7.0]]
+    rng = np.random.default_rng(4)
+    out = {}
+    for w in (7, 8, 40):
+        img = (rng.random((5, w, 3)) * np.exp2(rng.integers(-20, 20, (5, w, 1)))).astype(f32)
+        flat = img.reshape(-1, 3)
+        flat[:len(px)] = np.array(px, f32)[:flat.shape[0]]
+        img[4] = f32(0.75)                                   # a constant row
+        out[w] = img
+    return out
+
+
+def test_pfm_round_trip(tmp_path):
+    from micro_raytracer_amd import _lib
+    for w, img in _writer_cases().items():
+        p = tmp_path / f"o{w}.pfm"
+        _lib.save_image_f32(p, img)
+        raw = open(p, "rb").read()
+        head = f"PF\n{w} 5\n-1.0\n".encode()
+        assert raw.startswith(head) and raw[len(head):] == img[::-1].astype("<f4").tobytes()
+        assert H.same(H.read_pfm(p), img)
+
+
+def test_hdr_round_trip_and_bound(tmp_path):
+    from micro_raytracer_amd import _lib
+    from micro_raytracer_amd.scene import read_hdr
+    for w, img in _writer_cases().items():
+        p = tmp_path / f"o{w}.hdr"
+        _lib.save_image_f32(p, img)
+        raw = open(p, "rb").read()
+        assert raw.startswith(f"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y 5 +X {w}\n".encode())
+        t = read_hdr(str(p))
+        assert (t.w, t.h) == (w, 5)
+        got = t.dat.reshape(5, w, 3)
+        enc = H.rgbe_encode(img)
+        assert H.same(got, H.rgbe_decode(enc))
+        # the bound of the rule: with NaN / negatives as 0 and +inf as FLT_MAX, every component within v / 256 of the input,
+        # v the pixel's largest -- below the saturation of the exponent byte (v < 2^127) and above the cut-off (v >= 2^-127)
+        x = np.where(np.isnan(img) | (img < 0), 0.0, np.minimum(img.astype(np.float64), H.FLT_MAX))
+        v = x.max(-1, keepdims=True)
+        normal = (v >= 2.0 ** -127) & (v * (1 + 2.0 ** -9) < 2.0 ** 127)
+        err = np.abs(got.astype(np.float64) - x)
+        assert (err <= v / 256)[np.broadcast_to(normal, err.shape)].all()
+        assert (got[np.broadcast_to(v < 2.0 ** -127, got.shape)] == 0).all()
+        sat = np.broadcast_to(v >= 2.0 ** 127, got.shape)
+        assert (enc[..., 3][v[..., 0] >= 2.0 ** 127] == 255).all() and (got[sat] <= 255 * 2.0 ** 119).all()
+        if w >= 8:
+            assert raw.count(b"\x02\x02" + bytes([w >> 8, w & 255])) >= 5       # new-style scanlines
+        else:
+            assert len(raw) == raw.index(b"+X 7\n") + 5 + 5 * 7 * 4            # flat
+    # the mantissa that rounds to 256 moves to the next exponent
+    assert H.rgbe_encode(np.array([255.5 / 256, 0, 0], f32)).tolist() == [128, 0, 0, 129]
+    assert H.rgbe_encode(np.array([0.999, 0, 0], f32)).tolist() == [128, 0, 0, 129] and H.rgbe_encode(np.array([1.0, 0, 0], f32)).tolist() == [128, 0, 0, 129]
+    assert H.rgbe_encode(np.array([0.99, 0, 0], f32)).tolist() == [253, 0, 0, 128]
+    assert H.rgbe_encode(np.array([np.inf, 0, 0], f32)).tolist() == [255, 0, 0, 255]
+
+
+def test_hdr_run_length_is_on(tmp_path):
+    from micro_raytracer_amd import _lib
+    from micro_raytracer_amd.scene import read_hdr
+    img = np.full((4, 64, 3), 0.75, f32)
+    p = tmp_path / "flat.hdr"
+    _lib.save_image_f32(p, img)
+    head = len(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y 4 +X 64\n")
+    assert os.path.getsize(p) - head < 4 * 64 * 4 // 4
+    assert H.same(read_hdr(str(p)).dat.reshape(4, 64, 3), img)
+    # a long literal stretch and a run longer than 127 in one scanline
+    rng = np.random.default_rng(1)
+    img = np.concatenate([rng.random((2, 300, 3)).astype(f32), np.full((2, 200, 3), 0.5, f32)], 1)
+    p = tmp_path / "mixed.hdr"
+    _lib.save_image_f32(p, img)
+    assert H.same(read_hdr(str(p)).dat.reshape(2, 500, 3), H.rgbe_decode(H.rgbe_encode(img)))
+
+
+def test_writer_rejections(tmp_path):
+    from micro_raytracer_amd import MrtError, _abi, _lib
+    L = _lib.lib()
+    img = np.ones((2, 3, 3), f32)
+    fp = img.ctypes.data_as(C.POINTER(C.c_float))
+    for name in ("o.png", "o.exr", "o", "o.hdr.txt"):
+        with pytest.raises(MrtError) as e:
+            _lib.save_image_f32(tmp_path / name, img)
+        assert e.value.code == _abi.MRT_ERR_ARG and "extension" in e.value.msg
+    ok = str(tmp_path / "o.pfm").encode()
+    assert L.mrt_save_image_f32(None, fp, 3, 2) == _abi.MRT_ERR_ARG
+    assert L.mrt_save_image_f32(ok, None, 3, 2) == _abi.MRT_ERR_ARG
+    assert L.mrt_save_image_f32(ok, fp, 0, 2) == _abi.MRT_ERR_ARG
+    assert L.mrt_save_image_f32(ok, fp, 3, 0) == _abi.MRT_ERR_ARG
+    assert not os.path.exists(tmp_path / "o.pfm")
+    with pytest.raises(MrtError) as e:
+        _lib.save_image_f32(tmp_path / "no_such_dir" / "o.hdr", img)
+    assert e.value.code == _abi.MRT_ERR_STATE
+
+
+# ---- 4. ABI, Python, CLI ---------------------------------------------------------------------------------------------------------
+def test_header_declares_the_hdr_abi():
+    from micro_raytracer_amd import _abi, _lib
+    hdr = open(os.path.join(ROOT, "include", "mrt.h")).read()
+    for s in ("mrt_img_hdr", "mrt_save_image_f32"):
+        assert s in _lib.SYMBOLS and re.search(r"\bint " + s + r"\(", hdr) and hasattr(_lib.lib(), s)
+    assert re.search(r"#define MRT_RESIZE_LANCZOS3 0u", hdr) and re.search(r"#define MRT_RESIZE_BOX\s+1u", hdr)
+    assert re.search(r"#define MRT_ABI_VERSION 3u", hdr) and _lib.lib().mrt_abi_version() == 3
+    assert (_abi.RESIZE_LANCZOS3, _abi.RESIZE_BOX) == (0, 1) and _abi.RESIZE_FILTERS == {"lanczos3": 0, "box": 1}
+    # LP64 layout of the two structs as the C compiler lays them out
+    assert C.sizeof(_abi.HdrOpts) == 32 and _abi.HdrOpts.denoise.offset == 8 and _abi.HdrOpts.reserved.offset == 16
+    assert C.sizeof(_abi.HdrInfo) == 48 and _abi.HdrInfo.dn.offset == 8 and _abi.HdrInfo.reserved.offset == 40
+    # a null context is an argument error before any device work
+    out = np.zeros(3, f32)
+    assert _lib.lib().mrt_img_hdr(None, None, out.ctypes.data_as(C.POINTER(C.c_float)), None) == _abi.MRT_ERR_ARG
+
+
+def test_python_and_cli_argument_checks(tmp_path, capsys):
+    from micro_raytracer_amd import MrtError, Sampler, _abi, scenes
+    from micro_raytracer_amd import __main__ as cli
+    with pytest.raises(MrtError) as e:
+        Sampler().img_hdr()
+    assert e.value.code == _abi.MRT_ERR_STATE
+    (tmp_path / "plain.json").write_text(json.dumps(scenes.cornell_box(res=(32, 32), sample=1)))
+    for out in ("o.png", "o.ppm"):
+        with pytest.raises(SystemExit) as e:
+            cli.main([str(tmp_path / "plain.json"), "-o", str(tmp_path / out), "--resize", "box"])
+        assert e.value.code == 2 and "--resize" in capsys.readouterr().err
+    with pytest.raises(SystemExit) as e:
+        cli.main([str(tmp_path / "plain.json"), "-o", str(tmp_path / "o.hdr"), "--resize", "cubic"])
+    assert e.value.code == 2 and "cubic" in capsys.readouterr().err
+    assert cli.is_float_output("a/b.HDR") and cli.is_float_output("x.pfm") and not cli.is_float_output("x.hdr.png")
