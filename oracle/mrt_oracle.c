@@ -830,12 +830,14 @@ static inline v3 light_vec(const light_t *l, v3 hit_p)   /* src/rt.rs:1029-1032,
     return v3_neg(v3_norm(l->v));
 }
 
-/* reduce_light(iter(x, y)) for one sample: src/rt.rs:937-994 with RaytraceIterator::next, :1014-1066 */
-static v3 trace_sample(const orc_ctx *c, scratch_t *s, const pixel_cam_t *pc, uint32_t pixel, uint32_t sample)
+/* reduce_light(iter) for one sample on a given first ray: src/rt.rs:949-994 with RaytraceIterator::next, :1014-1066.
+ * kernel_segments (may be NULL) receives the count under the kernel's stop rule: the closest-hit
+ * queries of this path up to and including the first recorded hit, in path order, whose emit coin comes up -- the fold below
+ * throws away everything behind that hit, the kernel never traces it.  s->segments keeps counting every query. */
+static v3 trace_path(const orc_ctx *c, scratch_t *s, ray_t next_ray, uint32_t pk, uint32_t *kernel_segments)
 {
-    uint32_t pk = orc_path_key(c->seed, pixel, sample);
-    ray_t next_ray = camera_ray(c, pc, pk);
     uint32_t n = 0;
+    uint64_t seg0 = s->segments;
     int escaped = 0;      /* the path left the scene (in direction next_ray.dir) instead of running out of bounces */
     /* RaytraceIterator::next, collected (src/rt.rs:961) */
     while (next_ray.bounce <= c->bounce) {
@@ -858,6 +860,14 @@ static v3 trace_sample(const orc_ctx *c, scratch_t *s, const pixel_cam_t *pc, ui
             if (ray_refract(c, &h1.ray, &h1, pk, &r)) { next_ray = r; n_hit = h1; }
         }
         s->path[n++] = n_hit;
+    }
+    if (kernel_segments) {
+        uint32_t ks = (uint32_t)(s->segments - seg0);
+        for (uint32_t k = 0; k < n; k++) {
+            const hit_t *hit = &s->path[k];
+            if (bernoulli(hit_get_emit(c, hit), orc_draw_u32(pk, dim_of(hit->ray.bounce, SL_EMIT_COIN)))) { ks = k + 1; break; }
+        }
+        *kernel_segments = ks;
     }
     v3 col;
     if (c->has_env) {
@@ -903,6 +913,13 @@ static v3 trace_sample(const orc_ctx *c, scratch_t *s, const pixel_cam_t *pc, ui
         col = v3_muls(v3_add(d_col, l_col), hit->ray.pwr);        /* src/rt.rs:992 */
     }
     return col;
+}
+
+/* reduce_light(iter(x, y)) for one sample: the camera's ray (src/rt.rs:937-947, 900-931), then the path */
+static v3 trace_sample(const orc_ctx *c, scratch_t *s, const pixel_cam_t *pc, uint32_t pixel, uint32_t sample)
+{
+    uint32_t pk = orc_path_key(c->seed, pixel, sample);
+    return trace_path(c, s, camera_ray(c, pc, pk), pk, NULL);
 }
 
 void orc_trace_pixel(const orc_ctx *c, uint32_t x, uint32_t y, uint32_t sidx, float rgb[3], uint32_t *segments)
@@ -982,6 +999,30 @@ void orc_ray_query(const orc_ctx *c, size_t n, const float *orig, const float *d
         q[3] = (uint32_t)(h0.inst - h0.obj->inst);
         memcpy(&q[4], &h0.ray.t, 4); memcpy(&q[5], &h1.ray.t, 4);
         memcpy(&q[6], &h0.norm.x, 4); memcpy(&q[7], &h0.norm.y, 4); memcpy(&q[8], &h0.norm.z, 4);
+    }
+    scratch_free(&s);
+}
+
+/* Radiance along caller-supplied rays (mrt_oracle.h).  The ray is one that Ray::cast has already made, as
+ * in orc_ray_query: the origin as given, the direction as given, pwr 1, bounce 0; no lens draw is taken, every later draw sits
+ * at its usual slot under the path key of (seed, key_i, sample).  Samples are added one by one, as src/sampler.rs:62-70 adds. */
+void orc_radiance(const orc_ctx *c, size_t n, const float *orig, const float *dir, const uint32_t *key, uint32_t sample_base,
+                  uint32_t n_samples, float *rgb, uint64_t *segments)
+{
+    scratch_t s; scratch_init(c, &s);
+    for (size_t i = 0; i < n; i++) {
+        ray_t ray = ray_cast_default(V3(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]), V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]));
+        ray.orig = V3(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]);
+        v3 sum = V3(0.0f, 0.0f, 0.0f);
+        uint64_t segs = 0;
+        for (uint32_t j = 0; j < n_samples; j++) {
+            uint32_t ks;
+            v3 col = trace_path(c, &s, ray, orc_path_key(c->seed, key ? key[i] : (uint32_t)i, sample_base + j), &ks);
+            sum.x += col.x; sum.y += col.y; sum.z += col.z;
+            segs += ks;
+        }
+        rgb[3 * i] = sum.x; rgb[3 * i + 1] = sum.y; rgb[3 * i + 2] = sum.z;
+        if (segments) segments[i] = segs;
     }
     scratch_free(&s);
 }

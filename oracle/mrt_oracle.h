@@ -29,6 +29,11 @@
  * environment's mapping, rot and filter -- neither sky.pwr nor the mean m enters it), not from csrc/mrt_denoise.h.  It is
  * anchored to float64 closest hits, rotated instances and camera included, and holds the x86 build of aov_pixel and the GPU to
  * bit equality on every plane (tests/test_oracle_aov.py, tests/test_gpu_oracle_aov.py, the fuzz of tests/test_fuzz_scenes.py).
+ *
+ * RADIANCE ON SUPPLIED RAYS: orc_radiance runs the path loop and fold of orc_execute on a first ray handed in (DESIGN.md section
+ * 18: traced as given, no lens draw).  It is anchored to orc_execute and orc_trace_pixel bit for bit on the camera's own rays and
+ * holds the x86 build of rays_body and the GPU's mrt_radiance to 1e-4 of max(n_samples, |sum|) per ray, with equal segment counts
+ * (tests/test_radiance_oracle_host.py, tests/test_gpu_radiance_oracle.py).
  */
 #ifndef MRT_ORACLE_H
 #define MRT_ORACLE_H
@@ -91,6 +96,15 @@ void orc_aov(const orc_ctx *c, float *depth, float *normal, float *albedo, int32
  * world shading normal at t0 as orc_aov forms it, as bit patterns; words 4..8 are 0 on a miss. */
 #define ORC_RAY_WORDS 9u
 void orc_ray_query(const orc_ctx *c, size_t n, const float *orig, const float *dir, uint32_t *out);
+
+/* Radiance along n caller-supplied rays: ray i is path-traced as given -- a ray as Ray::cast leaves it, as
+ * for orc_ray_query: no shift of the origin by E, no normalisation, pwr 1, bounce 0, no lens draw -- for the samples
+ * [sample_base, sample_base + n_samples) under the path key orc_path_key(seed, key[i], sample); key == NULL: key[i] = i.
+ * rgb[n][3]: the samples' reduce_light values added one by one from 0, as src/sampler.rs:62-70 adds them.  segments[n] (may be
+ * NULL): ray i's closest-hit queries under the kernel's stop rule -- per path, those up to and including the first hit, in path
+ * order, whose emit coin comes up (the reference traces on and its fold discards the rest; orc_segments counts those too). */
+void orc_radiance(const orc_ctx *c, size_t n, const float *orig, const float *dir, const uint32_t *key, uint32_t sample_base,
+                  uint32_t n_samples, float *rgb, uint64_t *segments);
 
 /* Stand-alone pieces for unit tests */
 void orc_tonemap_px(const float sum[3], uint32_t count, float gamma, float exp, uint8_t out[3]);

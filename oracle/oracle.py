@@ -54,6 +54,8 @@ def lib():
     L.orc_aov.restype = None
     L.orc_ray_query.argtypes = [vp, C.c_size_t, f32p, f32p, u32p]
     L.orc_ray_query.restype = None
+    L.orc_radiance.argtypes = [vp, C.c_size_t, f32p, f32p, u32p, u32, u32, f32p, C.POINTER(C.c_uint64)]
+    L.orc_radiance.restype = None
     L.orc_trace_pixel.argtypes = [vp, u32, u32, u32, f32p, u32p]
     L.orc_tonemap_px.argtypes = [f32p, u32, C.c_float, C.c_float, u8p]
     L.orc_lanczos3_resize.argtypes = [u8p, u32, u32, u8p, u32, u32]
@@ -167,6 +169,32 @@ class Oracle:
         out = np.zeros((orig.shape[0], 9), np.uint32)
         lib().orc_ray_query(self._c, orig.shape[0], _fp(orig), _fp(dir), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
+
+    def radiance(self, orig, dir, n_samples, sample_base=0, key=None, threads=None):
+        """orc_radiance on n rays (traced as given), samples [sample_base, + n_samples), key None: the ray index.  Returns
+        (sums float32 [n][3], segments uint64 [n] under the kernel's stop rule)."""
+        orig, dir = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
+        assert orig.ndim == 2 and orig.shape[1] == 3 and orig.shape == dir.shape
+        assert n_samples > 0 and sample_base + n_samples <= 0xffffffff
+        n = orig.shape[0]
+        key = np.arange(n, dtype=np.uint32) if key is None else np.ascontiguousarray(key, np.uint32)
+        assert key.shape == (n,)
+        sums, seg = np.zeros((n, 3), np.float32), np.zeros(n, np.uint64)
+        L, u32p, u64p = lib(), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+
+        def part(lo, hi):          # rays are independent and orc_radiance only reads the context: slices on threads (ctypes drops the GIL)
+            L.orc_radiance(self._c, hi - lo, _fp(orig[lo:hi]), _fp(dir[lo:hi]), key[lo:hi].ctypes.data_as(u32p), sample_base, n_samples,
+                           _fp(sums[lo:hi]), seg[lo:hi].ctypes.data_as(u64p))
+
+        threads = max(1, min(threads or min(16, os.cpu_count() or 1), n // 64))
+        if threads == 1:
+            part(0, n)
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            cuts = np.linspace(0, n, 4 * threads + 1).astype(int)
+            with ThreadPoolExecutor(threads) as pool:
+                list(pool.map(lambda b: part(b[0], b[1]), zip(cuts[:-1], cuts[1:])))
+        return sums, seg
 
     def trace_pixel(self, x, y, s):
         rgb = np.zeros(3, np.float32)

@@ -69,14 +69,16 @@ def x86_camera_rays(L, holder):
     return o, d
 
 
-def x86_radiance(L, holder, feat, orig, dir, n_samples, seed=SEED, sample_base=0, key=None, threads=8):
+def x86_radiance(L, holder, feat, orig, dir, n_samples, seed=SEED, sample_base=0, key=None, threads=8, segments=False):
+    """The sums; with segments=True, (sums, the batch's segment total as mrt_rays_info.segments counts it)."""
     o, d = np.ascontiguousarray(orig, f32), np.ascontiguousarray(dir, f32)
     out = np.zeros_like(o)
     k = None if key is None else np.ascontiguousarray(key, np.uint32)
+    seg = C.c_uint64(0)
     rc = L.ry_radiance(*_ptrs(holder), feat, seed, sample_base, n_samples, o.size // 3, _p(o), _p(d), None if k is None else _p(k, C.c_uint32),
-                       threads, _p(out), None)
+                       threads, _p(out), C.byref(seg) if segments else None)
     assert rc == 0, L.ry_error()
-    return out
+    return (out, int(seg.value)) if segments else out
 
 
 def bits(a):
