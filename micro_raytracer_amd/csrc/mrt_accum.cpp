@@ -43,21 +43,10 @@ int mrt::api::img_prepare(mrt_ctx *c)
         ResampleTaps v, h;
         lanczos3_taps(nh, rh, v);
         lanczos3_taps(nw, rw, h);
-        HIP_TRY(im->vl.alloc(rh));
-        HIP_TRY(im->vc.alloc(rh));
-        HIP_TRY(im->vw.alloc((size_t)rh * v.cap));
-        HIP_TRY(im->hl.alloc(rw));
-        HIP_TRY(im->hc.alloc(rw));
-        HIP_TRY(im->hw.alloc((size_t)rw * h.cap));
-        HIP_TRY(hipMemcpy(im->vl.p, v.left.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(im->vc.p, v.count.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(im->vw.p, v.weight.data(), sizeof(float) * (size_t)rh * v.cap, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(im->hl.p, h.left.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(im->hc.p, h.count.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(im->hw.p, h.weight.data(), sizeof(float) * (size_t)rw * h.cap, hipMemcpyHostToDevice));
+        HIP_TRY(im->lanczos3.v.upload(v, rh));
+        HIP_TRY(im->lanczos3.h.upload(h, rw));
         HIP_TRY(im->tmp.alloc((size_t)nw * rh * 3));
         HIP_TRY(im->out.alloc((size_t)rw * rh * 3));
-        im->vcap = v.cap; im->hcap = h.cap;
         return MRT_OK;
     }();
     if (rc) { im.reset(); (void)hipGetLastError(); return rc; }     // (what failed is not left pending for the next launch)
@@ -67,13 +56,10 @@ int mrt::api::img_prepare(mrt_ctx *c)
 
 static int img_tonemap(mrt_ctx *c, const char *fn)
 {
-    Frame f;
-    if (const int rc = whole_frame(c, fn, " (the reference would panic on an empty map, src/sampler.rs:85)", f)) return rc;
+    MeanSrc S;
+    if (const int rc = whole_frame(c, fn, " (the reference would panic on an empty map, src/sampler.rs:85)", S)) return rc;
     HIP_TRY(hipEventRecord(c->ev0.get(), c->stream.get()));
-    if (c->adaptive)                          // each pixel with its tile's 1/count (tile counts of the last adaptive call)
-        HIP_TRY(launch_tonemap_tiles(f.rgb, c->img->ss.p, c->ad->counts(), c->pk.nw, c->pk.nh, c->pk.gamma, tonemap_wexp(c), c->stream.get()));
-    else
-        HIP_TRY(launch_tonemap(f.rgb, c->img->ss.p, c->pk.nw * c->pk.nh, 1.0f / (float)f.count, c->pk.gamma, tonemap_wexp(c), c->stream.get()));
+    HIP_TRY(launch_tonemap(S, c->img->ss.p, c->pk.nh, c->pk.gamma, tonemap_wexp(c), c->stream.get()));
     return MRT_OK;
 }
 
@@ -84,8 +70,8 @@ int mrt::api::img_finish(mrt_ctx *c, uint8_t *rgb8, bool resize)
     const unsigned char *src = im.ss.p;
     size_t bytes = (size_t)nw * nh * 3;
     if (resize && (rw != nw || rh != nh)) {
-        HIP_TRY(launch_lanczos_v(im.ss.p, im.tmp.p, nw, rh, im.vl.p, im.vc.p, im.vw.p, im.vcap, c->stream.get()));
-        HIP_TRY(launch_lanczos_h(im.tmp.p, im.out.p, nw, rw, rh, im.hl.p, im.hc.p, im.hw.p, im.hcap, c->stream.get()));
+        HIP_TRY(launch_lanczos_v(im.ss.p, im.tmp.p, nw, rh, im.lanczos3.v.dev(), c->stream.get()));
+        HIP_TRY(launch_lanczos_h(im.tmp.p, im.out.p, nw, rw, rh, im.lanczos3.h.dev(), c->stream.get()));
         src = im.out.p;
         bytes = (size_t)rw * rh * 3;
     }

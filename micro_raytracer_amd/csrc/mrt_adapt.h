@@ -1,5 +1,6 @@
-// mrt_adapt.h — per-pixel and per-tile bodies of the adaptive-sampling stop rule (mrt_execute_adaptive).
-// Shared by the evaluation kernel in mrt_kernels.hip and, for the CPU-side unit tests, an x86 build.
+// mrt_adapt.h — per-pixel and per-tile bodies of the adaptive-sampling stop rule (mrt_execute_adaptive), and what
+// its per-tile counts make of a frame's means: MeanSrc, the one statement of a pixel's 1/count.
+// Shared by the kernels, the host units and, for the CPU-side unit tests, an x86 build.
 //
 // A tile that has traced n samples per pixel holds A (the sum of all n) and H (the sum of its even-numbered rounds: n/2
 // samples).  Its error compares the two means, relative to the square root of the pixel's brightness:
@@ -14,6 +15,21 @@ namespace mrt {
 
 // 1/n as the tone map forms it for a count n (mrt_accum.cpp img_tonemap: 1.0f / (float)count)
 MRT_HD float adapt_recip(u32 n) { return 1.0f / (float)n; }
+
+// the 8x8 tile of pixel (x, y) in the per-tile tables of an nw pixels wide frame (fewer tiles than pixels: 32 bits hold it)
+MRT_HD u32 tile_index(u32 nw, u32 x, u32 y) { return (y >> 3) * ((nw + 7u) >> 3) + (x >> 3); }
+
+// A frame's mean radiance as every consumer of it reads it (tone map, denoisers, linear float image): sums [nh][nw][3] with one
+// 1/count, or -- tile_count not null, after an adaptive render -- with the counts of the 8x8 tiles.  Finished means: rc = 1.0f.
+struct MeanSrc {
+    const float *sums;
+    float rc;
+    const u32 *tile_count;
+    u32 nw;
+};
+
+// 1/count of pixel (x, y)
+MRT_HD float mean_rc(const MeanSrc &S, u32 x, u32 y) { return S.tile_count ? adapt_recip(S.tile_count[tile_index(S.nw, x, y)]) : S.rc; }
 
 // e_pixel of one pixel: a, h = its three A and H words; rc = adapt_recip(n), rh = adapt_recip(n / 2)
 MRT_HD float adapt_pixel_error(const float *a, const float *h, float rc, float rh)

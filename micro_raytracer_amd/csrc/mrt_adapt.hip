@@ -5,7 +5,7 @@
 //   reduce_chunks_listed  reduce_chunks over the listed tiles, into the accumulator and (even rounds) the half buffer
 //   adapt_eval            the stop rule (mrt_adapt.h) per listed tile, one wavefront per tile
 //   adapt_compact         the next tile list, in list order
-//   tonemap_tiles_u8      tonemap_u8 with each 8x8 tile's own sample count
+// (tonemap_tiles_u8, the tone map with each tile's own count, stands next to tonemap_u8 in mrt_kernels.hip)
 //
 // Build: as mrt_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -13,7 +13,6 @@
 #include "mrt_adapt.h"
 #include "mrt_kernels.h"
 #include "mrt_megakernel.h"
-#include "mrt_post.h"
 
 namespace mrt {
 
@@ -98,18 +97,6 @@ __global__ void __launch_bounds__(1024) adapt_compact(const u32 *__restrict__ li
     if (threadIdx.x == 0) *n_out = base_s;
 }
 
-// tonemap_u8 with each pixel's own count: rc = 1/count of its 8x8 wave tile
-__global__ void __launch_bounds__(256) tonemap_tiles_u8(const float *__restrict__ accum, unsigned char *__restrict__ out, const u32 *__restrict__ tile_count,
-                                                        u32 nw, u32 nh, float gamma, float wexp)
-{
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nw * nh) return;
-    const u32 y = i / nw, x = i - y * nw;
-    const float rc = adapt_recip(tile_count[(y >> 3) * ((nw + 7u) >> 3) + (x >> 3)]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = tonemap_channel(accum[(size_t)i * 3 + k], rc, gamma, wexp);
-}
-
 // ---- launchers (declared in mrt_kernels.h) ----
 hipError_t launch_pt_list(const Params &P, const TileList &TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst, hipStream_t stream)
 {
@@ -131,12 +118,6 @@ hipError_t launch_adapt_eval(const float *accum, const float *half, const u32 *l
 {
     if (n_listed) hipLaunchKernelGGL(adapt_eval, dim3(n_listed), dim3(64), 0, stream, accum, half, list, nw, nh, n, threshold, last ? 1u : 0u, keep, tile_count, tile_conv);
     hipLaunchKernelGGL(adapt_compact, dim3(1), dim3(1024), 0, stream, list, keep, n_listed, list_out, n_out);
-    return hipGetLastError();
-}
-
-hipError_t launch_tonemap_tiles(const float *accum, unsigned char *out, const u32 *tile_count, u32 nw, u32 nh, float gamma, float wexp, hipStream_t stream)
-{
-    hipLaunchKernelGGL(tonemap_tiles_u8, dim3((nw * nh + 255) / 256), dim3(256), 0, stream, accum, out, tile_count, nw, nh, gamma, wexp);
     return hipGetLastError();
 }
 

@@ -120,10 +120,10 @@ int mrt_sample_counts(mrt_ctx *c, uint32_t *counts)
 {
     if (!c || !counts) return fail(MRT_ERR_ARG, "mrt_sample_counts: null argument");
     if (const int rc = enter(c)) return rc;
-    const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u;
+    const u32 nw = c->pk.nw, nh = c->pk.nh;
     const u32 uniform = frame_of(c).count;
     for (u32 y = 0; y < nh; ++y)
-        for (u32 x = 0; x < nw; ++x) counts[(size_t)y * nw + x] = c->adaptive ? c->ad->tile_count[(y / 8u) * n_tx + x / 8u] : uniform;
+        for (u32 x = 0; x < nw; ++x) counts[(size_t)y * nw + x] = c->adaptive ? c->ad->tile_count[tile_index(nw, x, y)] : uniform;
     ok();
     return MRT_OK;
 }

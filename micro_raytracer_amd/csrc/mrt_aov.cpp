@@ -86,7 +86,7 @@ static int denoise_opts(const mrt_denoise_opts *o, const char *fn, DnOpts &r)
 int mrt::api::denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_info *info, const char *fn, const float **out)
 {
     DnOpts d;
-    Frame f;
+    MeanSrc S;
     bool cached;
     double aov_ms;
     int rc;
@@ -94,19 +94,18 @@ int mrt::api::denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_inf
     if (d.mode == MRT_DN_VARIANCE && !c->adaptive)
         return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE needs the half buffer of an adaptive render on this context since its last reset or "
                     "mrt_set_accum; for a uniform budget of n samples call mrt_execute_adaptive with threshold 0 and min_samples = max_samples = n", fn);
-    if ((rc = whole_frame(c, fn, "", f)) || (rc = aov_compute(c, cached, aov_ms))) return rc;
+    if ((rc = whole_frame(c, fn, "", S)) || (rc = aov_compute(c, cached, aov_ms))) return rc;
     Aov &a = *c->aov;
     const u32 nw = c->pk.nw, nh = c->pk.nh;
     const size_t np = (size_t)nw * nh;
     if (!a.dn.p) HIP_TRY(a.dn.alloc(np * 11u));
     float *e0 = a.dn.p, *e1 = e0 + 4u * np, *dst = e1 + 4u * np;
-    const u32 *tc = c->adaptive ? c->ad->counts() : nullptr;     // per-tile counts of the last adaptive call
     const bool env = c->pk.P.off_env != 0u;
     HIP_TRY(hipEventRecord(a.ev[0].get(), c->stream.get()));
     if (d.mode == MRT_DN_VARIANCE && d.passes != 0u)
-        HIP_TRY(launch_denoise_var(f.rgb, c->ad->half.p, tc, a.guide.p, a.albedo.p, nw, nh, d.passes, d.sv, d.sn, d.sp, d.firefly, e0, e1, dst, c->stream.get(), env));
+        HIP_TRY(launch_denoise_var(S, c->ad->half.p, a.guide.p, a.albedo.p, nh, d.passes, d.sv, d.sn, d.sp, d.firefly, e0, e1, dst, c->stream.get(), env));
     else
-        HIP_TRY(launch_denoise(f.rgb, 1.0f / (float)f.count, tc, a.guide.p, a.albedo.p, nw, nh, d.passes, d.sc, d.sn, d.sp, e0, e1, dst, c->stream.get(), env));
+        HIP_TRY(launch_denoise(S, a.guide.p, a.albedo.p, nh, d.passes, d.sc, d.sn, d.sp, e0, e1, dst, c->stream.get(), env));
     HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     float ms = 0.0f;
@@ -172,7 +171,7 @@ int mrt_img_denoised(mrt_ctx *c, const mrt_denoise_opts *o, uint8_t *rgb8, mrt_d
     int rc;
     if ((rc = denoise_run(c, o, info, "mrt_img_denoised", &dst)) || (rc = img_prepare(c))) return rc;
     HIP_TRY(hipEventRecord(c->ev0.get(), c->stream.get()));
-    HIP_TRY(launch_tonemap(dst, c->img->ss.p, c->pk.nw * c->pk.nh, 1.0f, c->pk.gamma, tonemap_wexp(c), c->stream.get()));
+    HIP_TRY(launch_tonemap(mean_src(c, dst), c->img->ss.p, c->pk.nh, c->pk.gamma, tonemap_wexp(c), c->stream.get()));
     return img_finish(c, rgb8, true);
 }
 

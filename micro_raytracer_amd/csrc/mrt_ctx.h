@@ -84,21 +84,38 @@ struct Adaptive {
     std::vector<u32> tile_count;                  // per-tile counts of the last adaptive call (host copy)
     u32 *counts() const { return tiles.p + 3u * (size_t)n_tiles; }      // ... on the device, where the tone map and the denoiser read them
 };
-// the image path (mrt_img, mrt_img_ss, mrt_img_denoised); Lanczos3 to the output resolution when it differs: the taps of both
-// passes (vl ... hcap), the vertical pass's output (tmp), the image (out)
+// One axis of a resample on the device: the tables of a ResampleTaps over n output indices, as the kernels read them (DevTaps)
+struct Taps {
+    DeviceMem<u32> left, count;
+    DeviceMem<float> weight;
+    u32 cap = 0;
+    hipError_t upload(const ResampleTaps &t, u32 n)
+    {
+        hipError_t e;
+        if ((e = left.alloc(n)) || (e = count.alloc(n)) || (e = weight.alloc((size_t)n * t.cap))) return e;
+        if ((e = hipMemcpy(left.p, t.left.data(), sizeof(u32) * n, hipMemcpyHostToDevice)) ||
+            (e = hipMemcpy(count.p, t.count.data(), sizeof(u32) * n, hipMemcpyHostToDevice)) ||
+            (e = hipMemcpy(weight.p, t.weight.data(), sizeof(float) * (size_t)n * t.cap, hipMemcpyHostToDevice))) return e;
+        cap = t.cap;
+        return hipSuccess;
+    }
+    DevTaps dev() const { return {left.p, count.p, weight.p, cap}; }
+};
+// ... and both passes of one: vertical first
+struct Resampler { Taps v, h; };
+// the image path (mrt_img, mrt_img_ss, mrt_img_denoised); Lanczos3 to the output resolution when it differs: its taps, the
+// vertical pass's output (tmp), the image (out)
 struct Image {
     DeviceMem<unsigned char> ss;                  // the tone-mapped supersampled frame [nh][nw][3]
-    DeviceMem<u32> vl, vc, hl, hc;
-    DeviceMem<float> vw, hw, tmp;
+    Resampler lanczos3;
+    DeviceMem<float> tmp;
     DeviceMem<unsigned char> out;
-    u32 vcap = 0, hcap = 0;
 };
-// the linear float image (mrt_img_hdr), created whole by the first call: the box taps of both passes (the Lanczos3
-// taps are the Image's own), the vertical pass's output, the image, the events around the call's kernels
+// the linear float image (mrt_img_hdr), created whole by the first call: the box taps (the Lanczos3 taps are the
+// Image's own), the vertical pass's output, the image, the events around the call's kernels
 struct Hdr {
-    DeviceMem<u32> vl, vc, hl, hc;
-    DeviceMem<float> vw, hw, tmp, out;            // tmp [res_h][nw][3], out [res_h][res_w][3]
-    u32 vcap = 0, hcap = 0;
+    Resampler box;
+    DeviceMem<float> tmp, out;                    // tmp [res_h][nw][3], out [res_h][res_w][3]
     Event ev[2];
 };
 // first-hit AOVs and the denoiser (mrt_aov, mrt_denoise: DESIGN.md §13), on the context's device; the AOVs depend on scene and
@@ -208,12 +225,21 @@ inline Frame frame_of(const mrt_ctx *c)
     if (c->full.p) return {c->full.p, c->full_count};
     return {c->shard_count == 1 ? c->d_accum : nullptr, c->count};
 }
-// ... for an observation of the whole frame's means (the image, the denoiser), refused without the whole frame or a sample
-inline int whole_frame(const mrt_ctx *c, const char *fn, const char *empty_note, Frame &f)
+// The means an observation reads (mrt_adapt.h MeanSrc): a plane of finished means as it is (the denoiser's output), or -- means
+// null -- that frame's sums with its 1/count, per 8x8 tile after an adaptive render (the tile counts of the last adaptive call)
+inline MeanSrc mean_src(const mrt_ctx *c, const float *means = nullptr)
 {
-    f = frame_of(c);
+    if (means) return {means, 1.0f, nullptr, c->pk.nw};
+    const Frame f = frame_of(c);
+    return {f.rgb, adapt_recip(f.count), c->adaptive ? c->ad->counts() : nullptr, c->pk.nw};
+}
+// ... of the whole frame (the image, the denoiser, the float image), refused without the whole frame or a sample
+inline int whole_frame(const mrt_ctx *c, const char *fn, const char *empty_note, MeanSrc &S)
+{
+    const Frame f = frame_of(c);
     if (!f.rgb) return fail(MRT_ERR_STATE, "%s: this context holds only its own rows; gather and mrt_set_accum first", fn);
     if (f.count == 0) return fail(MRT_ERR_STATE, "%s: no samples accumulated%s", fn, empty_note);
+    S = mean_src(c);
     return MRT_OK;
 }
 

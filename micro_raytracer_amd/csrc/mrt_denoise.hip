@@ -33,19 +33,13 @@ __global__ void __launch_bounds__(256) aov_first_hit(const Params P, float4 *__r
     ids[2 * p] = a.rend; ids[2 * p + 1] = a.inst;
 }
 
-// 1/count of pixel (x, y): the uniform rc, or its 8x8 tile's count (adaptive renders; mrt_adapt.h adapt_recip)
-__device__ inline float dn_rc(float rc, const u32 *tile_count, u32 nw, u32 x, u32 y)
-{
-    return tile_count ? 1.0f / (float)tile_count[(y >> 3) * ((nw + 7u) >> 3) + (x >> 3)] : rc;
-}
-
 __global__ void __launch_bounds__(256) dn_mean(const float *__restrict__ accum, float rc, const u32 *__restrict__ tile_count, u32 nw, u32 nh,
                                                float *__restrict__ out)
 {
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= nw * nh) return;
     const u32 y = i / nw, x = i - y * nw;
-    const float r = dn_rc(rc, tile_count, nw, x, y);
+    const float r = mean_rc({accum, rc, tile_count, nw}, x, y);
     for (u32 k = 0; k < 3u; ++k) out[(size_t)i * 3 + k] = accum[(size_t)i * 3 + k] * r;
 }
 
@@ -56,7 +50,7 @@ struct DnPassArgs {
     const float4 *e_in;                // not first: e of the previous pass, one float4 per pixel
     const float *accum;                // first: the accumulator [nh][nw][3] ...
     float rc;                          // ... with this 1/count, or
-    const u32 *tile_count;             // ... per 8x8 tile counts (adaptive; null: rc)
+    const u32 *tile_count;             // ... per 8x8 tile counts (adaptive; null: rc): with nw, the fields of a MeanSrc (mrt_adapt.h)
     const float *albedo;               // [nh][nw][3]
     const float4 *guide;               // [2][nh][nw]: (n, t), (x, hit)
     float4 *e_out;                     // not last
@@ -93,11 +87,12 @@ hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo
     return hipGetLastError();
 }
 
-hipError_t launch_denoise(const float *accum, float rc, const u32 *tile_count, const float *guide, const float *albedo, u32 nw, u32 nh, u32 passes,
+hipError_t launch_denoise(const MeanSrc &S, const float *guide, const float *albedo, u32 nh, u32 passes,
                           float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env)
 {
+    const u32 nw = S.nw;
     if (passes == 0u) {
-        hipLaunchKernelGGL(dn_mean, dim3((unsigned)(((size_t)nw * nh + 255u) / 256u)), dim3(256), 0, stream, accum, rc, tile_count, nw, nh, out);
+        hipLaunchKernelGGL(dn_mean, dim3((unsigned)(((size_t)nw * nh + 255u) / 256u)), dim3(256), 0, stream, S.sums, S.rc, S.tile_count, nw, nh, out);
         return hipGetLastError();
     }
     float4 *buf[2] = {reinterpret_cast<float4 *>(e0), reinterpret_cast<float4 *>(e1)};
@@ -109,7 +104,7 @@ hipError_t launch_denoise(const float *accum, float rc, const u32 *tile_count, c
         A.first = i == 0u; A.last = i + 1u == passes;
         A.sc = dn_pass_sc(sc, i); A.sn = sn; A.sp = sp;
         A.e_in = buf[(i + 1u) & 1u]; A.e_out = buf[i & 1u];
-        A.accum = accum; A.rc = rc; A.tile_count = tile_count;
+        A.accum = S.sums; A.rc = S.rc; A.tile_count = S.tile_count;
         A.albedo = albedo; A.guide = reinterpret_cast<const float4 *>(guide);
         A.out = out;
         // sub-images of a class are at most ceil(n / s) wide / high

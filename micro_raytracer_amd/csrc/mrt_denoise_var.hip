@@ -30,8 +30,6 @@ struct DnvArgs {
 
 constexpr u32 kDnvB = 16, kDnvT1 = kDnvB + 2, kDnvT3 = kDnvB + 6, kDnvT = kDnvB + 4;
 
-__device__ inline u32 dnv_count(const u32 *tile_count, u32 nw, u32 x, u32 y) { return tile_count[(y >> 3) * ((nw + 7u) >> 3) + (x >> 3)]; }
-
 __device__ inline DnGuide dnv_guide_of(float4 a, float4 b)
 {
     DnGuide g;
@@ -54,7 +52,7 @@ __global__ void __launch_bounds__(256) dnv_prep(const DnvArgs A)
             const float a[3] = {A.accum[3 * p], A.accum[3 * p + 1], A.accum[3 * p + 2]};
             const float alb[3] = {A.albedo[3 * p], A.albedo[3 * p + 1], A.albedo[3 * p + 2]};
             float m[3];
-            dnv_mean(a, alb, hit, dnv_count(A.tile_count, A.nw, (u32)fx, (u32)fy), env, m);
+            dnv_mean(a, alb, hit, A.tile_count[tile_index(A.nw, (u32)fx, (u32)fy)], env, m);
             e = make_float4(m[0], m[1], m[2], hit);
         }
         s_e[t] = e;
@@ -84,7 +82,7 @@ __global__ void __launch_bounds__(256) dnv_prep(const DnvArgs A)
     const float a[3] = {A.accum[3 * p], A.accum[3 * p + 1], A.accum[3 * p + 2]};
     const float h[3] = {A.half[3 * p], A.half[3 * p + 1], A.half[3 * p + 2]};
     const float alb[3] = {A.albedo[3 * p], A.albedo[3 * p + 1], A.albedo[3 * p + 2]};
-    const float h2 = dnv_h2(a, h, alb, ep4.w, dnv_count(A.tile_count, A.nw, x, y), env);
+    const float h2 = dnv_h2(a, h, alb, ep4.w, A.tile_count[tile_index(A.nw, x, y)], env);
     A.out[p] = make_float4(e[0], e[1], e[2], h2);
 }
 
@@ -196,16 +194,17 @@ __global__ void __launch_bounds__(256) dnv_pass(const DnvPassArgs A)
 }
 
 // ---- launcher (declared in mrt_kernels.h) ----
-hipError_t launch_denoise_var(const float *accum, const float *half, const u32 *tile_count, const float *guide, const float *albedo, u32 nw, u32 nh,
-                              u32 passes, float sv, float sn, float sp, float firefly, float *e0, float *e1, float *out, hipStream_t stream, bool env)
+hipError_t launch_denoise_var(const MeanSrc &S, const float *half, const float *guide, const float *albedo, u32 nh, u32 passes,
+                              float sv, float sn, float sp, float firefly, float *e0, float *e1, float *out, hipStream_t stream, bool env)
 {
-    if (passes == 0u || !half || !tile_count) return hipErrorInvalidValue;
+    if (passes == 0u || !half || !S.tile_count) return hipErrorInvalidValue;
+    const u32 nw = S.nw;
     float4 *buf[2] = {reinterpret_cast<float4 *>(e0), reinterpret_cast<float4 *>(e1)};
     const dim3 frame((nw + kDnvB - 1u) / kDnvB, (nh + kDnvB - 1u) / kDnvB);
     DnvArgs V;
     V.nw = nw; V.nh = nh; V.env = env ? 1u : 0u;
     V.f = firefly; V.sn = sn; V.sp = sp;
-    V.accum = accum; V.half = half; V.tile_count = tile_count; V.albedo = albedo;
+    V.accum = S.sums; V.half = half; V.tile_count = S.tile_count; V.albedo = albedo;
     V.guide = reinterpret_cast<const float4 *>(guide);
     V.in = nullptr; V.out = buf[0];
     hipLaunchKernelGGL(dnv_prep, frame, dim3(256), 0, stream, V);

@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(256) dn_pass(const DnPassArgs A)
             g0 = A.guide[p];
             g1 = A.guide[np + p];
             if (A.first) {
-                const float r = dn_rc(A.rc, A.tile_count, A.nw, (u32)fx, (u32)fy);
+                const float r = mean_rc({A.accum, A.rc, A.tile_count, A.nw}, (u32)fx, (u32)fy);
                 e.x = (A.accum[3 * p] * r) / dn_demod(A.albedo[3 * p], g1.w, MRT_DN_ENV != 0);
                 e.y = (A.accum[3 * p + 1] * r) / dn_demod(A.albedo[3 * p + 1], g1.w, MRT_DN_ENV != 0);
                 e.z = (A.accum[3 * p + 2] * r) / dn_demod(A.albedo[3 * p + 2], g1.w, MRT_DN_ENV != 0);

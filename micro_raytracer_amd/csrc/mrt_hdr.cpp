@@ -29,20 +29,9 @@ static int hdr_prepare(mrt_ctx *c)
         ResampleTaps v, h;
         box_taps(nh, rh, v);
         box_taps(nw, rw, h);
-        HIP_TRY(hd->vl.alloc(rh));
-        HIP_TRY(hd->vc.alloc(rh));
-        HIP_TRY(hd->vw.alloc((size_t)rh * v.cap));
-        HIP_TRY(hd->hl.alloc(rw));
-        HIP_TRY(hd->hc.alloc(rw));
-        HIP_TRY(hd->hw.alloc((size_t)rw * h.cap));
-        HIP_TRY(hipMemcpy(hd->vl.p, v.left.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(hd->vc.p, v.count.data(), sizeof(u32) * rh, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(hd->vw.p, v.weight.data(), sizeof(float) * (size_t)rh * v.cap, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(hd->hl.p, h.left.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(hd->hc.p, h.count.data(), sizeof(u32) * rw, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(hd->hw.p, h.weight.data(), sizeof(float) * (size_t)rw * h.cap, hipMemcpyHostToDevice));
+        HIP_TRY(hd->box.v.upload(v, rh));
+        HIP_TRY(hd->box.h.upload(h, rw));
         HIP_TRY(hd->tmp.alloc((size_t)nw * rh * 3));
-        hd->vcap = v.cap; hd->hcap = h.cap;
         return MRT_OK;
     }();
     if (rc) { hd.reset(); (void)hipGetLastError(); return rc; }
@@ -110,34 +99,27 @@ int mrt_img_hdr(mrt_ctx *c, const mrt_hdr_opts *o, float *rgb, mrt_hdr_info *inf
     for (int k = 0; k < 4; ++k) if (o->reserved[k]) return fail(MRT_ERR_ARG, "mrt_img_hdr: reserved[%d] must be 0", k);
     mrt_hdr_info hi;
     memset(&hi, 0, sizeof hi);
-    // the source: the filtered means as they are, or the sums with the context's 1/count (per tile after an adaptive render)
-    const float *src = nullptr;
-    float rcount = 1.0f;
-    const u32 *tc = nullptr;
+    // the source: the filtered means as they are, or the frame's sums and their 1/count
+    MeanSrc S;
     int rc;
     if (o->denoise) {
-        if ((rc = denoise_run(c, o->denoise, &hi.dn, "mrt_img_hdr", &src))) return rc;
+        const float *dn = nullptr;
+        if ((rc = denoise_run(c, o->denoise, &hi.dn, "mrt_img_hdr", &dn))) return rc;
+        S = mean_src(c, dn);
     } else {
-        Frame f;
-        if ((rc = enter(c)) || (rc = whole_frame(c, "mrt_img_hdr", "", f))) return rc;
-        src = f.rgb;
-        rcount = 1.0f / (float)f.count;
-        if (c->adaptive) tc = c->ad->counts();
+        if ((rc = enter(c)) || (rc = whole_frame(c, "mrt_img_hdr", "", S))) return rc;
     }
     if ((rc = img_prepare(c)) || (rc = hdr_prepare(c))) return rc;
     const u32 nw = c->pk.nw, nh = c->pk.nh, rw = c->pk.res_w, rh = c->pk.res_h;
-    const Image &im = *c->img;
     Hdr &hd = *c->hdr;
     hipStream_t st = c->stream.get();
     if (c->event_timing) HIP_TRY(hipEventRecord(hd.ev[0].get(), st));
     if (rw == nw && rh == nh) {
-        HIP_TRY(launch_hdr_copy(src, rcount, tc, hd.out.p, nw, nh, st));
-    } else if (o->filter == MRT_RESIZE_BOX) {
-        HIP_TRY(launch_hdr_v(src, rcount, tc, hd.tmp.p, nw, rh, hd.vl.p, hd.vc.p, hd.vw.p, hd.vcap, st));
-        HIP_TRY(launch_hdr_h(hd.tmp.p, hd.out.p, nw, rw, rh, hd.hl.p, hd.hc.p, hd.hw.p, hd.hcap, st));
-    } else {                                      // the taps of mrt_img
-        HIP_TRY(launch_hdr_v(src, rcount, tc, hd.tmp.p, nw, rh, im.vl.p, im.vc.p, im.vw.p, im.vcap, st));
-        HIP_TRY(launch_hdr_h(hd.tmp.p, hd.out.p, nw, rw, rh, im.hl.p, im.hc.p, im.hw.p, im.hcap, st));
+        HIP_TRY(launch_hdr_copy(S, hd.out.p, nh, st));
+    } else {                                      // Lanczos3: the taps of mrt_img
+        const Resampler &r = o->filter == MRT_RESIZE_BOX ? hd.box : c->img->lanczos3;
+        HIP_TRY(launch_hdr_v(S, hd.tmp.p, rh, r.v.dev(), st));
+        HIP_TRY(launch_hdr_h(hd.tmp.p, hd.out.p, nw, rw, rh, r.h.dev(), st));
     }
     if (c->event_timing) HIP_TRY(hipEventRecord(hd.ev[1].get(), st));
     HIP_TRY(hipStreamSynchronize(st));

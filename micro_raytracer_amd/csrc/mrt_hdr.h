@@ -14,18 +14,14 @@
 
 namespace mrt {
 
-// What the vertical pass reads: sums [nh][nw][3] with one 1/count, or with the counts of the 8x8 tiles (tile_count not null)
-struct HdrSrc {
-    const float *sums;
-    float rc;
-    const u32 *tile_count;
-    u32 nw;
-};
+// What the vertical pass reads is the MeanSrc of mrt_adapt.h (the sums and their 1/count); the x86 probe of the tests
+// (tests/emu/hdr_probe.cpp) names it as the float image's own
+using HdrSrc = MeanSrc;
 
 // m of element e = x * 3 + c of source row y
-MRT_HD float hdr_mean(const HdrSrc &S, u32 y, u32 e)
+MRT_HD float hdr_mean(const MeanSrc &S, u32 y, u32 e)
 {
-    const float rc = S.tile_count ? adapt_recip(S.tile_count[(size_t)(y >> 3) * ((S.nw + 7u) >> 3) + ((e / 3u) >> 3)]) : S.rc;
+    const float rc = mean_rc(S, e / 3u, y);
     return S.sums[(size_t)y * S.nw * 3u + e] * rc;
 }
 
@@ -34,7 +30,7 @@ MRT_HD float hdr_clamp(float u) { return u > 0.0f ? u : 0.0f; }
 // t[oy0 .. oy0 + R)[e] of the vertical pass, rows past dh left out: one walk over the source rows the R outputs span, each mean
 // formed once and added to every output whose taps hold that row -- per output still its own taps in index order from +0.0f.
 template <u32 R>
-MRT_HD void hdr_vertical(const HdrSrc &S, u32 e, u32 oy0, u32 dh, const u32 *left, const u32 *count, const float *weight, u32 cap, float *t)
+MRT_HD void hdr_vertical(const MeanSrc &S, u32 e, u32 oy0, u32 dh, const u32 *left, const u32 *count, const float *weight, u32 cap, float *t)
 {
     u32 l[R], n[R];
     u32 lo = 0xffffffffu, hi = 0u;

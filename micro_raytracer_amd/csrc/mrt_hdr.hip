@@ -17,7 +17,7 @@ namespace mrt {
 constexpr u32 kHdrRows = 4;
 
 template <u32 R>
-__global__ void __launch_bounds__(256) hdr_v(HdrSrc S, float *__restrict__ dst, u32 dh, const u32 *__restrict__ left, const u32 *__restrict__ count,
+__global__ void __launch_bounds__(256) hdr_v(MeanSrc S, float *__restrict__ dst, u32 dh, const u32 *__restrict__ left, const u32 *__restrict__ count,
                                              const float *__restrict__ weight, u32 cap)
 {
     const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(256) hdr_h(const float *__restrict__ src, floa
     q[0] = o[0]; q[1] = o[1]; q[2] = o[2];
 }
 
-__global__ void __launch_bounds__(256) hdr_copy(HdrSrc S, float *__restrict__ dst, u32 nh)
+__global__ void __launch_bounds__(256) hdr_copy(MeanSrc S, float *__restrict__ dst, u32 nh)
 {
     const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 y = blockIdx.y;
@@ -51,26 +51,22 @@ __global__ void __launch_bounds__(256) hdr_copy(HdrSrc S, float *__restrict__ ds
 }
 
 // ---- launchers (declared in mrt_kernels.h) ----
-hipError_t launch_hdr_v(const float *sums, float rc, const u32 *tile_count, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,
-                        const float *weight, u32 cap, hipStream_t stream)
+hipError_t launch_hdr_v(const MeanSrc &S, float *dst, u32 dh, const DevTaps &v, hipStream_t stream)
 {
-    const HdrSrc S = {sums, rc, tile_count, sw};
-    hipLaunchKernelGGL((hdr_v<kHdrRows>), dim3((sw * 3u + 255u) / 256u, (dh + kHdrRows - 1u) / kHdrRows), dim3(256), 0, stream, S, dst, dh, left, count,
-                       weight, cap);
+    hipLaunchKernelGGL((hdr_v<kHdrRows>), dim3((S.nw * 3u + 255u) / 256u, (dh + kHdrRows - 1u) / kHdrRows), dim3(256), 0, stream, S, dst, dh, v.left,
+                       v.count, v.weight, v.cap);
     return hipGetLastError();
 }
 
-hipError_t launch_hdr_h(const float *src, float *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count, const float *weight, u32 cap,
-                        hipStream_t stream)
+hipError_t launch_hdr_h(const float *src, float *dst, u32 sw, u32 dw, u32 dh, const DevTaps &h, hipStream_t stream)
 {
-    hipLaunchKernelGGL(hdr_h, dim3((dw + 255u) / 256u, dh), dim3(256), 0, stream, src, dst, sw, dw, dh, left, count, weight, cap);
+    hipLaunchKernelGGL(hdr_h, dim3((dw + 255u) / 256u, dh), dim3(256), 0, stream, src, dst, sw, dw, dh, h.left, h.count, h.weight, h.cap);
     return hipGetLastError();
 }
 
-hipError_t launch_hdr_copy(const float *sums, float rc, const u32 *tile_count, float *dst, u32 nw, u32 nh, hipStream_t stream)
+hipError_t launch_hdr_copy(const MeanSrc &S, float *dst, u32 nh, hipStream_t stream)
 {
-    const HdrSrc S = {sums, rc, tile_count, nw};
-    hipLaunchKernelGGL(hdr_copy, dim3((nw * 3u + 255u) / 256u, nh), dim3(256), 0, stream, S, dst, nh);
+    hipLaunchKernelGGL(hdr_copy, dim3((S.nw * 3u + 255u) / 256u, nh), dim3(256), 0, stream, S, dst, nh);
     return hipGetLastError();
 }
 

@@ -2,10 +2,19 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include "mrt_adapt.h"     // MeanSrc: the means the image, denoiser and float-image launchers read
 #include "mrt_inst.h"      // pt_instantiation: FEAT template argument of the kernel launch_pt picks; pt_lds_bytes
 #include "mrt_scene.h"
 
 namespace mrt {
+
+// One axis of a resample on the device: per output index its first source index and tap count, `cap` weights each
+// (mrt_pack.h ResampleTaps, uploaded)
+struct DevTaps {
+    const u32 *left, *count;
+    const float *weight;
+    u32 cap;
+};
 
 hipError_t configure_pt(size_t max_lds_bytes);
 hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 features, hipStream_t stream, const TileList *list = nullptr);
@@ -17,28 +26,23 @@ hipError_t launch_reduce_chunks_listed(float *accum, float *half, const float *p
                                        size_t stride, u32 n_chunks, hipStream_t stream);
 hipError_t launch_adapt_eval(const float *accum, const float *half, const u32 *list, u32 n_listed, u32 nw, u32 nh, u32 n, float threshold, bool last,
                              u32 *keep, u32 *tile_count, u32 *tile_conv, u32 *list_out, u32 *n_out, hipStream_t stream);
-hipError_t launch_tonemap_tiles(const float *accum, unsigned char *out, const u32 *tile_count, u32 nw, u32 nh, float gamma, float wexp, hipStream_t stream);
 // mrt_denoise.hip: first-hit AOVs (guide [2][nh][nw] float4, albedo [nh][nw][3], ids [nh][nw][2]) and the a-trous passes
 hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo, i32 *ids, hipStream_t stream);
-hipError_t launch_denoise(const float *accum, float rc, const u32 *tile_count, const float *guide, const float *albedo, u32 nw, u32 nh, u32 passes,
+hipError_t launch_denoise(const MeanSrc &S, const float *guide, const float *albedo, u32 nh, u32 passes,
                           float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env = false);   // env: the context has an environment texture
-// mrt_denoise_var.hip: the variance-guided mode, passes >= 1; half: the adaptive half buffer, tile_count not null
-hipError_t launch_denoise_var(const float *accum, const float *half, const u32 *tile_count, const float *guide, const float *albedo, u32 nw, u32 nh,
-                              u32 passes, float sv, float sn, float sp, float firefly, float *e0, float *e1, float *out, hipStream_t stream, bool env);
+// mrt_denoise_var.hip: the variance-guided mode, passes >= 1; half: the adaptive half buffer, S.tile_count not null
+hipError_t launch_denoise_var(const MeanSrc &S, const float *half, const float *guide, const float *albedo, u32 nh, u32 passes,
+                              float sv, float sn, float sp, float firefly, float *e0, float *e1, float *out, hipStream_t stream, bool env);
 hipError_t launch_scatter_rows(float *frame, const float *gathered, const u32 *rowmap, u32 n_rows, u32 row_words, hipStream_t stream);
-hipError_t launch_tonemap(const float *accum, unsigned char *out, u32 n_px, float rc, float gamma, float wexp, hipStream_t stream);
-hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,
-                            const float *weight, u32 cap, hipStream_t stream);
-hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count,
-                            const float *weight, u32 cap, hipStream_t stream);
-// mrt_hdr.hip: the linear float image (mrt_img_hdr): the means sums * rc (per-tile counts when tile_count is not null) through the
-// vertical pass into dst [dh][sw][3], that through the horizontal pass and the clamp at 0 into dst [dh][dw][3]; without a resize
-// the clamped means [nh][nw][3]
-hipError_t launch_hdr_v(const float *sums, float rc, const u32 *tile_count, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,
-                        const float *weight, u32 cap, hipStream_t stream);
-hipError_t launch_hdr_h(const float *src, float *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count, const float *weight, u32 cap,
-                        hipStream_t stream);
-hipError_t launch_hdr_copy(const float *sums, float rc, const u32 *tile_count, float *dst, u32 nw, u32 nh, hipStream_t stream);
+// the tone map of the means of S [nh][S.nw][3]: tonemap_u8, or tonemap_tiles_u8 when S has per-tile counts
+hipError_t launch_tonemap(const MeanSrc &S, unsigned char *out, u32 nh, float gamma, float wexp, hipStream_t stream);
+hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh, const DevTaps &v, hipStream_t stream);
+hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw, u32 dh, const DevTaps &h, hipStream_t stream);
+// mrt_hdr.hip: the linear float image (mrt_img_hdr): the means of S [.][S.nw][3] through the vertical pass into dst [dh][S.nw][3],
+// that through the horizontal pass and the clamp at 0 into dst [dh][dw][3]; without a resize the clamped means [nh][S.nw][3]
+hipError_t launch_hdr_v(const MeanSrc &S, float *dst, u32 dh, const DevTaps &v, hipStream_t stream);
+hipError_t launch_hdr_h(const float *src, float *dst, u32 sw, u32 dw, u32 dh, const DevTaps &h, hipStream_t stream);
+hipError_t launch_hdr_copy(const MeanSrc &S, float *dst, u32 nh, hipStream_t stream);
 // mrt_rayq.hip: the ray-query test hook (mrt_selftest_trace), instantiation `inst` at 256 threads with `lds` bytes of LDS; n rays,
 // out [n][MRT_TRACE_WORDS].  rayq_has: that instantiation exists
 hipError_t launch_rayq(const Params &P, bool scene_in_lds, u32 inst, size_t lds, u32 n, const float *orig, const float *dir, u32 *out, hipStream_t stream);

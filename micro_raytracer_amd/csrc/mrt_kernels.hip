@@ -4,7 +4,7 @@
 //                    it reaches: one lane per supersampled pixel, all samples of the launch in
 //                    registers, scene staged in LDS, one accumulator read-modify-write per launch.
 //   (pt_megakernel_list, the same over a list of 8x8 tiles, and the other kernels of adaptive sampling: mrt_adapt.hip)
-//   tonemap_u8       Sampler::img's per-pixel map (src/sampler.rs:84-96)
+//   tonemap_u8       Sampler::img's per-pixel map (src/sampler.rs:84-96); tonemap_tiles_u8: with each 8x8 tile's own sample count
 //   lanczos3_v/_h    image::imageops::resize(.., Lanczos3) (src/sampler.rs:98): vertical pass to f32,
 //                    horizontal pass to u8, taps precomputed on the host.
 //   math_selftest    elementwise device math contract, for the parity tests.
@@ -51,6 +51,18 @@ __global__ void __launch_bounds__(256) tonemap_u8(const float *__restrict__ accu
 {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_px) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = tonemap_channel(accum[(size_t)i * 3 + k], rc, gamma, wexp);
+}
+
+// tonemap_u8 with each pixel's own count: rc = 1/count of its 8x8 wave tile (adaptive renders)
+__global__ void __launch_bounds__(256) tonemap_tiles_u8(const float *__restrict__ accum, unsigned char *__restrict__ out, const u32 *__restrict__ tile_count,
+                                                        u32 nw, u32 nh, float gamma, float wexp)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nw * nh) return;
+    const u32 y = i / nw, x = i - y * nw;
+    const float rc = adapt_recip(tile_count[tile_index(nw, x, y)]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = tonemap_channel(accum[(size_t)i * 3 + k], rc, gamma, wexp);
 }
@@ -193,23 +205,23 @@ hipError_t launch_scatter_rows(float *frame, const float *gathered, const u32 *r
     return hipGetLastError();
 }
 
-hipError_t launch_tonemap(const float *accum, unsigned char *out, u32 n_px, float rc, float gamma, float wexp, hipStream_t stream)
+hipError_t launch_tonemap(const MeanSrc &S, unsigned char *out, u32 nh, float gamma, float wexp, hipStream_t stream)
 {
-    hipLaunchKernelGGL(tonemap_u8, dim3((n_px + 255) / 256), dim3(256), 0, stream, accum, out, n_px, rc, gamma, wexp);
+    const u32 n_px = S.nw * nh;
+    if (S.tile_count) hipLaunchKernelGGL(tonemap_tiles_u8, dim3((n_px + 255) / 256), dim3(256), 0, stream, S.sums, out, S.tile_count, S.nw, nh, gamma, wexp);
+    else hipLaunchKernelGGL(tonemap_u8, dim3((n_px + 255) / 256), dim3(256), 0, stream, S.sums, out, n_px, S.rc, gamma, wexp);
     return hipGetLastError();
 }
 
-hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh, const u32 *left, const u32 *count,
-                            const float *weight, u32 cap, hipStream_t stream)
+hipError_t launch_lanczos_v(const unsigned char *src, float *dst, u32 sw, u32 dh, const DevTaps &v, hipStream_t stream)
 {
-    hipLaunchKernelGGL(lanczos3_v, dim3((sw * 3u + 255) / 256, dh), dim3(256), 0, stream, src, dst, sw, dh, left, count, weight, cap);
+    hipLaunchKernelGGL(lanczos3_v, dim3((sw * 3u + 255) / 256, dh), dim3(256), 0, stream, src, dst, sw, dh, v.left, v.count, v.weight, v.cap);
     return hipGetLastError();
 }
 
-hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw, u32 dh, const u32 *left, const u32 *count,
-                            const float *weight, u32 cap, hipStream_t stream)
+hipError_t launch_lanczos_h(const float *src, unsigned char *dst, u32 sw, u32 dw, u32 dh, const DevTaps &h, hipStream_t stream)
 {
-    hipLaunchKernelGGL(lanczos3_h, dim3((dw + 255) / 256, dh), dim3(256), 0, stream, src, dst, sw, dw, dh, left, count, weight, cap);
+    hipLaunchKernelGGL(lanczos3_h, dim3((dw + 255) / 256, dh), dim3(256), 0, stream, src, dst, sw, dw, dh, h.left, h.count, h.weight, h.cap);
     return hipGetLastError();
 }
 

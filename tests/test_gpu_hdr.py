@@ -80,6 +80,34 @@ def test_adaptive_render_uses_per_tile_counts(oracle_mod):
     s.close()
 
 
+def test_consumers_of_one_accumulator_agree_on_every_count():
+    """Tone map, denoiser, float image and mrt_sample_counts read one frame of sums through one statement of a pixel's 1/count
+    (csrc/mrt_adapt.h MeanSrc): on a 13x11 frame -- 2x2 tiles, the right column 5 pixels wide, the bottom row 3 high -- whose
+    tiles stop at different counts they give the same means, bit for bit.  Threshold 0.35: on the x86 build (tests/emu render,
+    np_tile_errors) the tile errors are 0.451, 0.327, 0.486, 0.436 at 64 samples and 0.403, -, 0.397, 0.272 at 96, none below
+    0.45 at 32: counts 128, 64, 128, 96."""
+    from micro_raytracer_amd import Sampler, scenes
+    render, _ = make_holder(scenes.cornell_box(res=(13, 11), sample=AD_MAX, bounce=8))
+    s = Sampler(seed=AD_SEED, device=0)
+    s.execute_adaptive(render, 0.35, min_samples=AD_MIN, max_samples=AD_MAX, step=AD_STEP)
+    assert (s.nw, s.nh) == (13, 11)
+    sums, counts = s.accum()[0], s.sample_counts()
+    print("tile counts", counts[::8, ::8].tolist())
+    assert counts.shape == (11, 13) and len(np.unique(counts)) >= 2, np.unique(counts)
+    for ty in range(2):                                           # one count per 8x8 tile, the partial ones included
+        for tx in range(2):
+            assert len(np.unique(counts[8 * ty:8 * ty + 8, 8 * tx:8 * tx + 8])) == 1
+    mean = sums * (f32(1.0) / counts.astype(f32))[..., None]
+    assert mean.dtype == f32
+    assert H.same(s.denoise(passes=0), mean)
+    hdr = s.img_hdr()
+    assert H.same(hdr, np.where(mean > 0, mean, f32(0.0)))
+    assert H.same(s.img_hdr(filter="box"), hdr)                   # no resize: the filter does not matter
+    assert np.array_equal(s.img_ss(), s.img_denoised(passes=0))
+    assert np.array_equal(s.img(), s.img_ss())                    # output size = supersampled size
+    s.close()
+
+
 # ---- the denoised source -----------------------------------------------------------------------------------------------------------
 def test_denoised_source(oracle_mod):
     from micro_raytracer_amd import Sampler, scenes
