@@ -488,17 +488,36 @@ MRT_HD RayPre ray_pre(V3 o, V3 d)
 // The slab test runs on the box grown by a margin mg: t = (c - o) * inv -+ (h + mg) * |inv| per axis, with the
 // reciprocal direction clamped to +-1e30 (a zero component then reads as "parallel": no constraint inside the slab,
 // a sure miss outside) -- coordinates on this route are bounded by 1e6, so nothing overflows and no NaN can arise.
+// ONE margin per ray, so the ray is kept as inv = 1 / d (clamped), ainv = |inv|, oinv = o * inv, qm = margin * |inv|, and a
+// step is six FMAs:  t = c * inv - o * inv -+ (h * |inv| + mg * |inv|)
 struct CullRay {
-    V3 o, inv, ainv;
+    V3 inv, ainv, oinv, qm;
 };
 MRT_HD float clamp_inv(float d) { return fmin_(fmax_(rcp_fast(d), -1e30f), 1e30f); }
-MRT_HD CullRay cull_ray(V3 o, V3 d)
+// (in two steps: the reciprocals are stated before the margin is worked out, the origin's and the margin's products after it --
+// the order every culling kernel was measured with)
+MRT_HD CullRay cull_ray(V3 d)
 {
     CullRay c;
-    c.o = o;
     c.inv = v3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
     c.ainv = v3(fabs_(c.inv.x), fabs_(c.inv.y), fabs_(c.inv.z));
     return c;
+}
+MRT_HD void cull_from(CullRay &c, V3 o, float mg) { c.oinv = hadam(o, c.inv); c.qm = muls(c.ainv, mg); }
+// the slab step of every culling walk (instance BVH, binary and 4-wide triangle BVH): box (c, h) against the ray; tn = where
+// the ray enters the grown box
+MRT_HD bool cull_hit(const CullRay &R, float cx, float cy, float cz, float hx, float hy, float hz, float &tn)
+{
+    const float px = fma_fast(cx, R.inv.x, -R.oinv.x), py = fma_fast(cy, R.inv.y, -R.oinv.y), pz = fma_fast(cz, R.inv.z, -R.oinv.z);
+    const float qx = fma_fast(hx, R.ainv.x, R.qm.x), qy = fma_fast(hy, R.ainv.y, R.qm.y), qz = fma_fast(hz, R.ainv.z, R.qm.z);
+    tn = fmax_(fmax_(px - qx, py - qy), pz - qz);
+    const float tf = fmin_(fmin_(px + qx, py + qy), pz + qz);
+    return !(tn > tf || tf < 0.0f);
+}
+MRT_HD bool cull_hit(const CullRay &R, float cx, float cy, float cz, float hx, float hy, float hz)
+{
+    float tn;
+    return cull_hit(R, cx, cy, cz, hx, hy, hz, tn);
 }
 MRT_HD bool cull_ok(V3 o, float dd)     // finite origin within the bounded range, unit-length finite direction
 {
@@ -529,13 +548,15 @@ MRT_HD float cull_margin(float k, float kpos, V3 r, V3 h, float big)
     const float ext = fmax_(fmax_(fabs_(r.x) + h.x, fabs_(r.y) + h.y), fabs_(r.z) + h.z);
     return fma_fast(k, ext, fma_fast(kpos, big, 1e-6f * MRT_MARGIN_SCALE));
 }
-MRT_HD bool cull_slab(const CullRay &R, V3 r, V3 h, float mg, float &tn)
+// the ray of a triangle-BVH walk, in mesh coordinates (ol = origin - pos): one culling margin per ray, from the mesh bounds
+MRT_HD CullRay tri_cull_ray(const float *M, V3 pos, V3 ol, V3 rd)
 {
-    const V3 p = hadam(r, R.inv);
-    const V3 q = hadam(v3(h.x + mg, h.y + mg, h.z + mg), R.ainv);
-    tn = fmax_(fmax_(p.x - q.x, p.y - q.y), p.z - q.z);
-    const float tf = fmin_(fmin_(p.x + q.x, p.y + q.y), p.z + q.z);
-    return !(tn > tf || tf < 0.0f);
+    CullRay R = cull_ray(rd);
+    const V3 c = ld3(M, MESH_BC), hh = ld3(M, MESH_BH);
+    const float big = fmax_(fmax_(fabs_(pos.x), fabs_(pos.y)), fabs_(pos.z)) + fmax_(fmax_(fabs_(c.x) + hh.x, fabs_(c.y) + hh.y), fabs_(c.z) + hh.z)
+                      + fmax_(fmax_(fabs_(ol.x), fabs_(ol.y)), fabs_(ol.z));
+    cull_from(R, ol, cull_margin(kMarginTri, kMarginPosTri, sub(c, ol), hh, big));
+    return R;
 }
 
 // The reference's own walk, src/rt.rs:740-772: for rays the triangle BVH must not cull (non-finite, non-unit) and meshes
@@ -597,16 +618,54 @@ MRT_HD bool mesh_isect_ref(const Scn &S, u32 mesh, V3 ro, V3 rd, V3 m, V3 pos, f
 // test runs on those, and a hit triangle counts iff the reference's octree walk would have listed it (membership + parent
 // tables, exact box tests).  The candidate set, and with it the answer, does not depend on the order of the tests.
 
-// the conservative slab test of the triangle BVHs: box (c, h) in mesh coordinates against a ray given as inv = 1 / d (clamped),
-// ainv = |inv|, oinv = o * inv, qm = margin * |inv|:  t = c * inv - o * inv -+ (h * |inv| + mg * |inv|)
-struct TriCull { V3 inv, ainv, oinv, qm; };
-MRT_HD bool tri_cull_hit(const TriCull &R, float cx, float cy, float cz, float hx, float hy, float hz)
+// The exact half of a triangle-BVH walk is the same in all three walks (4-wide, leaf queue, two leaves): the triangle test,
+// memb_candidate, tri_take.  Its `continue`s and the ANY return stay in the walks' loops: the same statements behind ONE helper
+// with early returns compiled into a slower loop, 3.10 against 3.33 Gsamples/s on the 967-triangle scene.
+
+// Triangle `id` (hit by the ray) is a candidate iff some octree leaf listing it is reached: every box from that leaf up to the
+// root hit.  sl / sh: the slots of the first and the last reached occurrence; ANY stops at the first.  C: the membership tables.
+template <bool ANY>
+MRT_HD bool memb_candidate(const Scn &S, const float *C, u32 tri0, u32 root, u32 id, V3 ro, V3 m, V3 pos, u32 &sl, u32 &sh)
 {
-    const float px = fma_fast(cx, R.inv.x, -R.oinv.x), py = fma_fast(cy, R.inv.y, -R.oinv.y), pz = fma_fast(cz, R.inv.z, -R.oinv.z);
-    const float qx = fma_fast(hx, R.ainv.x, R.qm.x), qy = fma_fast(hy, R.ainv.y, R.qm.y), qz = fma_fast(hz, R.ainv.z, R.qm.z);
-    const float tn = fmax_(fmax_(px - qx, py - qy), pz - qz);
-    const float tf = fmin_(fmin_(px + qx, py + qy), pz + qz);
-    return !(tn > tf || tf < 0.0f);
+    const Params &P = *S.P;
+    const float *F = S.F;
+    const float *N0 = F + P.off_node;
+    const u32 head = ldu(C, P.off_memb + tri0 + id);
+    const u32 e0 = head & 0xffffffu, ne = head >> 24;
+    float a0, a1;
+    bool cand = false;
+    sl = 0xffffffffu; sh = 0u;
+    for (u32 q = 0; q < ne; ++q) {
+        const u32 w = ldu(C, P.off_membe + e0 + q);
+        u32 n = root + (w >> MEMB_SLOT_BITS);
+        bool reached = true;
+        while (n != root) {
+            MRT_COUNT(CT_MEMB_BOX);
+            if (!box_isect(ld3(N0, n * NODE_WORDS + NODE_HALF), ro, m, add(pos, ld3(N0, n * NODE_WORDS + NODE_REL)), a0, a1)) { reached = false; break; }
+            n = ldu(F, P.off_parent + n);
+        }
+        if (!reached) continue;
+        if (ANY) return true;
+        const u32 slot = w & MEMB_SLOT_MASK;    // entries are in slot order
+        if (!cand) sl = slot;
+        sh = slot;
+        cand = true;
+    }
+    return cand;
+}
+
+// What a closest-hit walk has so far: keys and slots of its first minimum and last maximum (t0, i0, t1, i1 are the caller's)
+struct TriBest {
+    bool any = false;
+    i32 k0 = 0, k1 = 0;
+    u32 s0 = 0, s1 = 0;
+};
+MRT_HD void tri_take(TriBest &B, float t, u32 id, u32 sl, u32 sh, float &t0, i32 &i0, float &t1, i32 &i1)
+{
+    const i32 k = total_key(t);
+    if (!B.any) { B.any = true; t0 = t1 = t; i0 = i1 = (i32)id; B.k0 = B.k1 = k; B.s0 = sl; B.s1 = sh; return; }
+    if (k < B.k0 || (k == B.k0 && sl < B.s0)) { B.k0 = k; B.s0 = sl; t0 = t; i0 = (i32)id; }      // min_by: first minimum, src/rt.rs:764
+    if (k > B.k1 || (k == B.k1 && sh > B.s1)) { B.k1 = k; B.s1 = sh; t1 = t; i1 = (i32)id; }      // max_by: last maximum, src/rt.rs:765
 }
 
 // Diagnostics: mesh queries answered by the reference's own walk instead of a triangle BVH -- slot 6: the 4-wide walk's area
@@ -638,18 +697,13 @@ MRT_HD void count_fallback(const Params &P, u32 slot)
 // first leaf: its first candidate ends it.  An area that the stack alone fills (a degenerate tree) is answered by the caller
 // through the reference's own walk: exact, only slow.  Returns 0 none, 1 hit, 2 overflow.
 template <bool ANY, u32 FEAT>
-MRT_HD int mesh_walk4(const Scn &S, u32 tb, const TriCull &R, u32 tri0, u32 root, V3 ro, V3 rd, V3 m, V3 pos, float &t0, i32 &i0, float &t1, i32 &i1)
+MRT_HD int mesh_walk4(const Scn &S, u32 tb, const CullRay &R, u32 tri0, u32 root, V3 ro, V3 rd, V3 m, V3 pos, float &t0, i32 &i0, float &t1, i32 &i1)
 {
     const Params &P = *S.P;
     const float *F = S.F;
     const float *C = S.G;                                // membership tables and triangles: cold (F_DEEP implies F_COLD)
-    const float *CT = S.G;
-    const float *N0 = F + P.off_node;
-    const float *B0 = S.F + P.off_tbvh;
-    bool any = false;
-    i32 k0 = 0, k1 = 0;
-    u32 s0 = 0, s1 = 0;
-    float a0, a1;
+    const float *B0 = F + P.off_tbvh;
+    TriBest best;
     WalkMem W(S);
     const u32 cap = P.walk_cap;
     u32 cur = tb;              // index of the node to visit, NO_NODE: none
@@ -669,8 +723,8 @@ MRT_HD int mesh_walk4(const Scn &S, u32 tb, const TriCull &R, u32 tri0, u32 root
             const F4 cw = ld4(Nd, B4_CHILD);
             sched_fence();                                       // all eight reads are issued here, whatever is scheduled below
             const u32 w0 = f2u(cw.x), w1 = f2u(cw.y), w2 = f2u(cw.z), w3 = f2u(cw.w);
-            const bool h0 = tri_cull_hit(R, cx.x, cy.x, cz.x, hx.x, hy.x, hz.x) && w0 != 0u, h1 = tri_cull_hit(R, cx.y, cy.y, cz.y, hx.y, hy.y, hz.y) && w1 != 0u;
-            const bool h2 = tri_cull_hit(R, cx.z, cy.z, cz.z, hx.z, hy.z, hz.z) && w2 != 0u, h3 = tri_cull_hit(R, cx.w, cy.w, cz.w, hx.w, hy.w, hz.w) && w3 != 0u;
+            const bool h0 = cull_hit(R, cx.x, cy.x, cz.x, hx.x, hy.x, hz.x) && w0 != 0u, h1 = cull_hit(R, cx.y, cy.y, cz.y, hx.y, hy.y, hz.y) && w1 != 0u;
+            const bool h2 = cull_hit(R, cx.z, cy.z, cz.z, hx.z, hy.z, hz.z) && w2 != 0u, h3 = cull_hit(R, cx.w, cy.w, cz.w, hx.w, hy.w, hz.w) && w3 != 0u;
             // hit internal children as a mask (internal children occupy the first slots and are consecutive nodes)
             const u32 hm = ((h0 && (w0 >> 31)) ? 1u : 0u) | ((h1 && (w1 >> 31)) ? 2u : 0u) | ((h2 && (w2 >> 31)) ? 4u : 0u) | ((h3 && (w3 >> 31)) ? 8u : 0u);
             const u32 c0 = w0 & ~B4_INTERNAL;                    // index of child 0 (only used when some internal child was hit)
@@ -703,44 +757,20 @@ MRT_HD int mesh_walk4(const Scn &S, u32 tb, const TriCull &R, u32 tri0, u32 root
             const u32 id = (leaf & 0xffffffu) + j;
             ++j; ++probe_tris;
             if (j == (leaf >> 24)) { ++e; j = 0u; if (e < nq) leaf = W.get(cap - 1u - e); }
-            // (the exact half is written out here, `continue` by `continue`, as in the binary walks: the same statements behind
-            // a helper with early returns compiled into a slower loop, 3.10 against 3.33 Gsamples/s on the 967-triangle scene)
-            const float *T = CT + P.off_tri + (tri0 + id) * TRI_WORDS;
+            const float *T = C + P.off_tri + (tri0 + id) * TRI_WORDS;
             float t;
             MRT_COUNT(CT_TBVH_TRI);
             if (!tri_isect(add(ld3(T, 0), pos), ld3(T, 3), ld3(T, 6), ro, rd, t)) continue;
             MRT_COUNT(CT_TBVH_TRI_HIT);
-            // candidate iff some octree leaf listing the triangle is reached: every box from that leaf up to the root hit
-            const u32 head = ldu(C, P.off_memb + tri0 + id);
-            const u32 e0 = head & 0xffffffu, ne = head >> 24;
-            u32 sl = 0xffffffffu, sh = 0u;
-            bool cand = false;
-            for (u32 q = 0; q < ne; ++q) {
-                const u32 w = ldu(C, P.off_membe + e0 + q);
-                u32 n = root + (w >> MEMB_SLOT_BITS);
-                bool reached = true;
-                while (n != root) {
-                    MRT_COUNT(CT_MEMB_BOX);
-                    if (!box_isect(ld3(N0, n * NODE_WORDS + NODE_HALF), ro, m, add(pos, ld3(N0, n * NODE_WORDS + NODE_REL)), a0, a1)) { reached = false; break; }
-                    n = ldu(F, P.off_parent + n);
-                }
-                if (!reached) continue;
-                if (ANY) return 1;
-                const u32 slot = w & MEMB_SLOT_MASK;    // entries are in slot order
-                if (!cand) sl = slot;
-                sh = slot;
-                cand = true;
-            }
-            if (!cand) continue;
-            const i32 k = total_key(t);
-            if (!any) { any = true; t0 = t1 = t; i0 = i1 = (i32)id; k0 = k1 = k; s0 = sl; s1 = sh; continue; }
-            if (k < k0 || (k == k0 && sl < s0)) { k0 = k; s0 = sl; t0 = t; i0 = (i32)id; }      // min_by: first minimum, src/rt.rs:764
-            if (k > k1 || (k == k1 && sh > s1)) { k1 = k; s1 = sh; t1 = t; i1 = (i32)id; }      // max_by: last maximum, src/rt.rs:765
+            u32 sl, sh;
+            if (!memb_candidate<ANY>(S, C, tri0, root, id, ro, m, pos, sl, sh)) continue;
+            if (ANY) return 1;
+            tri_take(best, t, id, sl, sh, t0, i0, t1, i1);
         }
         MRT_PROBE_ROUND(probe_steps, probe_tris, 0u);
         if (cur == NO_NODE) break;
     }
-    return any ? 1 : 0;
+    return best.any ? 1 : 0;
 }
 
 // Meshes in LDS walk a BINARY triangle BVH, threaded (stackless, depth-first, skip links), one 32-byte node per step: 27 VALU
@@ -761,8 +791,6 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
     const float *M = F + P.off_mesh + mesh * MESH_WORDS;
     const u32 tri0 = ldu(M, MESH_TRI0), root = ldu(M, MESH_ROOT);
     const u32 tb = ldu(M, MESH_TBVH);
-    bool any = false;
-    i32 k0 = 0, k1 = 0;
     MRT_COUNT(CT_MESH_CALL);
 
     // Rays that are NaN in every component of their direction (Vec3f::norm of a zero or non-finite vector, src/lin.rs:64-66) or
@@ -796,35 +824,6 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
         }
     }
 
-    if constexpr (FEAT & F_DEEP) {
-        // ---- meshes beyond the LDS: the 4-wide table ----
-        const V3 ol = sub(ro, pos);
-        if (tb != NO_NODE && cull_ok(ol, dd) && fabs_(pos.x) < 1e6f && fabs_(pos.y) < 1e6f && fabs_(pos.z) < 1e6f) {
-            const float *N0 = F + P.off_node;
-            float a0, a1;
-            // a ray that misses the octree root has no candidates at all, src/rt.rs:745
-            if (!box_isect(ld3(N0, root * NODE_WORDS + NODE_HALF), ro, m, add(pos, ld3(N0, root * NODE_WORDS + NODE_REL)), a0, a1)) return false;
-            MRT_COUNT(CT_MESH_ROOT_HIT);
-            const CullRay CR = cull_ray(ol, rd);
-            TriCull R;
-            R.inv = CR.inv; R.ainv = CR.ainv;
-            {
-                const V3 c = ld3(M, MESH_BC), hh = ld3(M, MESH_BH);
-                const float big = fmax_(fmax_(fabs_(pos.x), fabs_(pos.y)), fabs_(pos.z)) + fmax_(fmax_(fabs_(c.x) + hh.x, fabs_(c.y) + hh.y), fabs_(c.z) + hh.z)
-                                  + fmax_(fmax_(fabs_(ol.x), fabs_(ol.y)), fabs_(ol.z));
-                const float mg = cull_margin(kMarginTri, kMarginPosTri, sub(c, ol), hh, big);
-                R.oinv = hadam(ol, R.inv);
-                R.qm = muls(R.ainv, mg);
-            }
-            const int r = mesh_walk4<ANY, FEAT>(S, tb, R, tri0, root, ro, rd, m, pos, t0, i0, t1, i1);
-            if (r == 2) { count_fallback(P, 6); return mesh_isect_ref<ANY, FEAT>(S, mesh, ro, rd, m, pos, t0, i0, t1, i1); }
-            return r != 0;
-        }
-        count_fallback(P, 7);
-        MRT_PROBE_FALLBACK(ro, rd, dd);
-        return mesh_isect_ref<ANY, FEAT>(S, mesh, ro, rd, m, pos, t0, i0, t1, i1);
-    }
-
     // ---- triangle BVH route (mrt_scene.h): the triangles the ray hits, then their candidacy in the reference's octree walk ----
     const V3 ol = sub(ro, pos);
     if (tb != NO_NODE && cull_ok(ol, dd) && fabs_(pos.x) < 1e6f && fabs_(pos.y) < 1e6f && fabs_(pos.z) < 1e6f) {
@@ -833,19 +832,15 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
         // a ray that misses the octree root has no candidates at all, src/rt.rs:745
         if (!box_isect(ld3(N0, root * NODE_WORDS + NODE_HALF), ro, m, add(pos, ld3(N0, root * NODE_WORDS + NODE_REL)), a0, a1)) return false;
         MRT_COUNT(CT_MESH_ROOT_HIT);
-        const float *B0 = F + P.off_tbvh;
-        // one culling margin per ray, from the mesh bounds
-        const CullRay R = cull_ray(ol, rd);
-        V3 oinv, qm;
-        {
-            const V3 c = ld3(M, MESH_BC), hh = ld3(M, MESH_BH);
-            const float big = fmax_(fmax_(fabs_(pos.x), fabs_(pos.y)), fabs_(pos.z)) + fmax_(fmax_(fabs_(c.x) + hh.x, fabs_(c.y) + hh.y), fabs_(c.z) + hh.z)
-                              + fmax_(fmax_(fabs_(ol.x), fabs_(ol.y)), fabs_(ol.z));
-            const float mg = cull_margin(kMarginTri, kMarginPosTri, sub(c, ol), hh, big);
-            oinv = hadam(ol, R.inv);
-            qm = muls(R.ainv, mg);
+        const CullRay R = tri_cull_ray(M, pos, ol, rd);
+        if constexpr (FEAT & F_DEEP) {
+            // meshes beyond the LDS: the 4-wide table
+            const int r = mesh_walk4<ANY, FEAT>(S, tb, R, tri0, root, ro, rd, m, pos, t0, i0, t1, i1);
+            if (r == 2) { count_fallback(P, 6); return mesh_isect_ref<ANY, FEAT>(S, mesh, ro, rd, m, pos, t0, i0, t1, i1); }
+            return r != 0;
         }
-        u32 s0 = 0, s1 = 0;
+        const float *B0 = F + P.off_tbvh;
+        TriBest best;
         u32 node = tb;
         if constexpr ((!ANY || MRT_SHADOW_QUEUE) && has_walk_area(FEAT)) {
             // Closest-hit walk with EVERY leaf postponed: the box walk runs on until the tree is exhausted (or the lane's queue
@@ -867,11 +862,7 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
                     MRT_COUNT(CT_TBVH_NODE);
                     const u32 skip = f2u(nb.z);
                     const u32 leaf = opaque_v(f2u(nb.w)), child = node + 1u;        // (an integer to the compiler: `!= 0` stays v_cmp_ne_u32)
-                    const float px = fma_fast(na.x, R.inv.x, -oinv.x), py = fma_fast(na.y, R.inv.y, -oinv.y), pz = fma_fast(na.z, R.inv.z, -oinv.z);
-                    const float qx = fma_fast(na.w, R.ainv.x, qm.x), qy = fma_fast(nb.x, R.ainv.y, qm.y), qz = fma_fast(nb.y, R.ainv.z, qm.z);
-                    const float tn = fmax_(fmax_(px - qx, py - qy), pz - qz);
-                    const float tf = fmin_(fmin_(px + qx, py + qy), pz + qz);
-                    const bool hit = !(tn > tf || tf < 0.0f);
+                    const bool hit = cull_hit(R, na.x, na.y, na.z, na.w, nb.x, nb.y);
                     q.put_at(qo, leaf);                                // branch-free: the slot only counts when the leaf was hit
                     qo += (hit && leaf != 0u) ? q_pitch : 0u;
                     // the table is in depth-first order: a leaf's skip link IS the next node (pack_scene puts a never-hit
@@ -891,36 +882,15 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
                     MRT_COUNT(CT_TBVH_TRI);
                     if (!tri_isect(add(ld3(T, 0), pos), ld3(T, 3), ld3(T, 6), ro, rd, t)) continue;
                     MRT_COUNT(CT_TBVH_TRI_HIT);
-                    const u32 head = ldu(C, P.off_memb + tri0 + id);
-                    const u32 e0 = head & 0xffffffu, ne = head >> 24;
-                    u32 sl = 0xffffffffu, sh = 0u;
-                    bool cand = false;
-                    for (u32 k = 0; k < ne; ++k) {
-                        const u32 w = ldu(C, P.off_membe + e0 + k);
-                        u32 n = root + (w >> MEMB_SLOT_BITS);
-                        bool reached = true;
-                        while (n != root) {
-                            MRT_COUNT(CT_MEMB_BOX);
-                            if (!box_isect(ld3(N0, n * NODE_WORDS + NODE_HALF), ro, m, add(pos, ld3(N0, n * NODE_WORDS + NODE_REL)), a0, a1)) { reached = false; break; }
-                            n = ldu(F, P.off_parent + n);
-                        }
-                        if (!reached) continue;
-                        if (ANY) return true;
-                        const u32 slot = w & MEMB_SLOT_MASK;    // entries are in slot order
-                        if (!cand) sl = slot;
-                        sh = slot;
-                        cand = true;
-                    }
-                    if (!cand) continue;
-                    const i32 k = total_key(t);
-                    if (!any) { any = true; t0 = t1 = t; i0 = i1 = (i32)id; k0 = k1 = k; s0 = sl; s1 = sh; continue; }
-                    if (k < k0 || (k == k0 && sl < s0)) { k0 = k; s0 = sl; t0 = t; i0 = (i32)id; }      // min_by: first minimum, src/rt.rs:764
-                    if (k > k1 || (k == k1 && sh > s1)) { k1 = k; s1 = sh; t1 = t; i1 = (i32)id; }      // max_by: last maximum, src/rt.rs:765
+                    u32 sl, sh;
+                    if (!memb_candidate<ANY>(S, C, tri0, root, id, ro, m, pos, sl, sh)) continue;
+                    if (ANY) return true;
+                    tri_take(best, t, id, sl, sh, t0, i0, t1, i1);
                 }
                 MRT_PROBE_ROUND(probe_steps, probe_tris, 0u);
                 if (node == BVH_END) break;
             }
-            return any;
+            return best.any;
         }
         // "while-while" with one postponed leaf: a lane walks boxes until it has found two leaves (or the end), then the
         // wavefront runs the exact triangle tests of both together -- fewer, fuller rounds than one leaf at a time.
@@ -936,12 +906,7 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
                 MRT_COUNT(CT_TBVH_NODE);
                 const u32 skip = f2u(nb.z);
                 const u32 leaf = f2u(nb.w), child = node + 1u;
-                // t = c * inv - o * inv -+ (h * |inv| + mg * |inv|)
-                const float px = fma_fast(na.x, R.inv.x, -oinv.x), py = fma_fast(na.y, R.inv.y, -oinv.y), pz = fma_fast(na.z, R.inv.z, -oinv.z);
-                const float qx = fma_fast(na.w, R.ainv.x, qm.x), qy = fma_fast(nb.x, R.ainv.y, qm.y), qz = fma_fast(nb.y, R.ainv.z, qm.z);
-                const float tn = fmax_(fmax_(px - qx, py - qy), pz - qz);
-                const float tf = fmin_(fmin_(px + qx, py + qy), pz + qz);
-                const bool hit = !(tn > tf || tf < 0.0f);
+                const bool hit = cull_hit(R, na.x, na.y, na.z, na.w, nb.x, nb.y);
                 const u32 cand = hit ? leaf : 0u;                  // a leaf to test, or 0
                 const bool have_a = leaf_a != 0u;
                 leaf_b |= have_a ? cand : 0u;
@@ -959,35 +924,13 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
                 MRT_COUNT(CT_TBVH_TRI);
                 if (!tri_isect(add(ld3(T, 0), pos), ld3(T, 3), ld3(T, 6), ro, rd, t)) continue;
                 MRT_COUNT(CT_TBVH_TRI_HIT);
-                // candidate iff some octree leaf listing the triangle is reached: every box from that leaf up to the root hit
-                const u32 head = ldu(C, P.off_memb + tri0 + id);
-                const u32 e0 = head & 0xffffffu, ne = head >> 24;
-                u32 sl = 0xffffffffu, sh = 0u;
-                bool cand = false;
-                for (u32 e = 0; e < ne; ++e) {
-                    const u32 w = ldu(C, P.off_membe + e0 + e);
-                    u32 n = root + (w >> MEMB_SLOT_BITS);
-                    bool reached = true;
-                    while (n != root) {
-                        MRT_COUNT(CT_MEMB_BOX);
-                        if (!box_isect(ld3(N0, n * NODE_WORDS + NODE_HALF), ro, m, add(pos, ld3(N0, n * NODE_WORDS + NODE_REL)), a0, a1)) { reached = false; break; }
-                        n = ldu(F, P.off_parent + n);
-                    }
-                    if (!reached) continue;
-                    if (ANY) return true;
-                    const u32 slot = w & MEMB_SLOT_MASK;    // entries are in slot order
-                    if (!cand) sl = slot;
-                    sh = slot;
-                    cand = true;
-                }
-                if (!cand) continue;
-                const i32 k = total_key(t);
-                if (!any) { any = true; t0 = t1 = t; i0 = i1 = (i32)id; k0 = k1 = k; s0 = sl; s1 = sh; continue; }
-                if (k < k0 || (k == k0 && sl < s0)) { k0 = k; s0 = sl; t0 = t; i0 = (i32)id; }      // min_by: first minimum, src/rt.rs:764
-                if (k > k1 || (k == k1 && sh > s1)) { k1 = k; s1 = sh; t1 = t; i1 = (i32)id; }      // max_by: last maximum, src/rt.rs:765
+                u32 sl, sh;
+                if (!memb_candidate<ANY>(S, C, tri0, root, id, ro, m, pos, sl, sh)) continue;
+                if (ANY) return true;
+                tri_take(best, t, id, sl, sh, t0, i0, t1, i1);
             }
         }
-        return any;
+        return best.any;
     }
 
     count_fallback(P, 7);
@@ -1220,24 +1163,22 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
         // the exact tests at the ray's distance from the farthest instance.  Rays that are not finite or not unit length
         // are not culled at all.
         const bool cull = cull_ok(ray_.o, ray_.dd);         // (the ray as given: F_IDENT's ray_i only serves the exact tests)
-        const CullRay R = cull_ray(ray_.o, ray_.d);
+        CullRay R = cull_ray(ray_.d);
         const float *N0 = F + P.off_bvh;
         u32 node = P.n_bvh_nodes ? 0u : BVH_END;
         // ONE margin per ray, from the root box (node 0): k x its extent seen from the origin + ksq x that extent squared (spheres)
-        // + kpos x the coordinate magnitudes, so that a step is the triangle BVH's: t = c * inv - o * inv -+ (h * |inv| + mg * |inv|)
-        V3 oinv, qm;
+        // + kpos x the coordinate magnitudes, so that a step is the triangle BVH's (cull_hit)
         float mg;
         {
             const F4 ra = ld4(N0, 0), rb = ld4(N0, 4);
-            const V3 r = sub(v3(ra.x, ra.y, ra.z), R.o);
+            const V3 r = sub(v3(ra.x, ra.y, ra.z), ray_.o);
             const float ext = fmax_(fmax_(fabs_(r.x) + ra.w, fabs_(r.y) + rb.x), fabs_(r.z) + rb.y);
             const float obig = fmax_(fmax_(fabs_(ray_.o.x), fabs_(ray_.o.y)), fabs_(ray_.o.z));
             // (spheres: sqrt(r^2 + 2 eps' D^2) - r <= min(eps' D^2 / r, sqrt(2 eps') D) -- the square law up to D / r = 1000, 4e-3 D beyond)
             const float ksq = fmin_(P.inst_ksq * ext, 4e-3f) * MRT_MARGIN_SCALE;
             mg = fma_fast(P.inst_k * MRT_MARGIN_SCALE + ksq, ext, fma_fast(P.inst_kpos * MRT_MARGIN_SCALE, obig + obig + ext, 1e-6f * MRT_MARGIN_SCALE));
-            oinv = hadam(R.o, R.inv);
-            qm = muls(R.ainv, mg);
         }
+        cull_from(R, ray_.o, mg);
         // "while-while": every lane first walks boxes until it stands on a leaf (cheap iterations, all lanes busy), then
         // the wavefront runs the expensive exact tests of the leaves together.
         for (;;) {
@@ -1250,11 +1191,8 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
                 const F4 na = ld4(N0, node * BVH_WORDS), nb = ld4(N0, node * BVH_WORDS + 4);
                 MRT_COUNT(CT_BVH_NODE);
                 const u32 skip = f2u(nb.z), leaf = f2u(nb.w);
-                const float px = fma_fast(na.x, R.inv.x, -oinv.x), py = fma_fast(na.y, R.inv.y, -oinv.y), pz = fma_fast(na.z, R.inv.z, -oinv.z);
-                const float qx = fma_fast(na.w, R.ainv.x, qm.x), qy = fma_fast(nb.x, R.ainv.y, qm.y), qz = fma_fast(nb.y, R.ainv.z, qm.z);
-                const float tn = fmax_(fmax_(px - qx, py - qy), pz - qz);
-                const float tf = fmin_(fmin_(px + qx, py + qy), pz + qz);
-                bool hit_node = !(tn > tf || tf < 0.0f);
+                float tn;
+                bool hit_node = cull_hit(R, na.x, na.y, na.z, na.w, nb.x, nb.y, tn);
                 if (!ANY) hit_node = hit_node && !(tn > far);
                 hit_node = hit_node || !cull;      // rays that must not be culled visit everything
                 const u32 cand = hit_node ? leaf : 0u;             // a leaf to test, or 0

@@ -191,11 +191,12 @@ void emu_math(int op, const float *a, const float *b, float *out, size_t n)
 
 // Mesh arm of Renderer::intersect for n rays against renderer 0 (a mesh), through the TBVH route and through the reference's
 // octree walk (forced by dd = NaN, which only steers the route).  out[i*10..]: hit, t0 bits, i0, t1 bits, i1 for each route.
-// A third route walks the 4-wide table of the same mesh (F_DEEP lane code).
+// A third route walks the 4-wide table of the same mesh (F_DEEP lane code), a fourth the binary table with the warm lane code
+// (F_COLD: closest hits through the leaf queue, of MRT_EMU_LEAF_QUEUE entries where the environment has it).
 // Returns the number of rays on which the routes differ (ANY queries included), or < 0.
 int emu_mesh_probe(const mrt_render_desc *d, uint32_t n, const float *orig, const float *dir, uint32_t *out, uint32_t *stats /*[2]*/)
 {
-    lane::Packing k, kw;
+    lane::Packing k, kw, kq;
     const int rc = lane::pack(d, nullptr, PackOpts(), lane::Level(), k, g_err);
     if (rc) return rc;
     const Params &P = k.P;
@@ -208,13 +209,17 @@ int emu_mesh_probe(const mrt_render_desc *d, uint32_t n, const float *orig, cons
     // the same mesh with the 4-wide table (what the F_DEEP kernels walk): a third route through the same exact tests
     if (lane::pack(d, nullptr, PackOpts(), lane::level_of(1, walk_cap()), kw, g_err)) return -101;
     const Scn &Sw = kw.S;
+    // ... and with the binary table under the warm lane code, whose walk area is the leaf queue
+    if (lane::pack(d, nullptr, PackOpts(), lane::level_of(0xffffffffu), kq, g_err)) return -102;
+    if (const char *v = getenv("MRT_EMU_LEAF_QUEUE")) { const int c = atoi(v); if (c >= 1 && c <= (int)kWalkCapMax) kq.P.walk_cap = (uint32_t)c; }
+    const Scn &Sq = kq.S;
     for (uint32_t i = 0; i < n; ++i) {
         const V3 o = v3(orig[i * 3], orig[i * 3 + 1], orig[i * 3 + 2]), dr = v3(dir[i * 3], dir[i * 3 + 1], dir[i * 3 + 2]);
         const RayPre ray = ray_pre<F_ALL>(o, dr);
-        uint32_t r[3][5];
-        bool anyq[3];
-        for (int route = 0; route < 3; ++route) {
-            const Scn &SS = route == 2 ? Sw : S;
+        uint32_t r[4][5];
+        bool anyq[4];
+        for (int route = 0; route < 4; ++route) {
+            const Scn &SS = route == 2 ? Sw : route == 3 ? Sq : S;
             const float *I = SS.F + SS.P->off_inst;
             const F4 ia = ld4(I, 0);
             const V3 pos = v3(ia.x, ia.y, ia.z);
@@ -226,6 +231,9 @@ int emu_mesh_probe(const mrt_render_desc *d, uint32_t n, const float *orig, cons
             if (route == 2) {
                 h = mesh_isect<false, F_ALL | F_COLD | F_DEEP>(SS, 0, ro, ray.d, dd, ray.m, pos, t0, i0, t1, i1);
                 anyq[route] = mesh_isect<true, F_ALL | F_COLD | F_DEEP>(SS, 0, ro, ray.d, dd, ray.m, pos, u0, j0, u1, j1);
+            } else if (route == 3) {
+                h = mesh_isect<false, F_ALL | F_COLD>(SS, 0, ro, ray.d, dd, ray.m, pos, t0, i0, t1, i1);
+                anyq[route] = mesh_isect<true, F_ALL | F_COLD>(SS, 0, ro, ray.d, dd, ray.m, pos, u0, j0, u1, j1);
             } else {
                 h = mesh_isect<false, F_ALL>(SS, 0, ro, ray.d, dd, ray.m, pos, t0, i0, t1, i1);
                 anyq[route] = mesh_isect<true, F_ALL>(SS, 0, ro, ray.d, dd, ray.m, pos, u0, j0, u1, j1);
@@ -247,7 +255,9 @@ int emu_mesh_probe(const mrt_render_desc *d, uint32_t n, const float *orig, cons
         }
         if (r[0][0]) ++hits;
         // (triangle ids are positions in the table's leaf order, which both tables share: they come from one binary tree)
-        if (memcmp(r[0], r[1], sizeof r[0]) != 0 || memcmp(r[0], r[2], sizeof r[0]) != 0 || anyq[0] != anyq[1] || anyq[0] != anyq[2] || anyq[0] != (bool)r[0][0]) ++bad;
+        bool same = anyq[0] == (bool)r[0][0];
+        for (int route = 1; route < 4; ++route) same = same && memcmp(r[0], r[route], sizeof r[0]) == 0 && anyq[0] == anyq[route];
+        if (!same) ++bad;
         if (out) { memcpy(out + (size_t)i * 10, r[0], sizeof r[0]); memcpy(out + (size_t)i * 10 + 5, r[1], sizeof r[1]); }
     }
     if (stats) { stats[0] = hits; stats[1] = with_tbvh; }

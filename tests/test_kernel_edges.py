@@ -177,7 +177,8 @@ def test_deep_walk_and_walk_area_overflow_on_x86(seed, oracle_mod, emu_mod, monk
 
 
 def test_mesh_route_at_large_scales_and_far_positions(emu_mod, monkeypatch):
-    """The triangle-BVH routes (binary, and 4-wide at walk areas of 4 and 16 entries) against the reference's octree walk on
+    """The triangle-BVH routes (binary in two-leaf rounds, binary through leaf queues of 1 and 8 entries, and 4-wide at walk
+    areas of 4 and 16 entries) against the reference's octree walk on
     meshes scaled by 1e-3 .. 1e3 and placed up to 1e5 from the origin (the route is taken below 1e6; a mesh stays at most
     ~1e4 of its sizes away, where f32 positions still resolve it): the culling margins of
     mrt_trace.h must hold where the rounding of the exact tests is largest."""
@@ -199,8 +200,10 @@ def test_mesh_route_at_large_scales_and_far_positions(emu_mod, monkeypatch):
         h = build_desc(load_render(desc))
         o, d = mesh_probe.rays_for(rng, tris, 4000)
         o = np.ascontiguousarray(o + np.asarray(pos, np.float32))
-        for cap in (4, 16):
+        # (the leaf queue of the warm binary walk at one entry -- a round per leaf -- and at kLeafQueue of mrt_trace.h)
+        for cap, queue in ((4, 1), (16, 8)):
             monkeypatch.setenv("MRT_EMU_WALK_CAP", str(cap))
+            monkeypatch.setenv("MRT_EMU_LEAF_QUEUE", str(queue))
             out = np.zeros((len(o), 10), np.uint32)
             stats = (C.c_uint32 * 2)()
             bad = L.emu_mesh_probe(C.cast(h.ptr(), C.c_void_p), len(o), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
