@@ -841,7 +841,8 @@ bool all_ident(const Tables &T)
 // The AXIS table (mrt_scene.h): for scenes of untransformed planes and spheres whose planes all lie along an axis, the
 // closest-hit scan of the plain F_IDENT kernel tests a plane with the one component of ray and position that its normal
 // selects (mrt_trace.h trace; DESIGN.md section 7 has the argument that no bit changes).  The bound on the magnitudes keeps
-// every shifted origin finite and every numerator inside the window of the division core.
+// every shifted origin finite and every numerator inside the upper end of the division core's window; a plane position along
+// its axis of +-0 or at least kAxisPlaneMin keeps a non-zero numerator inside the lower end (the scan tests neither).
 // plain_ident: all_ident and no scene feature.  True when the scene has the table.
 bool axis_table(Tables &T, bool plain_ident)
 {
@@ -856,7 +857,11 @@ bool axis_table(Tables &T, bool plain_ident)
             u32 ones = 0u, zeros = 0u;
             for (u32 k = 0; k < 3u; ++k) {
                 const u32 w = ir[INST_P5 + k], mag = w & 0x7fffffffu;
-                if (mag == 0x3f800000u) { ++ones; code = k + 1u; sd = ir[INST_P3] ^ (w & 0x80000000u); }      // s * d: d, or d with its sign flipped
+                if (mag == 0x3f800000u) {
+                    ++ones; code = k + 1u; sd = ir[INST_P3] ^ (w & 0x80000000u);      // s * d: d, or d with its sign flipped
+                    const float pk = fabsf(fbits(ir[INST_POS + k]));                   // on the coordinate plane, or well off it
+                    ok = ok && (pk == 0.0f || pk >= kAxisPlaneMin);
+                }
                 else if (mag == 0u) ++zeros;
             }
             ok = ok && ones == 1u && zeros == 2u;
@@ -864,6 +869,8 @@ bool axis_table(Tables &T, bool plain_ident)
         T.axis_tab.push_back(code); T.axis_tab.push_back(sd);
         scan = ok;
     }
+    // one record of padding: the scan fetches one record ahead without asking whether there is one (mrt_scene.h)
+    for (u32 k = 0; k < AXIS_WORDS; ++k) T.axis_tab.push_back(0u);
     return scan;
 }
 

@@ -56,13 +56,18 @@ enum : u32 { INSTX_REND = 0, INSTX_PLANE_NW = 1 };
 constexpr u32 INSTX_WORDS = 4;
 // AXIS (only for scenes the axis scan serves, Params.axis_scan: every instance untransformed, planes and spheres only, every
 // plane's unit normal n^ along an axis -- one component exactly +-1, the others +-0 --, every position, plane offset and r*r
-// finite and at most kAxisMax in magnitude; behind INSTX, one record per instance, in the order of INST):
+// finite and at most kAxisMax in magnitude, every plane's position along its axis +-0 or at least kAxisPlaneMin in magnitude; behind INSTX, one record per instance, in the order of INST):
 //   [0] code: 0 sphere | 1, 2, 3 plane along x, y, z   [1] plane: s * d, with s = the normal's +-1 and d = INST word 3 (exact)
 // The INST records are what they are without it; the closest-hit scan of the plain F_IDENT kernel reads this table instead of
 // tag and normal (mrt_trace.h trace).
+// ONE RECORD PAST THE END: that scan fetches record j + 1 of INST and of AXIS while it tests record j, the last one included, and
+// never looks at what it fetched there.  Both reads stay inside the staged blob: INSTX lies behind INST (an INSTX record per
+// instance: at least INST_WORDS / 2 words, the half of a record the scan reads), and the AXIS table carries AXIS_WORDS words of
+// zero padding behind its last record (axis_table of mrt_pack.cpp; part of the table, so every size and staging mark counts them).
 enum : u32 { AXIS_CODE = 0, AXIS_SD = 1 };
 constexpr u32 AXIS_WORDS = 2;
 constexpr float kAxisMax = 0x1p38f;
+constexpr float kAxisPlaneMin = 0x1p-15f;      // a served plane's position along its axis: +-0, or at least this (mrt_trace.h: why)
 constexpr u32 TAG_KIND_MASK = 7u, TAG_IDENT = 8u, TAG_XF_SHIFT = 4u;
 
 // XF: [0..8] L (lookat)  [9..17] R (rotate_y)  [18] 1 if both equal the identity as values
@@ -231,8 +236,8 @@ enum : u32 {
                       // zero, infinite or NaN component still take the reference's two mat-vecs (xf_vec)
                       // AXIS SCAN (F_IDENT alone: planes and spheres, no lights, closest hit): a scene whose planes all lie along an
                       // axis carries the AXIS table of mrt_scene.h (Params.axis_scan), and a query whose whole wavefront has every
-                      // direction component inside the division window and every origin component within kAxisMax scans it with
-                      // a second body (trace, "axis scan"): the three refined reciprocals of the direction once per ray, a plane
+                      // direction component inside the division window and every origin component within kAxisMax -- and none
+                      // within 2^-40 of zero without being zero -- scans it with a second body (trace, "axis scan"): the three refined reciprocals of the direction once per ray, a plane
                       // from the ONE component its normal selects.  Same bits; any other query, the shadow
                       // query and every other kernel take the generic body
     F_ENV = 1024u,    // the sky has an environment texture (mrt.h mrt_env): env_uv / env_color at the two miss sites of

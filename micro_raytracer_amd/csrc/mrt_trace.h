@@ -62,7 +62,7 @@ constexpr u32 kLeafQueue = MRT_LEAF_QUEUE;
 #ifndef MRT_PROBE_ROUND                // one round of a lane's triangle-BVH walk: box steps taken, triangles tested, membership boxes
 #define MRT_PROBE_ROUND(steps, tris, membs)
 #endif
-enum : u32 { CT_TRACE = 0, CT_LIN_TEST, CT_BVH_NODE, CT_BVH_TEST, CT_MESH_CALL, CT_MESH_ROOT_HIT, CT_TBVH_NODE, CT_TBVH_TRI, CT_TBVH_TRI_HIT, CT_MEMB_BOX, CT_TRACE_ANY, CT_WALK_OVERFLOW, CT_WALK_ROUND, CT_REF_TRI, CT_REF_BOX, CT_AXIS_SCAN, CT_COUNT };
+enum : u32 { CT_TRACE = 0, CT_LIN_TEST, CT_BVH_NODE, CT_BVH_TEST, CT_MESH_CALL, CT_MESH_ROOT_HIT, CT_TBVH_NODE, CT_TBVH_TRI, CT_TBVH_TRI_HIT, CT_MEMB_BOX, CT_TRACE_ANY, CT_WALK_OVERFLOW, CT_WALK_ROUND, CT_REF_TRI, CT_REF_BOX, CT_AXIS_SCAN, CT_AXIS_REDO, CT_COUNT };
 enum : u32 { PH_ITER = 0, PH_REGEN, PH_SPHERE_MATH, PH_PLANE_HIT, PH_SHADE, PH_NORMAL_NONPLANE, PH_SCATTER1, PH_SCATTER2, PH_REFRACT, PH_EMIT_END, PH_LIGHTS, PH_COUNT };
 
 constexpr float kE = 0.0001f;                 // src/rt.rs:7
@@ -988,6 +988,19 @@ MRT_HD bool isect_instance(const Scn &S, const RayPre &ray, u32 i, const F4 &ia,
     return false;
 }
 
+// End of one arm of the axis scan's dispatch: an empty statement the compiler can neither drop nor find equal to another arm's, so
+// that every arm keeps its own update of the closest hit and falls through to the loop's exit test (merged, the arms meet in
+// one update block behind scalar flags: about ten scalar instructions per instance).  Nothing on x86.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MRT_ARM_END(name) asm volatile("; axis scan: end of arm " name)
+// The compiler forgets what it knows about a wave-uniform value (which stays where it is: no instruction).  Between the tests of
+// the dispatch: tests of ONE known value become a switch, and a switch a tree of compares with flags between its leaves.
+#define MRT_FORGET_SCALAR(v) asm volatile("" : "+s"(v))
+#else
+#define MRT_ARM_END(name)
+#define MRT_FORGET_SCALAR(v)
+#endif
+
 template <bool V> struct BoolTag { static constexpr bool value = V; };
 
 // RayTracer::closest_hit, src/rt.rs:867-898: every renderer x instance in order, first minimum of the entry distance
@@ -1068,9 +1081,26 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
         // (one predicate, no short-circuit branches: the test runs once per query with all lanes on)
         const bool tame = (int)in_window(d.x) & (int)in_window(d.y) & (int)in_window(d.z) & (int)(fabs_(o.x) <= kAxisMax) & (int)(fabs_(o.y) <= kAxisMax) &
                           (int)(fabs_(o.z) <= kAxisMax);
+        // A plane numerator -(ro_k + s d) is fl(ro_k - pos_k) (s d == -pos_k as a number), and no window test stands in front of
+        // its division core:
+        //   pos_k != 0: pack_scene serves only planes with |pos_k| >= kAxisPlaneMin = 2^-15.  A non-zero difference of two floats is
+        //     at least the smaller of their ulps: ulp(pos_k) >= 2^-38, ulp(ro_k) >= 2^-40 for |ro_k| >= 2^-17, and a smaller
+        //     (or zero) ro_k leaves |ro_k - pos_k| > 2^-16.  So |num| is 0 or at least 2^-40, and at most 2^40 by the bounds.
+        //   pos_k == +-0: ro_k is o_k and |num| = |o_k|: `near0` below sends a query with 0 < |o_k| < 2^-40 in some lane to the
+        //     generic body before the loop (CT_AXIS_REDO; rays that start within 2^-40 of a coordinate plane without being on it).
+        //   num == +-0: +-0 times the reciprocal is +-0, both residuals are zeros and the core returns a zero, as the division
+        //     does: bits 0 or 0x80000000, a miss by `0 < bits` on either route, and a miss records nothing.  (Not a corner: a ray
+        //     that leaves a wall at a grazing angle starts exactly on it -- 3 in 10^4 closest-hit queries of the Cornell box.)
+        auto off0 = [](float x) { return (int)(x == 0.0f) | (int)(fabs_(x) >= kWinLo); };
+        const bool near0 = !(off0(o.x) & off0(o.y) & off0(o.z));
+        bool axis = false;
         if (P.axis_scan && n && wave_all(tame)) {
-            scanned = true;
             MRT_COUNT(CT_AXIS_SCAN);
+            axis = wave_all(!near0);
+            if (!axis) { MRT_COUNT(CT_AXIS_REDO); }
+        }
+        if (axis) {
+            scanned = true;
             const float *A = F + P.off_axis;
 #if defined(MRT_FAST_IEEE)
             const V3 r = v3(rcp_refined_(d.x), rcp_refined_(d.y), rcp_refined_(d.z));
@@ -1083,41 +1113,80 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
             auto plane = [&](u32 i, float ok, float dk, float rk, float pk, float sd) {
                 const float ro = pk + (ok - pk);
                 const float num = -(ro + sd);
-                float tt;
 #if defined(MRT_FAST_IEEE)
-                if (wave_all(fabs_(num) >= kWinLo)) tt = div_core_(num, dk, rk);      // (|num| <= 2^40 by the bounds)
-                else
+                const float tt = div_core_(num, dk, rk);
+#else
+                const float tt = num / dk;
 #endif
-                    tt = num / dk;
                 (void)rk;
                 const i32 kb = (i32)f2u(tt);
                 if (kb > 0 && kb < best_key) { best_key = kb; best.inst = i; best.t1 = tt; }
             };
+            // one sphere: Sphere::intersect as sphere_isect has it, on the shifted origin, with ONE window test for the root and
+            // the two quotients: the root's core first, then disc, -b - sq, -b + sq and 2a against the window together (their
+            // smallest and largest magnitude; a NaN disc makes all three NaN, an infinite one fails the upper end, and nothing
+            // else gives a NaN here).  Inside it the quotient of the entry distance is a non-zero number: `0 < bits < best_key`
+            // is the `t0 < 0` miss and the key comparison at once, as for a plane.  A wavefront with a lane outside takes the full
+            // expansions: the same bits (mrt_math.h), just not as fast.
+            const float a = ray_.dd, den = 2.0f * a;
+            const bool a_mid = (int)(a > 0.0f) & (int)(a < 1e18f);
+#if defined(MRT_FAST_IEEE)
+            const bool den_ok = in_window(den);
+            const float rden = rcp_refined_(den);
+#endif
+            auto sphere = [&](u32 i, const F4 &ia) {
+                const V3 pos = v3(ia.x, ia.y, ia.z);
+                const V3 ro = add(pos, sub(o, pos));          // (no identity test: see above)
+                const V3 oo = sub(ro, pos);
+                const float b = 2.0f * dot(oo, d);
+                const float c = dot(oo, oo) - ia.w;
+                const float disc = b * b - 4.0f * a * c;
+                if (disc < 0.0f) return;
+                if (b > 1e-20f && a_mid && disc >= 0.0f) return;      // (moving away: see sphere_isect)
+                MRT_PROBE(PH_SPHERE_MATH);
+#if defined(MRT_FAST_IEEE)
+                const float sqc = sqrt_core_(disc);
+                const float m0 = -b - sqc, m1 = -b + sqc;
+                const float least = __builtin_fminf(__builtin_fminf(disc, fabs_(m0)), fabs_(m1));
+                const float most = __builtin_fmaxf(__builtin_fmaxf(disc, fabs_(m0)), fabs_(m1));
+                if (wave_all((int)(least >= kWinLo) & (int)(most <= kWinHi) & (int)den_ok)) {
+                    const float q0 = div_core_(m0, den, rden), q1 = div_core_(m1, den, rden);
+                    const i32 kb = (i32)f2u(q0);
+                    if (kb > 0 && kb < best_key) { best_key = kb; best.inst = i; best.t1 = q1; }
+                    return;
+                }
+#endif
+                const float sq = __builtin_sqrtf(disc);
+                const float q0 = (-b - sq) / den, q1 = (-b + sq) / den;
+                if (q0 < 0.0f) return;
+                const i32 key = total_key(q0);
+                if (key < best_key) { best_key = key; best.inst = i; best.t1 = q1; }
+            };
             auto test = [&](u32 i, const F4 &ia, const F2 &ax) {
                 MRT_COUNT(CT_LIN_TEST);
                 MRT_PROBE_INST(i);
-                const u32 code = wave_uniform(f2u(ax.x));
-                if (code == 1u) plane(i, o.x, d.x, r.x, ia.x, ax.y);
-                else if (code == 2u) plane(i, o.y, d.y, r.y, ia.y, ax.y);
-                else if (code == 3u) plane(i, o.z, d.z, r.z, ia.z, ax.y);
-                else {
-                    const V3 pos = v3(ia.x, ia.y, ia.z);
-                    const V3 ro = add(pos, sub(o, pos));          // (no identity test: see above)
-                    float t0 = 0.0f, t1 = 0.0f;
-                    if (sphere_isect(ia.w, sub(ro, pos), d, ray_.dd, t0, t1)) {
-                        const i32 key = total_key(t0);
-                        if (key < best_key) { best_key = key; best.inst = i; best.t1 = t1; }
-                    }
-                }
+                u32 code = wave_uniform(f2u(ax.x));
+                // four tests in a row, no `else`, and nothing known about `code` from one to the next: the arms stay apart, each
+                // with its own update of the closest hit (see MRT_ARM_END)
+                if (code == 1u) { plane(i, o.x, d.x, r.x, ia.x, ax.y); MRT_ARM_END("x"); }
+                MRT_FORGET_SCALAR(code);
+                if (code == 2u) { plane(i, o.y, d.y, r.y, ia.y, ax.y); MRT_ARM_END("y"); }
+                MRT_FORGET_SCALAR(code);
+                if (code == 3u) { plane(i, o.z, d.z, r.z, ia.z, ax.y); MRT_ARM_END("z"); }
+                MRT_FORGET_SCALAR(code);
+                if (code == 0u) { sphere(i, ia); MRT_ARM_END("sphere"); }
             };
+            // two record buffers used in turn; the next record is fetched whether or not there is one: pack_scene keeps one
+            // record's room behind the INST and the AXIS table inside the staged blob (mrt_scene.h), and what is read there
+            // is never tested -- one exit test per instance
             u32 j = 0;
-            F4 a0 = ld4(I, 0), b0 = a0;
-            F2 c0 = ld2(A, 0), e0 = c0;
+            F4 a0 = ld4(I, 0), b0;
+            F2 c0 = ld2(A, 0), e0;
             for (;;) {
-                if (j + 1u < n) { b0 = ld4(I, (j + 1u) * INST_WORDS); e0 = ld2(A, (j + 1u) * AXIS_WORDS); }
+                b0 = ld4(I, (j + 1u) * INST_WORDS); e0 = ld2(A, (j + 1u) * AXIS_WORDS);
                 test(j, a0, c0);
                 if (++j >= n) break;
-                if (j + 1u < n) { a0 = ld4(I, (j + 1u) * INST_WORDS); c0 = ld2(A, (j + 1u) * AXIS_WORDS); }
+                a0 = ld4(I, (j + 1u) * INST_WORDS); c0 = ld2(A, (j + 1u) * AXIS_WORDS);
                 test(j, b0, e0);
                 if (++j >= n) break;
             }
