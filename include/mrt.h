@@ -141,10 +141,15 @@ typedef struct mrt_opts {
     int32_t  device;        /* HIP device ordinal for this context; -1 = current device           */
     /* Row sharding (replaces the n_dim x n_dim tile jobs of src/sampler.rs:40-41): supersampled
      * rows are dealt in blocks of shard_rows rows, block b belongs to shard (b % shard_count).
-     * shard_count = 0 or 1 => this context renders the whole frame. */
+     * shard_count = 0 or 1 => this context renders the whole frame.
+     * The layout (csrc/mrt_shard.h, computed in 64 bits for every 32-bit input): the effective shard_rows is
+     * min(shard_rows, nh) -- a block taller than the frame owns the same rows as a block of nh rows, so every row
+     * goes to shard 0 and nobody allocates for rows that do not exist;
+     * padded_rows = ceil(ceil(nh / rows) / shard_count) * rows with the effective rows, or nh when shard_count == 1.
+     * Hence local_rows <= padded_rows < 2 * nh; mrt_create checks the first before it allocates (MRT_ERR_ARG). */
     uint32_t shard_index;
-    uint32_t shard_count;
-    uint32_t shard_rows;    /* 0 => default (8) */
+    uint32_t shard_count;   /* 0 => 1 */
+    uint32_t shard_rows;    /* 0 => default (8); values above nh are taken as nh */
     /* In-process multi-GPU (the single-process reference binary): n_devices > 1 makes one
      * sub-context per device 0..n_devices-1, row-sharded as above, gathered on device 0 by one
      * RCCL ncclGather per mrt_execute (librccl.so is loaded on demand).  Mutually exclusive with

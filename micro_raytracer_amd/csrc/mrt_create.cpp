@@ -7,9 +7,11 @@
 
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mrt_ctx.h"
+#include "mrt_shard.h"
 
 using namespace mrt;
 using namespace mrt::api;
@@ -192,12 +194,21 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts,
     c->device = dev;
     c->seed = opts->seed;
     c->shard_index = opts->shard_index; c->shard_count = shard_count;
-    c->shard_rows = opts->shard_rows ? opts->shard_rows : 8;
 
-    // rows of this shard: row block b (shard_rows rows) belongs to shard b % shard_count
-    const u32 nh = c->pk.nh;
-    for (u32 y = 0; y < nh; ++y) if ((y / c->shard_rows) % shard_count == c->shard_index) c->row_of.push_back(y);
-    c->local_rows = (u32)c->row_of.size();
+    // rows of this shard and the rows its planes are allocated for (mrt_shard.h): checked before the first allocation, since a
+    // plane of fewer rows than the kernels write is an out-of-bounds device write -- a guard, no input should reach it
+    {
+        ShardLayout L = shard_layout(c->pk.nh, opts->shard_index, shard_count, opts->shard_rows);
+        if (L.local_rows > L.padded_rows || L.padded_rows > 0xffffffffull) {
+            fail(MRT_ERR_ARG, "mrt_create: shard layout of %u rows (shard %u of %u, blocks of %u): %u local rows in %llu padded rows", c->pk.nh,
+                 opts->shard_index, shard_count, opts->shard_rows, L.local_rows, (unsigned long long)L.padded_rows);
+            return nullptr;
+        }
+        c->shard_rows = L.shard_rows;              // the effective value, min(shard_rows, nh): what the kernels divide by
+        c->local_rows = L.local_rows;
+        c->padded_rows = (u32)L.padded_rows;
+        c->row_of = std::move(L.row_of);
+    }
 
     auto bail = [&](int code, const char *what, hipError_t e) { fail(code, "mrt_create: %s: %s", what, hipGetErrorString(e)); return (mrt_ctx *)nullptr; };
     hipError_t e;
@@ -208,11 +219,6 @@ static mrt_ctx *create_single(const mrt_render_desc *desc, const mrt_opts *opts,
     const size_t all_words = c->pk.blob.size();
     if ((e = c->blob.alloc(all_words ? all_words : 4)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(scene)", e);
     if ((e = hipMemcpy(c->blob.p, c->pk.blob.data(), all_words * 4, hipMemcpyHostToDevice)) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemcpy(scene)", e);
-    {
-        const u32 n_blocks = (nh + c->shard_rows - 1) / c->shard_rows;
-        c->padded_rows = ((n_blocks + shard_count - 1) / shard_count) * c->shard_rows;
-        if (shard_count == 1) c->padded_rows = nh;
-    }
     if ((e = c->accum_own.alloc(plane_floats(c.get()))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMalloc(accumulator)", e);
     c->d_accum = c->accum_own.p;
     if ((e = hipMemset(c->d_accum, 0, plane_floats(c.get()) * sizeof(float))) != hipSuccess) return bail(MRT_ERR_DEVICE, "hipMemset", e);
@@ -272,14 +278,17 @@ static mrt_ctx *create_group(const mrt_render_desc *desc, const mrt_opts *opts, 
     g->device = 0; g->seed = opts->seed;
     g->knobs = knobs;
     g->defer = (opts->flags & MRT_FLAG_DEFER) != 0 || knobs.defer;
-    g->shard_count = 1; g->shard_index = 0; g->shard_rows = opts->shard_rows ? opts->shard_rows : 8;
-    g->local_rows = g->pk.nh; g->padded_rows = g->pk.nh;
-    for (u32 y = 0; y < g->pk.nh; ++y) g->row_of.push_back(y);
+    g->shard_count = 1; g->shard_index = 0;
+    {   // the group itself owns every row; its sub-contexts deal them by the caller's shard_rows
+        ShardLayout L = shard_layout(g->pk.nh, 0, 1, opts->shard_rows);
+        g->shard_rows = L.shard_rows; g->local_rows = L.local_rows; g->padded_rows = (u32)L.padded_rows;
+        g->row_of = std::move(L.row_of);
+    }
     g->group.reset(new Group());
     Group &gr = *g->group;
     for (u32 r = 0; r < n; ++r) {
         mrt_opts o = *opts;
-        o.n_devices = 0; o.device = (int)r; o.shard_index = r; o.shard_count = n; o.shard_rows = g->shard_rows;
+        o.n_devices = 0; o.device = (int)r; o.shard_index = r; o.shard_count = n; o.shard_rows = opts->shard_rows;
         o.flags &= ~MRT_FLAG_DEFER;                   // the group defers, not its shards
         gr.subs.emplace_back(create_single(desc, &o, ext, knobs));
         if (!gr.subs.back()) return nullptr;

@@ -1,9 +1,11 @@
 """Multi-GPU row sharding: one process per GPU (torch.distributed; backend "nccl" is RCCL on ROCm).
 
 The reference merges per-tile results into one HashMap under a Mutex (src/sampler.rs:60-70).
-Here every rank owns the supersampled rows of a block-cyclic set of 8-row blocks
-(block b -> rank b % world), renders them into its own accumulator, and ONE gather per
-batch of samples moves the shard accumulators to rank 0 over xGMI.  Nothing is reduced:
+Here every rank owns the supersampled rows of a block-cyclic set of row blocks (8 rows by
+default, never more than the frame has: block b -> rank b % world), renders them into its
+own accumulator, and ONE gather per batch of samples moves the shard accumulators to rank 0
+over xGMI.  The layout is the library's (csrc/mrt_shard.h), restated
+here in Python integers, which do not wrap at 32 bits.  Nothing is reduced:
 shards are disjoint, so a ring all-reduce (per-link bound on the xGMI mesh) would only add
 traffic; a gather uses the 7 inbound links of rank 0 concurrently.
 
@@ -17,18 +19,28 @@ import numpy as np
 DEFAULT_SHARD_ROWS = 8
 
 
+def effective_shard_rows(nh: int, shard_rows: int = DEFAULT_SHARD_ROWS) -> int:
+    """The block height the library deals rows by (csrc/mrt_shard.h): 0 means the default of 8, and a block taller than the
+    frame is a block of nh rows -- min(shard_rows, nh) -- so nobody allocates for rows that do not exist."""
+    return max(1, min(int(shard_rows) or DEFAULT_SHARD_ROWS, int(nh)))
+
+
 def shard_row_index(nh: int, rank: int, world: int, shard_rows: int = DEFAULT_SHARD_ROWS) -> np.ndarray:
-    """Frame rows owned by `rank`, in local order (same rule as mrt_create, csrc/mrt_create.cpp)."""
-    y = np.arange(nh)
-    return y[(y // shard_rows) % world == rank].astype(np.int64)
+    """Frame rows owned by `rank`, in local order (same rule as mrt_create, csrc/mrt_shard.h): block b of
+    min(shard_rows, nh) rows belongs to rank b % world; world == 0 means 1.  Python integers: nothing wraps at 32 bits."""
+    y = np.arange(nh, dtype=np.int64)
+    return y[(y // effective_shard_rows(nh, shard_rows)) % (int(world) or 1) == rank].astype(np.int64)
 
 
 def padded_rows(nh: int, world: int, shard_rows: int = DEFAULT_SHARD_ROWS) -> int:
-    """Rows every shard buffer is allocated for (the largest shard), so gathers are equal-sized."""
+    """Rows every shard buffer is allocated for (the largest shard, in whole blocks), so gathers are equal-sized:
+    ceil(ceil(nh / rows) / world) * rows with rows = min(shard_rows, nh), or nh for one rank.  local rows <= this < 2 * nh."""
+    world = int(world) or 1
     if world == 1:
         return nh
-    n_blocks = (nh + shard_rows - 1) // shard_rows
-    return ((n_blocks + world - 1) // world) * shard_rows
+    rows = effective_shard_rows(nh, shard_rows)
+    n_blocks = (nh + rows - 1) // rows
+    return ((n_blocks + world - 1) // world) * rows
 
 
 def probe_gather(device=None, group=None) -> bool:

@@ -19,7 +19,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, out_path, no_gather=False):
+def _worker(rank, world, port, out_path, no_gather=False, shard_rows=8):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     for p in (ROOT, os.path.join(ROOT, "tests")):
         if p not in sys.path:
@@ -41,21 +41,26 @@ def _worker(rank, world, port, out_path, no_gather=False):
     h = _abi.build_desc(render)
     o = oracle.Oracle(h, seed=4)
     nh, nw = o.nh, o.nw
-    rows = shard_row_index(nh, rank, world)
-    # render this rank's 8-row blocks (sample indices 0..1 for every block: a fresh count per block)
+    rows = shard_row_index(nh, rank, world, shard_rows)
+    # render this rank's row blocks (sample indices 0..1 for every block: a fresh count per block); the block height is stated
+    # here, not taken from dist.py: shard_rows rows, never more than the frame has
+    R = min(shard_rows, nh)
     full = np.zeros((nh, nw, 3), np.float32)
-    for b0 in range(0, nh, 8):
-        if (b0 // 8) % world == rank:
+    mine = []
+    for b0 in range(0, nh, R):
+        if (b0 // R) % world == rank:
             o.reset()
-            o.execute(2, threads=2, rows=(b0, min(nh, b0 + 8)))
+            o.execute(2, threads=2, rows=(b0, min(nh, b0 + R)))
             a, _ = o.accum()
-            full[b0:b0 + 8] = a[b0:b0 + 8]
-    local = torch.zeros((padded_rows(nh, world), nw, 3), dtype=torch.float32)
+            full[b0:b0 + R] = a[b0:b0 + R]
+            mine += range(b0, min(nh, b0 + R))
+    assert rows.tolist() == mine
+    local = torch.zeros((padded_rows(nh, world, shard_rows), nw, 3), dtype=torch.float32)
     local[: len(rows)] = torch.from_numpy(full[rows])
     # receive buffers allocated once and reused (ShardedSampler does this): a first exchange of other contents, then the real one
     parts = [torch.empty_like(local) for _ in range(world)] if (rank == 0 or use_all_gather) else None
-    gather_frame(torch.full_like(local, 7.0), nh, nw, dst=0, use_all_gather=use_all_gather, parts=parts)
-    frame = gather_frame(local, nh, nw, dst=0, use_all_gather=use_all_gather, parts=parts)
+    gather_frame(torch.full_like(local, 7.0), nh, nw, shard_rows, dst=0, use_all_gather=use_all_gather, parts=parts)
+    frame = gather_frame(local, nh, nw, shard_rows, dst=0, use_all_gather=use_all_gather, parts=parts)
     if rank == 0:
         assert all(p.data_ptr() == q.data_ptr() for p, q in zip(parts, parts))      # still the caller's buffers
         np.save(out_path, frame.numpy())
@@ -103,6 +108,32 @@ def test_more_ranks_uneven_shards_and_the_all_gather_fallback(tmp_path, oracle_m
     h = _abi.build_desc(load_render(scenes.cornell_box2(res=(40, 44), ssaa=1, sample=2)))
     o = oracle_mod.Oracle(h, seed=4)
     o.execute(2)
+    assert np.array_equal(got, o.accum()[0])
+
+
+@pytest.mark.parametrize("world,shard_rows", [(3, 3), (3, 13), (5, 45)])
+def test_shard_rows_other_than_the_tile_height_reassemble_the_frame(tmp_path, oracle_mod, world, shard_rows):
+    """Blocks of 3 and 13 rows on 3 ranks (44 rows: a partial last block), and 5 ranks with blocks one row taller than the
+    frame, so that four ranks own nothing and every buffer is the frame's 44 rows, not 45: rank 0 assembles the
+    single-process frame bit for bit."""
+    import torch.multiprocessing as mp
+    from micro_raytracer_amd import _abi, load_render, scenes
+    from micro_raytracer_amd.dist import padded_rows
+
+    out = str(tmp_path / "frame.npy")
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_worker, args=(r, world, port, out, False, shard_rows)) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(240)
+        assert p.exitcode == 0
+    got = np.load(out)
+    h = _abi.build_desc(load_render(scenes.cornell_box2(res=(40, 44), ssaa=1, sample=2)))
+    o = oracle_mod.Oracle(h, seed=4)
+    o.execute(2)
+    assert o.nh == 44 and padded_rows(44, world, shard_rows) == {(3, 3): 15, (3, 13): 26, (5, 45): 44}[(world, shard_rows)]
     assert np.array_equal(got, o.accum()[0])
 
 

@@ -74,7 +74,7 @@ def test_bench_under_torchrun_still_works():
     assert d["n_gpus"] == 2 and d["value"] > 0
 
 
-def _worker(rank, world, port, out_path):
+def _worker(rank, world, port, out_path, res=(160, 100), shard_rows=8):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, ROOT)
     import torch
@@ -83,8 +83,8 @@ def _worker(rank, world, port, out_path):
     from micro_raytracer_amd.dist import ShardedSampler
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.cuda.set_device(0)
-    render = load_render(scenes.cornell_box2(res=(160, 100), ssaa=1, sample=3))
-    ss = ShardedSampler(render, rank, world, 0, seed=6)
+    render = load_render(scenes.cornell_box2(res=res, ssaa=1, sample=3))
+    ss = ShardedSampler(render, rank, world, 0, seed=6, shard_rows=shard_rows)
     ss.execute(2)
     ss.execute(1)
     if rank == 0:
@@ -96,23 +96,33 @@ def _worker(rank, world, port, out_path):
     dist.destroy_process_group()
 
 
-def test_sharded_sampler_three_ranks_equal_single_context(tmp_path):
+def _three_ranks_equal_single_context(tmp_path, port, res=(160, 100), shard_rows=8):
     import torch.multiprocessing as mp
     from micro_raytracer_amd import Sampler, load_render, scenes
     out = str(tmp_path / "frame.npy")
     ctx = mp.get_context("spawn")
-    procs = [ctx.Process(target=_worker, args=(r, 3, 29733, out)) for r in range(3)]
+    procs = [ctx.Process(target=_worker, args=(r, 3, port, out, res, shard_rows)) for r in range(3)]
     for p in procs:
         p.start()
     for p in procs:
         p.join(300)
         assert p.exitcode == 0
-    render = load_render(scenes.cornell_box2(res=(160, 100), ssaa=1, sample=3))
+    render = load_render(scenes.cornell_box2(res=res, ssaa=1, sample=3))
     s = Sampler(seed=6)
     s.execute(render, n_samples=3)
     ref, _ = s.accum()
     assert np.array_equal(np.load(out), ref)
     assert np.array_equal(np.load(out + ".img.npy"), s.img())
+
+
+def test_sharded_sampler_three_ranks_equal_single_context(tmp_path):
+    _three_ranks_equal_single_context(tmp_path, 29733)
+
+
+def test_sharded_sampler_three_ranks_on_five_row_blocks(tmp_path):
+    """The same three ranks on a 20 x 23 frame dealt in 5-row blocks (5 blocks, the last of 3 rows; buffers of 10 rows):
+    ShardedSampler's own layout, which it asserts equal to the library's, places the gathered rows."""
+    _three_ranks_equal_single_context(tmp_path, 29735, res=(20, 23), shard_rows=5)
 
 
 _GROUP_SCRIPT = r"""
