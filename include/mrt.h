@@ -170,13 +170,22 @@ typedef struct mrt_opts {
                                         (2, 4, ... 32 per launch, each into a plane of its own) and a call only folds its sample into
                                         the accumulator and waits for that: same samples, added in the same order -- bit for bit the
                                         plain loop -- at the rate of batched launches; MRT_LOOKAHEAD=0 in the environment switches it
-                                        off too, MRT_LOOKAHEAD=n sets the samples per launch */
+                                        off too, MRT_LOOKAHEAD=n sets the samples per launch.  Tracing ahead starts with the third
+                                        consecutive one-sample call; what was traced ahead is dropped by an mrt_execute of another size,
+                                        mrt_reset, mrt_set_accum*, mrt_execute_adaptive, and by nothing else: an observation, mrt_bind_accum
+                                        or mrt_accum_device_ptr in the middle of a run leaves it running */
 #define MRT_FLAG_DEFER 4u            /* mrt_execute only books its samples; they are traced, batched, when 1024 are booked or when
                                         the accumulator is observed or replaced (mrt_accum*, mrt_img*, mrt_set_accum*, mrt_get_stats,
                                         mrt_bind_accum).  Same samples, same image as eager execution (sums re-associated like any
                                         batched call); the Duration of a booking call is ~0.  Also set by the environment variable
                                         MRT_DEFER=1 (a non-zero number; "0" or empty is off) for unmodified callers.  Ignored while the accumulator's device memory is
-                                        visible to the caller (mrt_bind_accum / mrt_accum_device_ptr). */
+                                        visible to the caller (mrt_bind_accum / mrt_accum_device_ptr).
+                                        What is booked is never cut: the call that brings it to 1024 or more has ALL of it traced, its own
+                                        samples included, as one launch over [count, count + booked) (1020 booked and a call of 100: one
+                                        launch of 1120), and so has an observation.  An entry point of the list above traces what is booked
+                                        before it checks anything else, so one that then refuses (mrt_img on a shard, an undersized
+                                        mrt_bind_accum) has traced it all the same; mrt_execute_adaptive and mrt_adapt_half are not on the
+                                        list and trace nothing; mrt_reset drops what is booked. */
 
 typedef struct mrt_ctx mrt_ctx;
 
@@ -185,7 +194,8 @@ typedef struct mrt_ctx mrt_ctx;
 typedef struct mrt_stats {
     double   kernel_ms;      /* HIP-event time of the path-tracing kernel of the last execute    */
     double   gather_ms;      /* time of the multi-GPU gather (0 on one device)                   */
-    uint64_t samples;        /* path samples traced by the last execute on this context          */
+    uint64_t samples;        /* path samples traced by the last execute on this context: of the launch that traced booked samples
+                                (MRT_FLAG_DEFER) all of them; mrt_reset and mrt_set_accum* leave the counters as they are */
     uint64_t segments;       /* path segments (closest-hit queries) of the last execute          */
     uint32_t launches;       /* kernel launches of the last execute                              */
     uint32_t lds_bytes;      /* LDS bytes per workgroup of the path-tracing kernel               */
@@ -244,7 +254,10 @@ int mrt_bind_accum(mrt_ctx *ctx, void *dev_ptr, size_t bytes);
 int mrt_set_accum_device(mrt_ctx *ctx, const void *dev_rgb, uint32_t count);
 
 /* Replace the accumulator contents with a full frame (rgb[nh][nw][3]) and sample count,
- * e.g. on rank 0 after a gather, or to resume (the reference never persists `colors`). */
+ * e.g. on rank 0 after a gather, or to resume (the reference never persists `colors`).
+ * A sharded context (shard_count > 1) keeps the frame and its count NEXT TO its own rows: mrt_accum, mrt_sample_counts, mrt_img*,
+ * mrt_img_hdr and mrt_denoise read that frame until mrt_reset or the next mrt_set_accum*, while mrt_execute, mrt_accum_local and
+ * the device pointer go on with the shard's own rows and their own count, which the call does not touch. */
 int mrt_set_accum(mrt_ctx *ctx, const float *rgb, uint32_t count);
 
 /* Sampler::img (src/sampler.rs:80-99): mean, gamma, extended Reinhard, u8 truncation, then the

@@ -11,17 +11,35 @@
 using namespace mrt;
 using namespace mrt::api;
 
+// A copy or a fill of device memory that later launches of this context read: on the context's stream, and waited for.
+// hipMemcpy between two device buffers and hipMemset return before the device has done the work, and they run on the null
+// stream, which the context's non-blocking stream is not ordered against: the next launch (the fold of a look-ahead plane is the
+// quickest) would read the accumulator while the copy still writes it, and the copy would then overwrite that sample.
+static int copy_on_stream(mrt_ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+{
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    return MRT_OK;
+}
+static int zero_on_stream(mrt_ctx *c, void *dst, size_t bytes)
+{
+    HIP_TRY(hipMemsetAsync(dst, 0, bytes, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    return MRT_OK;
+}
+
 // mrt_set_accum / mrt_set_accum_device on a single-device context: the whole frame into the accumulator, or, on a sharded
 // context, next to its own rows (only mrt_img and mrt_accum read it there)
 static int set_frame(mrt_ctx *c, const void *rgb, hipMemcpyKind kind, uint32_t count)
 {
     const size_t floats = (size_t)c->pk.nw * c->pk.nh * 3;
+    int rc;
     if (c->shard_count == 1) {
-        HIP_TRY(hipMemcpy(c->d_accum, rgb, floats * sizeof(float), kind));
+        if ((rc = copy_on_stream(c, c->d_accum, rgb, floats * sizeof(float), kind))) return rc;
         c->count = count;
     } else {
         if (!c->full.p) HIP_TRY(c->full.alloc(floats));
-        HIP_TRY(hipMemcpy(c->full.p, rgb, floats * sizeof(float), kind));
+        if ((rc = copy_on_stream(c, c->full.p, rgb, floats * sizeof(float), kind))) return rc;
         c->full_count = count;
     }
     ok();
@@ -151,7 +169,7 @@ int mrt_bind_accum(mrt_ctx *c, void *dev_ptr, size_t bytes)
     float *dst = dev_ptr ? (float *)dev_ptr : c->accum_own.p;
     if (dev_ptr && bytes < need) return fail(MRT_ERR_ARG, "mrt_bind_accum: buffer of %zu bytes, need %zu", bytes, need);     // nothing changed
     if (dst != c->d_accum) {
-        HIP_TRY(hipMemcpy(dst, c->d_accum, need, hipMemcpyDeviceToDevice));
+        if (const int rc = copy_on_stream(c, dst, c->d_accum, need, hipMemcpyDeviceToDevice)) return rc;
         c->d_accum = dst;
         c->P.accum = dst;
     }
@@ -200,7 +218,7 @@ int mrt_reset(mrt_ctx *c)
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipMemset(c->full.p, 0, (size_t)c->pk.nh * c->pk.nw * 3 * sizeof(float)));
     } else {
-        HIP_TRY(hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float)));
+        if ((rc = zero_on_stream(c, c->d_accum, plane_floats(c) * sizeof(float)))) return rc;
         c->full.reset();
     }
     c->count = 0; c->full_count = 0;

@@ -107,7 +107,8 @@ int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, d
     if ((rc = adapt_run(c, a, info)))
         return keep_first_error(rc, [&] {            // nothing half done stays behind: the context is an empty uniform one again
             (void)hipStreamSynchronize(c->stream.get());
-            (void)hipMemset(c->d_accum, 0, plane_floats(c) * sizeof(float));
+            (void)hipMemsetAsync(c->d_accum, 0, plane_floats(c) * sizeof(float), c->stream.get());      // on the stream the next launch runs on
+            (void)hipStreamSynchronize(c->stream.get());
             (void)hipGetLastError();
             c->adaptive = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
         });
