@@ -1,7 +1,7 @@
 // mrt_adapt.hip — gfx950 kernels of adaptive sampling (mrt_execute_adaptive).
 //
-//   pt_megakernel_list    pt_megakernel over a list of 8x8 wave tiles (the tiles still running); a translation unit of its
-//                         own, so that the ordinary launches are compiled exactly as without it
+//   pt_megakernel<.., TileList>   pt_megakernel (mrt_pt_kernel.h) over a list of 8x8 wave tiles (the tiles still running); its
+//                         144 instantiations are compiled here, next to the 144 ordinary ones of mrt_kernels.hip
 //   reduce_chunks_listed  reduce_chunks over the listed tiles, into the accumulator and (even rounds) the half buffer
 //   adapt_eval            the stop rule (mrt_adapt.h) per listed tile, one wavefront per tile
 //   adapt_compact         the next tile list, in list order
@@ -12,13 +12,9 @@
 
 #include "mrt_adapt.h"
 #include "mrt_kernels.h"
-#include "mrt_megakernel.h"
+#include "mrt_pt_kernel.h"
 
 namespace mrt {
-
-#define MRT_PT_LIST 1
-#include "mrt_pt_kernel.h"
-#undef MRT_PT_LIST
 
 // One wavefront per listed 8x8 tile, lane = pixel: wave tile list[blockIdx.x] -> this lane's accumulator word; false for lanes
 // outside the frame
@@ -100,10 +96,10 @@ __global__ void __launch_bounds__(1024) adapt_compact(const u32 *__restrict__ li
 // ---- launchers (declared in mrt_kernels.h) ----
 hipError_t launch_pt_list(const Params &P, const TileList &TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst, hipStream_t stream)
 {
-    return launch_pt_inst(P, &TL, grid, lds, block_threads, scene_in_lds, inst, stream);
+    return launch_pt_inst(P, grid, lds, block_threads, scene_in_lds, inst, stream, TL);
 }
 
-hipError_t configure_pt_list(size_t max_lds_bytes) { return configure_pt_inst(max_lds_bytes); }
+hipError_t configure_pt_list(size_t max_lds_bytes) { return configure_pt_inst<TileList>(max_lds_bytes); }
 
 hipError_t launch_reduce_chunks_listed(float *accum, float *half, const float *partial, const u32 *list, u32 n_listed, u32 nw, u32 nh,
                                        size_t stride, u32 n_chunks, hipStream_t stream)

@@ -13,6 +13,7 @@
 
 #include "mrt_denoise.h"
 #include "mrt_kernels.h"
+#include "mrt_megakernel.h"      // MRT_SHAPES_L2
 
 namespace mrt {
 
@@ -59,31 +60,77 @@ struct DnPassArgs {
 
 constexpr u32 kDnB = 16, kDnT = kDnB + 4;   // output block, LDS tile with the 2-entry halo
 
-#define MRT_DN_ENV 0
-#include "mrt_dn_pass_kernel.h"
-#undef MRT_DN_ENV
-#define MRT_DN_ENV 1
-#include "mrt_dn_pass_kernel.h"
-#undef MRT_DN_ENV
+// ENV: the kernel of contexts with an environment texture, whose miss pixels are demodulated by their backdrop
+// E(d) too (mrt_denoise.h dn_demod)
+template <bool ENV>
+__global__ void __launch_bounds__(256) dn_pass(const DnPassArgs A)
+{
+    __shared__ float4 s_e[kDnT * kDnT];
+    __shared__ float4 s_g0[kDnT * kDnT];
+    __shared__ float4 s_g1[kDnT * kDnT];
+    // block -> residue class (rx, ry) and block (bx, by) of that class's sub-image; sub-image pixel (i, j) is frame pixel
+    // (rx + s * i, ry + s * j)
+    const u32 rx = blockIdx.x % A.cx, bx = blockIdx.x / A.cx;
+    const u32 ry = blockIdx.y % A.cy, by = blockIdx.y / A.cy;
+    const u32 s = A.step;
+    const size_t np = (size_t)A.nw * A.nh;
+    for (u32 t = threadIdx.x; t < kDnT * kDnT; t += 256u) {
+        const u32 lj = t / kDnT, li = t - lj * kDnT;
+        const long long si = (long long)(bx * kDnB + li) - 2, sj = (long long)(by * kDnB + lj) - 2;
+        const long long fx = (long long)rx + (long long)s * si, fy = (long long)ry + (long long)s * sj;
+        float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g0 = e, g1 = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (si >= 0 && sj >= 0 && fx < (long long)A.nw && fy < (long long)A.nh) {
+            const size_t p = (size_t)fy * A.nw + (size_t)fx;
+            g0 = A.guide[p];
+            g1 = A.guide[np + p];
+            if (A.first) {
+                const float r = mean_rc({A.accum, A.rc, A.tile_count, A.nw}, (u32)fx, (u32)fy);
+                e.x = (A.accum[3 * p] * r) / dn_demod(A.albedo[3 * p], g1.w, ENV);
+                e.y = (A.accum[3 * p + 1] * r) / dn_demod(A.albedo[3 * p + 1], g1.w, ENV);
+                e.z = (A.accum[3 * p + 2] * r) / dn_demod(A.albedo[3 * p + 2], g1.w, ENV);
+            } else {
+                e = A.e_in[p];
+            }
+        }
+        s_e[t] = e; s_g0[t] = g0; s_g1[t] = g1;
+    }
+    __syncthreads();
+    const u32 li = threadIdx.x & 15u, lj = threadIdx.x >> 4;
+    const u32 fx = rx + s * (bx * kDnB + li), fy = ry + s * (by * kDnB + lj);
+    if ((unsigned long long)rx + (unsigned long long)s * (bx * kDnB + li) >= A.nw ||
+        (unsigned long long)ry + (unsigned long long)s * (by * kDnB + lj) >= A.nh) return;
+    const u32 c = (lj + 2u) * kDnT + li + 2u;
+    auto guide_of = [&](u32 k) { const float4 a = s_g0[k], b = s_g1[k]; DnGuide g; g.nx = a.x; g.ny = a.y; g.nz = a.z; g.t = a.w; g.px = b.x; g.py = b.y; g.pz = b.z; g.hit = b.w; return g; };
+    const DnGuide gp = guide_of(c);
+    const float4 ep4 = s_e[c];
+    const float ep[3] = {ep4.x, ep4.y, ep4.z};
+    DnAcc acc;
+    for (int dy = -2; dy <= 2; ++dy)
+        for (int dx = -2; dx <= 2; ++dx) {
+            const u32 k = (u32)((int)(lj + 2u) + dy) * kDnT + (u32)((int)(li + 2u) + dx);
+            const float4 eq4 = s_e[k];
+            const float eq[3] = {eq4.x, eq4.y, eq4.z};
+            acc.add(dn_tap_weight(dn_k5(dx) * dn_k5(dy), ep, eq, gp, guide_of(k), A.sc, A.sn, A.sp), eq);
+        }
+    float r[3];
+    acc.result(ep, r);
+    const size_t p = (size_t)fy * A.nw + fx;
+    if (A.last) {
+        for (u32 ch = 0; ch < 3u; ++ch) A.out[3 * p + ch] = r[ch] * dn_demod(A.albedo[3 * p + ch], gp.hit, ENV);
+    } else {
+        A.e_out[p] = make_float4(r[0], r[1], r[2], 0.0f);
+    }
+}
 
 // ---- launchers (declared in mrt_kernels.h) ----
 hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo, i32 *ids, hipStream_t stream)
 {
-    constexpr u32 FN = F_ALL & ~F_TRI;
     const u32 inst = pt_instantiation(256u, false, features);       // the L2 shape
     const dim3 grid((P.nw + 15u) / 16u, (P.nh + 15u) / 16u);
     float4 *g = reinterpret_cast<float4 *>(guide);
-    switch (inst) {
-    case FN: hipLaunchKernelGGL((aov_first_hit<FN>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case F_ALL: hipLaunchKernelGGL((aov_first_hit<F_ALL>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case FN | F_BVH: hipLaunchKernelGGL((aov_first_hit<FN | F_BVH>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case F_ALL | F_BVH: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_BVH>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case F_ALL | F_VATTR: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_VATTR>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case F_ALL | F_BVH | F_VATTR: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_BVH | F_VATTR>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case F_ALL | F_VATTR | F_ENV: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_VATTR | F_ENV>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    case F_ALL | F_BVH | F_VATTR | F_ENV: hipLaunchKernelGGL((aov_first_hit<F_ALL | F_BVH | F_VATTR | F_ENV>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
-    default: return hipErrorInvalidConfiguration;
-    }
+#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((aov_first_hit<(F)>), grid, dim3(256), 0, stream, P, g, albedo, ids); break;
+    switch (inst) { MRT_SHAPES_L2 default: return hipErrorInvalidConfiguration; }
+#undef MRT_CASE_L2
     return hipGetLastError();
 }
 
@@ -110,8 +157,8 @@ hipError_t launch_denoise(const MeanSrc &S, const float *guide, const float *alb
         // sub-images of a class are at most ceil(n / s) wide / high
         const u32 sw = (nw + A.step - 1u) / A.step, sh = (nh + A.step - 1u) / A.step;
         const dim3 grid(A.cx * ((sw + kDnB - 1u) / kDnB), A.cy * ((sh + kDnB - 1u) / kDnB));
-        if (env) hipLaunchKernelGGL(dn_pass_env, grid, dim3(256), 0, stream, A);
-        else hipLaunchKernelGGL(dn_pass, grid, dim3(256), 0, stream, A);
+        if (env) hipLaunchKernelGGL(dn_pass<true>, grid, dim3(256), 0, stream, A);
+        else hipLaunchKernelGGL(dn_pass<false>, grid, dim3(256), 0, stream, A);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -3,7 +3,7 @@
 //   pt_megakernel    Sampler::execute (reference src/sampler.rs:28-78) and everything of src/rt.rs
 //                    it reaches: one lane per supersampled pixel, all samples of the launch in
 //                    registers, scene staged in LDS, one accumulator read-modify-write per launch.
-//   (pt_megakernel_list, the same over a list of 8x8 tiles, and the other kernels of adaptive sampling: mrt_adapt.hip)
+//   (pt_megakernel<.., TileList>, the same over a list of 8x8 tiles, and the other kernels of adaptive sampling: mrt_adapt.hip)
 //   tonemap_u8       Sampler::img's per-pixel map (src/sampler.rs:84-96); tonemap_tiles_u8: with each 8x8 tile's own sample count
 //   lanczos3_v/_h    image::imageops::resize(.., Lanczos3) (src/sampler.rs:98): vertical pass to f32,
 //                    horizontal pass to u8, taps precomputed on the host.
@@ -15,13 +15,10 @@
 #include "mrt_kernels.h"
 #include "mrt_megakernel.h"
 #include "mrt_post.h"
+#include "mrt_pt_kernel.h"
 #include "mrt_trace.h"
 
 namespace mrt {
-
-#define MRT_PT_LIST 0
-#include "mrt_pt_kernel.h"
-#undef MRT_PT_LIST
 
 // acc[p] += chunk sums in chunk order (the canonical order of mrt_trace.h), one thread per accumulator word
 __global__ void __launch_bounds__(256) reduce_chunks(float *__restrict__ accum, const float *__restrict__ partial, size_t n_words,
@@ -184,12 +181,12 @@ hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 
     const size_t lds = pt_lds_bytes(P, block_threads, scene_in_lds, features);
     const u32 inst = pt_instantiation(block_threads, scene_in_lds, features);
     if (TL) return launch_pt_list(P, *TL, grid, lds, block_threads, scene_in_lds, inst, stream);
-    return launch_pt_inst(P, nullptr, grid, lds, block_threads, scene_in_lds, inst, stream);
+    return launch_pt_inst(P, grid, lds, block_threads, scene_in_lds, inst, stream);
 }
 
 hipError_t configure_pt(size_t max_lds_bytes)
 {
-    const hipError_t e = configure_pt_inst(max_lds_bytes);
+    const hipError_t e = configure_pt_inst<>(max_lds_bytes);
     return e != hipSuccess ? e : configure_pt_list(max_lds_bytes);
 }
 

@@ -1,5 +1,5 @@
-// mrt_megakernel.h — launch bounds of the path-tracing kernel (pt_megakernel in mrt_kernels.hip,
-// pt_megakernel_list in mrt_adapt.hip: mrt_pt_kernel.h) and the list of its instantiations.
+// mrt_megakernel.h — launch bounds of the path-tracing kernel (pt_megakernel of mrt_pt_kernel.h: the ordinary instantiations
+// in mrt_kernels.hip, the tile-list ones in mrt_adapt.hip) and the list of its instantiations.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,7 +43,7 @@ constexpr int waves_for(u32 feat_, int block_threads)
 #endif
 }
 
-// Instantiations of both kernels, per workgroup size (MRT_CASE(T, F) is defined at each use): one per feature set for the two
+// Instantiations of the kernel (with either tile source), per workgroup size (MRT_CASE(T, F) is defined at each use): one per feature set for the two
 // common launch shapes with the scene in LDS: 256 threads (2x2 wave tiles) and 64 threads (one 8x8 tile per workgroup, used
 // when the frame has too few tiles to balance 256 CUs with 4-wave workgroups).  The 512-thread shape (one LDS copy per CU,
 // scenes of 78-160 KB) and the scene-in-L2 fallback and the 1024-thread shape (one LDS copy + stash per CU, 16 waves) carry

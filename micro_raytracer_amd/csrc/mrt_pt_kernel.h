@@ -1,20 +1,25 @@
-// mrt_pt_kernel.h — the path-tracing kernel, included twice (no include guard): by mrt_kernels.hip with MRT_PT_LIST 0 as
-// pt_megakernel, the ordinary launches, and by mrt_adapt.hip with MRT_PT_LIST 1 as pt_megakernel_list, the tile-list
-// launches of adaptive sampling (argument TL).  Two translation units and the preprocessor, not a shared function: the
-// ordinary kernel is then exactly the text it was, and the compiler's decisions for it (registers, spills) do not move.
-// The host side of each kernel -- the launch of one instantiation and the LDS attribute of all of them -- comes from the end
-// of this file as well.  Needs mrt_megakernel.h (lds_stash_for, waves_for, the instantiation lists) and mrt_trace.h; expands
-// inside namespace mrt.
-#ifndef MRT_PT_LIST
-#error "define MRT_PT_LIST (0: pt_megakernel, 1: pt_megakernel_list) before including mrt_pt_kernel.h"
-#endif
+// mrt_pt_kernel.h — the path-tracing kernel and the host side of its instantiations.  ONE template for both tile sources: the
+// ordinary launches (mrt_kernels.hip: pt_megakernel<b, T, F>, every tile of the shard) and the tile-list launches of adaptive
+// sampling (mrt_adapt.hip: pt_megakernel<b, T, F, TileList>, with the list as a third kernel argument).  The tile source is a
+// trailing parameter pack, empty or one TileList, so the ordinary kernel keeps its name and its argument block, and the body is
+// the kernel's own: a body or a staging prologue moved into a shared device function changes the register allocation of the
+// headline kernel.
+#pragma once
+#include <hip/hip_runtime.h>
 
-template <bool SCENE_IN_LDS, int BLOCK_THREADS, u32 FEAT>
-#if MRT_PT_LIST
-__global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS)) pt_megakernel_list(const Params P, const u32 *__restrict__ blob_g, const TileList TL)
-#else
-__global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS)) pt_megakernel(const Params P, const u32 *__restrict__ blob_g)
-#endif
+#include "mrt_megakernel.h"      // waves_for, lds_stash_for, the instantiation lists
+#include "mrt_trace.h"
+
+namespace mrt {
+
+// The tile source of a launch: tile i of `all` (no list: the tiles of the shard in row-major order), or entry i of a TileList
+__device__ inline u32 tile_count(u32 all) { return all; }
+__device__ inline u32 tile_count(u32, const TileList &TL) { return TL.n; }
+__device__ inline u32 tile_at(u32 i) { return i; }
+__device__ inline u32 tile_at(u32 i, const TileList &TL) { return TL.tiles[i]; }
+
+template <bool SCENE_IN_LDS, int BLOCK_THREADS, u32 FEAT, class... Tiles>
+__global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS)) pt_megakernel(const Params P, const u32 *__restrict__ blob_g, const Tiles... TL)
 {
     extern __shared__ uint4 lds_blob[];
     const float *F;
@@ -34,11 +39,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
     const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     Scn S;
     S.F = F;
-#ifdef MRT_UNIFORM_SMEM
-    S.U = reinterpret_cast<const float *>(blob_g);
-#else
     S.U = F;
-#endif
     S.G = reinterpret_cast<const float *>(blob_g);
     S.P = &P;
     // behind the staged scene (16-byte aligned): [lane stash: ST_SLOTS x blockDim floats] [walk areas: P.walk_cap x blockDim words]
@@ -86,14 +87,10 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
     // Persistent workgroup (more than one wavefront, P.persist_grid set): its wavefronts draw tiles from a counter until the
     // launch is out of tiles, so a CU never waits for the slowest wavefront of a workgroup (whose LDS copy of the scene
     // would otherwise keep the next workgroup out).  Otherwise blockIdx addresses the one tile of each wavefront.
-    // A tile-list launch (pt_megakernel_list) maps its tile index i -- counter-drawn or blockIdx-addressed -- to TL.tiles[i].
+    // A tile-list launch maps its tile index i -- counter-drawn or blockIdx-addressed -- to TL.tiles[i].
     const bool persist = BLOCK_THREADS > 64 && P.persist_grid != 0u;
     const u32 n_tx = (P.nw + 7u) >> 3, n_ty = (P.local_rows + 7u) >> 3;
-#if MRT_PT_LIST
-    const u32 per_k = TL.n, total = per_k * P.k_split;
-#else
-    const u32 per_k = n_tx * n_ty, total = per_k * P.k_split;
-#endif
+    const u32 per_k = tile_count(n_tx * n_ty, TL...), total = per_k * P.k_split;
     for (;;) {
         u32 tx = blockIdx.x * P.tiles_x + wave % P.tiles_x, ty = blockIdx.y * P.tiles_y + wave / P.tiles_x, k = blockIdx.z;
         if (persist) {
@@ -102,24 +99,17 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
             t = __builtin_amdgcn_readfirstlane(t);
             if (t >= total) break;
             k = t / per_k;
-#if MRT_PT_LIST
-            const u32 r = TL.tiles[t - k * per_k];
-#else
-            const u32 r = t - k * per_k;
-#endif
+            const u32 r = tile_at(t - k * per_k, TL...);
             ty = r / n_tx;
             tx = r - ty * n_tx;
-        }
-#if MRT_PT_LIST
-        else {
+        } else if constexpr (sizeof...(Tiles) != 0) {
             // plain grid of a list launch: grid.x = ceil(n_listed / waves per workgroup), wavefront -> list entry
             const u32 i = blockIdx.x * (P.tiles_x * P.tiles_y) + wave;
             if (i >= per_k) break;
-            const u32 r = TL.tiles[i];
+            const u32 r = tile_at(i, TL...);
             ty = r / n_tx;
             tx = r - ty * n_tx;
         }
-#endif
         do_tile(tx, ty, k);
         if (!persist) break;
     }
@@ -139,21 +129,14 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
     }
 }
 
-// ---- host side of this kernel (static in each translation unit; the exported launchers are in mrt_kernels.hip / mrt_adapt.hip)
-#if MRT_PT_LIST
-#define MRT_PT_KERNEL pt_megakernel_list
-#define MRT_PT_ARGS P, P.blob, *TL
-#else
-#define MRT_PT_KERNEL pt_megakernel
-#define MRT_PT_ARGS P, P.blob
-#endif
+// ---- host side of one tile source (the exported launchers are in mrt_kernels.hip / mrt_adapt.hip, each with its own 144 kernels)
 // Launch instantiation `inst` (pt_instantiation) of a launch shape, grid and LDS bytes as launch_pt computed them; TL: the tile
-// list of pt_megakernel_list (unused by pt_megakernel).  A shape without that instantiation is an invalid configuration.
-static hipError_t launch_pt_inst(const Params &P, const TileList *TL, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst,
-                                 hipStream_t stream)
+// list of a tile-list launch, or nothing.  A shape without that instantiation is an invalid configuration.
+template <class... Tiles>
+inline hipError_t launch_pt_inst(const Params &P, dim3 grid, size_t lds, u32 block_threads, bool scene_in_lds, u32 inst, hipStream_t stream, const Tiles &...TL)
 {
-#define MRT_CASE(T, F) case (F): hipLaunchKernelGGL((MRT_PT_KERNEL<true, T, (F)>), grid, dim3(T), lds, stream, MRT_PT_ARGS); return hipGetLastError();
-#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((MRT_PT_KERNEL<false, 256, (F)>), grid, dim3(256), lds, stream, MRT_PT_ARGS); return hipGetLastError();
+#define MRT_CASE(T, F) case (F): hipLaunchKernelGGL((pt_megakernel<true, T, (F), Tiles...>), grid, dim3(T), lds, stream, P, P.blob, TL...); return hipGetLastError();
+#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((pt_megakernel<false, 256, (F), Tiles...>), grid, dim3(256), lds, stream, P, P.blob, TL...); return hipGetLastError();
     if (!scene_in_lds) {
         if (block_threads != 256u) return hipErrorInvalidConfiguration;
         switch (inst) { MRT_SHAPES_L2 default: break; }
@@ -171,16 +154,17 @@ static hipError_t launch_pt_inst(const Params &P, const TileList *TL, dim3 grid,
     return hipErrorInvalidConfiguration;
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for every scene-in-LDS instantiation of this kernel
-static hipError_t configure_pt_inst(size_t max_lds_bytes)
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for every scene-in-LDS instantiation of one tile source
+template <class... Tiles>
+inline hipError_t configure_pt_inst(size_t max_lds_bytes)
 {
     const int b = (int)max_lds_bytes;
     hipError_t e;
 #define MRT_CASE(T, F) \
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(&MRT_PT_KERNEL<true, T, (F)>), hipFuncAttributeMaxDynamicSharedMemorySize, b)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pt_megakernel<true, T, (F), Tiles...>), hipFuncAttributeMaxDynamicSharedMemorySize, b)) != hipSuccess) return e;
     MRT_SHAPES_64 MRT_SHAPES_256 MRT_SHAPES_512 MRT_SHAPES_1024
 #undef MRT_CASE
     return hipSuccess;
 }
-#undef MRT_PT_KERNEL
-#undef MRT_PT_ARGS
+
+}  // namespace mrt

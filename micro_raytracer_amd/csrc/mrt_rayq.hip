@@ -21,6 +21,7 @@ __global__ void __launch_bounds__(256) rayq(const Params P, const u32 *__restric
                                             const float *__restrict__ dir, u32 *__restrict__ out)
 {
     constexpr int BLOCK_THREADS = 256;
+    // the staging prologue of pt_megakernel (mrt_pt_kernel.h has the original), written out: a shared helper is not free
     extern __shared__ uint4 lds_blob[];
     const float *F;
     const u32 staged_words = !SCENE_IN_LDS ? 0u : staged_words_for(P, FEAT);
@@ -35,11 +36,7 @@ __global__ void __launch_bounds__(256) rayq(const Params P, const u32 *__restric
     }
     Scn S;
     S.F = F;
-#ifdef MRT_UNIFORM_SMEM
-    S.U = reinterpret_cast<const float *>(blob_g);
-#else
     S.U = F;
-#endif
     S.G = reinterpret_cast<const float *>(blob_g);
     S.P = &P;
     // behind the staged scene (16-byte aligned): [lane stash region, unused here] [walk areas: P.walk_cap x blockDim words]
@@ -112,7 +109,7 @@ bool rayq_has(bool scene_in_lds, u32 inst)
 
 // ---- mrt_selftest_instantiations (include/mrt.h): host only, no device ----
 // The rows are the expansion of the MRT_SHAPES_* lists of mrt_megakernel.h, the text launch_pt_inst (mrt_pt_kernel.h) dispatches
-// over: one row per (block_threads, scene_in_lds, FEAT) that exists as pt_megakernel and pt_megakernel_list.
+// over: one row per (block_threads, scene_in_lds, FEAT) that exists as pt_megakernel<.., F> and pt_megakernel<.., F, TileList>.
 extern "C" uint32_t mrt_selftest_instantiations(uint32_t *threads, uint32_t *scene_in_lds, uint32_t *feat, uint32_t cap)
 {
     using namespace mrt;

@@ -19,6 +19,7 @@ template <bool SCENE_IN_LDS, u32 FEAT>
 __global__ void __launch_bounds__(256, waves_for(FEAT, 256)) pt_rays(const Params P, const u32 *__restrict__ blob_g, u32 n, const float *__restrict__ orig,
                                                                      const float *__restrict__ dir, const u32 *__restrict__ key)
 {
+    // the staging prologue of pt_megakernel (mrt_pt_kernel.h has the original), written out: a shared helper is not free
     extern __shared__ uint4 lds_blob[];
     const float *F;
     if (SCENE_IN_LDS) {
@@ -32,11 +33,7 @@ __global__ void __launch_bounds__(256, waves_for(FEAT, 256)) pt_rays(const Param
     }
     Scn S;
     S.F = F;
-#ifdef MRT_UNIFORM_SMEM
-    S.U = reinterpret_cast<const float *>(blob_g);
-#else
     S.U = F;
-#endif
     S.G = reinterpret_cast<const float *>(blob_g);
     S.P = &P;
     S.wk = nullptr; S.wk_stride = 256;                 // (no feature set of MRT_RAYS_LIST has a walk area)

@@ -256,7 +256,7 @@ MRT_HD u32 staged_words_for(const Params &P, u32 feat) { return (feat & F_DEEP) 
 constexpr bool has_walk_area(u32 feat) { return (feat & F_TRI) && (feat & F_BOX) && (feat & F_COLD); }
 
 // Tile-list launches (adaptive sampling, mrt_execute_adaptive): only the n 8x8 wave tiles tiles[i] = ty * n_tx + tx are traced.
-// A kernel argument of its own (pt_megakernel_list), not a Params field: the ordinary launches keep their argument block.
+// A kernel argument of its own (pt_megakernel<.., TileList>), not a Params field: the ordinary launches keep their argument block.
 struct TileList {
     const u32 *tiles;
     u32 n;

@@ -16,19 +16,6 @@
 
 namespace mrt {
 
-#ifndef MRT_UNIFORM_TAG              // 0: instance tags stay per-lane values in the linear scans (experiment knob)
-#define MRT_UNIFORM_TAG 1
-#endif
-#ifndef MRT_T0_FROM_KEY              // 0: the closest hit's t0 is selected per candidate like its other fields (experiment knob)
-#define MRT_T0_FROM_KEY 1
-#endif
-#ifndef MRT_NZFIN_PRODUCT            // 0: three class checks per shifted origin instead of one on the product (experiment knob)
-#define MRT_NZFIN_PRODUCT 1
-#endif
-#ifndef MRT_SHADOW_QUEUE            // 1: shadow walks of kernels with a walk area postpone every leaf too (experiment: the x86 round
-                                    // model says -12 % box steps per wavefront, the GPU 3669 against 3721 Msamples/s: off)
-#define MRT_SHADOW_QUEUE 0
-#endif
 #ifndef MRT_LEAF_QUEUE              // build-time experiment knob (make EXTRA=-D...)
 #define MRT_LEAF_QUEUE 8u
 #endif
@@ -104,7 +91,7 @@ MRT_HD bool nzfin(float x)
 MRT_HD bool nzfin3(V3 v) { return nzfin(v.x) && nzfin(v.y) && nzfin(v.z); }
 // a SUFFICIENT test with one class check: a finite non-zero product has three finite non-zero factors (a zero factor gives 0 or
 // NaN, an infinite or NaN one inf or NaN); products that under- or overflow (|x y z| outside 1e-45 .. 3e38) answer false
-MRT_HD bool nzfin3_product(V3 v) { return MRT_NZFIN_PRODUCT ? nzfin((v.x * v.y) * v.z) : nzfin3(v); }
+MRT_HD bool nzfin3_product(V3 v) { return nzfin((v.x * v.y) * v.z); }
 // 24-bit multiply (v_mul_u32_u24: full rate, where v_mul_lo_u32 is not); both factors below 2^24
 MRT_HD u32 mul24(u32 a, u32 b)
 {
@@ -276,9 +263,9 @@ typedef __attribute__((address_space(3))) volatile char lds_char;
 #endif
 
 struct Scn {
-    const float *F;      // the packed scene (LDS): per-lane (divergent) lookups
-    const float *U;      // the same blob for wave-uniform reads of the traversal loop: LDS, or global memory
-                         // read through the scalar cache into SGPRs (MRT_UNIFORM_SMEM)
+    const float *F;      // the packed scene (LDS, or global memory in the L2 shape): per-lane (divergent) lookups
+    const float *U;      // the same pointer, for the wave-uniform reads of the traversal loop; every kernel and the x86 harness
+                         // (tests/emu/lane_host.h) set it to F
     const float *G;      // the whole blob in global memory (the octree leaf lists are not staged when every mesh has a TBVH)
     const Params *P;
     void *wk;            // this lane's walk area (device: an LDS column, entry e at wk[e * wk_stride]; x86 test build: unused)
@@ -842,13 +829,14 @@ MRT_HD bool mesh_isect(const Scn &S, u32 mesh, V3 ro, V3 rd, float dd, V3 m, V3 
         const float *B0 = F + P.off_tbvh;
         TriBest best;
         u32 node = tb;
-        if constexpr ((!ANY || MRT_SHADOW_QUEUE) && has_walk_area(FEAT)) {
+        if constexpr (!ANY && has_walk_area(FEAT)) {
             // Closest-hit walk with EVERY leaf postponed: the box walk runs on until the tree is exhausted (or the lane's queue
             // of kQ = Params.walk_cap leaves is full), then the exact tests of all queued leaves run together, one triangle per lane per trip.
             // A wavefront pays, per round, the longest box walk and the longest triangle list of its lanes: with two leaves
             // per round (below) that is 76 box steps + 12 triangle tests per loop iteration on the 967-triangle bench mesh,
             // with one round per walk 46 + 11 (tests/emu/round_probe.cpp).  Shadow queries keep the two-leaf rounds: their
-            // first candidate ends the walk.  The candidate set, and with it the answer, is the same in any order.
+            // first candidate ends the walk (postponing every leaf there too: -12 % box steps per wavefront in the x86 round model,
+            // but 3669 against 3721 Msamples/s on the GPU).  The candidate set, and with it the answer, is the same in any order.
             const u32 kQ = P.walk_cap;                             // kLeafQueue entries at least (plan_launch)
             WalkMem q(S);
             for (;;) {
@@ -955,7 +943,7 @@ MRT_HD bool isect_instance(const Scn &S, const RayPre &ray, u32 i, const F4 &ia,
     const float *F = S.U;
     const Params &P = *S.P;
     const V3 pos = v3(ia.x, ia.y, ia.z);
-    const u32 tag = (UNIFORM && (FEAT & F_TRI) && MRT_UNIFORM_TAG) ? wave_uniform(f2u(ib.x)) : f2u(ib.x);
+    const u32 tag = (UNIFORM && (FEAT & F_TRI)) ? wave_uniform(f2u(ib.x)) : f2u(ib.x);
     // (F_IDENT kernels: the kind is all that is left of the tag in the scan; dispatched on a scalar copy of it, +0.7 %)
     const u32 kind = (UNIFORM && (FEAT & F_IDENT)) ? wave_uniform(tag & TAG_KIND_MASK) : (tag & TAG_KIND_MASK);
     const bool ident = (FEAT & F_IDENT) ? true : (tag & TAG_IDENT) != 0;
@@ -1052,7 +1040,7 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
             best_key = key;
             best.rend = 0; best.inst = i; best.t1 = t1; best.i0 = i0; best.i1 = i1;
             // (kernels without an instance BVH recover t0 from its key after the scan: one select less per candidate, 4 cycles)
-            if constexpr ((FEAT & F_BVH) != 0 || !MRT_T0_FROM_KEY) best.t0 = t0;
+            if constexpr ((FEAT & F_BVH) != 0) best.t0 = t0;
         }
         return false;
     };
@@ -1076,7 +1064,7 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
     //   pos_k + (+-0) is pos_k for pos_k != 0 and +0 on both routes for pos_k == +-0 (a -0 difference needs o_k == -0 and
     //   pos_k == +0).  Order, strict comparison, prefetch and the t0-from-key recovery are the generic scan's.
     bool scanned = false;
-    if constexpr (!ANY && FEAT == F_IDENT && MRT_T0_FROM_KEY) {
+    if constexpr (!ANY && FEAT == F_IDENT) {
         const V3 o = ray_.o, d = ray_.d;
         // (one predicate, no short-circuit branches: the test runs once per query with all lanes on)
         const bool tame = (int)in_window(d.x) & (int)in_window(d.y) & (int)in_window(d.z) & (int)(fabs_(o.x) <= kAxisMax) & (int)(fabs_(o.y) <= kAxisMax) &
@@ -1280,7 +1268,7 @@ MRT_HD bool trace(const Scn &S, const RayPre &ray_, Hit &best)
         }
     }
     if (best.rend < 0) return false;
-    if constexpr ((FEAT & F_BVH) == 0 && MRT_T0_FROM_KEY) {
+    if constexpr ((FEAT & F_BVH) == 0) {
         // total_key is its own inverse (the sign bit stays); a NaN distance comes back as a NaN (payloads are not part of the contract)
         const i32 k = best_key;
         best.t0 = u2f((u32)(k ^ (i32)(((u32)(k >> 31)) >> 1)));

@@ -4,8 +4,8 @@
 
 Without a GPU: the dispatch is closed and the recipes complete (plan_launch); every reduced feature set renders its recipe scene
 on x86 (tests/emu/census_probe.cpp) bit for bit like the full set and within the oracle's bar; every recipe scene's x86 render meets
-the oracle at 32 and 40 samples.  On the GPU: every reachable row runs as itself, once as pt_megakernel and once as
-pt_megakernel_list, is held to the oracle, and all rows of a scene give the same accumulator bits."""
+the oracle at 32 and 40 samples.  On the GPU: every reachable row runs as itself, once as pt_megakernel<b, T, F> and once over a
+tile list as pt_megakernel<b, T, F, TileList>, is held to the oracle, and all rows of a scene give the same accumulator bits."""
 import ctypes as C
 import os
 
@@ -229,7 +229,7 @@ def test_every_row_of_a_scene_runs_as_itself(scene, oracle_mod, monkeypatch):
         assert IC.triple(st) == row, (env, IC.triple(st))
         same_l = float((got.view(np.uint32) == first32.view(np.uint32)).all(-1).mean())
         err_l = _linf(got, ref[SPP_LIST], SPP_LIST)
-        print(f"{IC.name_of(scene)} {row} pt_megakernel_list: k_split {st['k_split']}, lds_bytes {st['lds_bytes']}, L-inf {err_l:.2e}, "
+        print(f"{IC.name_of(scene)} {row} pt_megakernel over a tile list: k_split {st['k_split']}, lds_bytes {st['lds_bytes']}, L-inf {err_l:.2e}, "
               f"bit-identical {same_l:.2%}")
         assert (counts == SPP_LIST).all()
         _check(got, ref[SPP_LIST], SPP_LIST)
@@ -245,6 +245,6 @@ def test_census_closing_line():
     through both kernels, and so did the UNREACHABLE ones through the C ABI."""
     for shape, (err, same, n) in sorted(_RAN["worst"].items()):
         print(f"census shape {shape}: {n} rows run, worst L-inf {err:.2e}, lowest bit-identical share {same:.2%}")
-    print(f"census: {len(ROWS)} compiled, {len(_RAN['uniform'])} run as pt_megakernel, {len(_RAN['list'])} run as pt_megakernel_list, "
+    print(f"census: {len(ROWS)} compiled, {len(_RAN['uniform'])} run as pt_megakernel, {len(_RAN['list'])} run over a tile list, "
           f"{len(IC.UNREACHABLE)} unreachable by a scene description (run through the C ABI)")
     assert _RAN["uniform"] == _RAN["list"] == set(ROWS)
