@@ -1299,6 +1299,36 @@ MRT_HD Obj obj_of(const Scn &S, const Hit &h)
 }
 MRT_HD V3 to_object(const Obj &o, V3 hp) { return add(o.pos, xf_vec(o.X, o.ident, sub(hp, o.pos))); }
 
+// The same three for the shading of an F_IDENT kernel that decides a path's end before its scatter (render_pixel; IDENT = false:
+// the functions above).  Every instance is untransformed by construction, so the tag's identity bit is not decoded and no
+// per-instance transform address is formed: a vector whose product is not a nonzero finite number still takes the reference's
+// two mat-vecs, through ident_xf0 -- the ONE de-duplicated identity entry, instance 0's, which is the X0 of trace()'s scan, so
+// that scan and shading cannot disagree about a zero of either sign -- and that address is formed inside the fallback alone.
+MRT_HD const float *ident_xf0(const Scn &S) { return S.F + S.P->off_xf + (ldu(S.F + S.P->off_inst, INST_TAG) >> TAG_XF_SHIFT); }
+template <bool IDENT>
+MRT_HD Obj obj_of_t(const Scn &S, const Hit &h)
+{
+    if constexpr (!IDENT) return obj_of(S, h);
+    Obj o;
+    const float *I = S.F + S.P->off_inst + h.inst * INST_WORDS;
+    o.R = S.F + S.P->off_rend + (u32)h.rend * REND_WORDS;
+    o.IX = S.F + S.P->off_instx + h.inst * INSTX_WORDS;
+    o.X = nullptr;                                   // (not read: xf_obj)
+    o.pos = ld3(I, INST_POS);
+    o.ident = true;
+    o.kind = ldu(I, INST_TAG) & TAG_KIND_MASK;
+    return o;
+}
+template <bool IDENT>
+MRT_HD V3 xf_obj(const Scn &S, const Obj &o, V3 v)
+{
+    if constexpr (!IDENT) return xf_vec(o.X, o.ident, v);
+    if (nzfin3_product(v)) return v;
+    return xf_full(ident_xf0(S), v);
+}
+template <bool IDENT>
+MRT_HD V3 to_object_t(const Scn &S, const Obj &o, V3 hp) { return add(o.pos, xf_obj<IDENT>(S, o, sub(hp, o.pos))); }
+
 // ---- per-corner attributes (not in the reference; DESIGN.md section 14, in operation order) ----
 // Barycentric weights of the hit point p (object space, relative to the instance's position: n_hit - pos, as the sphere's
 // normal takes it) in the triangle v0, v0 + e1, v0 + e2: not clamped, f32, unfused;
@@ -1356,7 +1386,7 @@ MRT_HD void vattr_row(const Scn &S, const Obj &o, i32 tri_idx, u32 first4, float
 
 // Renderer::normal, src/rt.rs:776-793 with the Normal impls, src/rt.rs:414-466; triangles / meshes with corner normals: the
 // interpolated shading normal in the face normal's place (F_VATTR)
-template <u32 FEAT>
+template <u32 FEAT, bool IDENT = false>               // IDENT: see xf_obj
 MRT_HD V3 hit_normal(const Scn &S, const Obj &o, V3 n_hit, i32 tri_idx)
 {
     if (o.kind == KIND_PLANE) return ld3(o.IX, INSTX_PLANE_NW);          // norm(R*(L*n)) is per instance
@@ -1365,7 +1395,7 @@ MRT_HD V3 hit_normal(const Scn &S, const Obj &o, V3 n_hit, i32 tri_idx)
             const float *T = vattr_tri<FEAT>(S, o, tri_idx);
             float a[12];                                                 // words 0..11 of the row: vn in 0..8
             vattr_row<3>(S, o, tri_idx, 0u, a);
-            return norm(xf_vec(o.X, o.ident, vattr_normal(sub(n_hit, o.pos), ld3(T, 0), ld3(T, 3), ld3(T, 6), a + VATTR_VN)));
+            return norm(xf_obj<IDENT>(S, o, vattr_normal(sub(n_hit, o.pos), ld3(T, 0), ld3(T, 3), ld3(T, 6), a + VATTR_VN)));
         }
     }
     V3 n = v3(0.0f, 0.0f, 0.0f);
@@ -1377,7 +1407,7 @@ MRT_HD V3 hit_normal(const Scn &S, const Obj &o, V3 n_hit, i32 tri_idx)
         const float *T = ((FEAT & F_DEEP) ? S.G : S.F) + S.P->off_tri + (ldu(M, MESH_TRI0) + (u32)tri_idx) * TRI_WORDS;
         n = cross(ld3(T, 3), ld3(T, 6));
     }
-    return norm(xf_vec(o.X, o.ident, n));
+    return norm(xf_obj<IDENT>(S, o, n));
 }
 
 // Renderer::to_uv, src/rt.rs:795-809 with the UV impls, src/rt.rs:468-542.  Triangles and meshes: the reference hits todo!();
@@ -1494,11 +1524,13 @@ MRT_HD V3 pixel_focus(const Params &P, float cx, float cy)
 
 // the per-sample half of RayTracer::cast, src/rt.rs:916-931
 // lens position of a sample: the two draws of src/rt.rs:916-920
+MRT_HD V3 lens_at(const Params &P, float u1, float u2)           // u1, u2: the DIM_LENS_X and DIM_LENS_Z draws as unit floats
+{
+    return v3(P.cam_pos[0] + (u1 - 0.5f) * P.aprt, P.cam_pos[1], P.cam_pos[2] + (u2 - 0.5f) * P.aprt);
+}
 MRT_HD V3 lens_pos(const Params &P, u32 pk)
 {
-    const float u1 = u32_to_unit(draw_u32(pk, DIM_LENS_X));
-    const float u2 = u32_to_unit(draw_u32(pk, DIM_LENS_Z));
-    return v3(P.cam_pos[0] + (u1 - 0.5f) * P.aprt, P.cam_pos[1], P.cam_pos[2] + (u2 - 0.5f) * P.aprt);
+    return lens_at(P, u32_to_unit(draw_u32(pk, DIM_LENS_X)), u32_to_unit(draw_u32(pk, DIM_LENS_Z)));
 }
 
 MRT_HD void camera_ray(const Params &P, const float *camF, V3 focus, u32 pk, V3 &o, V3 &d)      // camF: cam_L, cam_R in the blob
@@ -1588,6 +1620,10 @@ struct LaneJob {
 // (mrt_radiance, mrt_rays.h): every sample of the lane starts on the ray (o, d) as given -- no shift of the origin, no
 // normalisation, no lens draws -- and `key` stands where the pixel index stands in the hash key; x and y are not read.
 struct CameraRays { static constexpr bool supplied = false; };
+// Kernels whose paths end independently of their scatter: no light loop and no emit / colour lookup at the recorded hit
+// (render_pixel decides the end first in these).  The plain sets 0-3, F_IDENT, F_IDENT | F_BOX, F_BVH, F_IDENT | F_BVH; not the
+// cold / deep / no-stash launch shapes, whose kernels park T and L in the lane stash or exist in the big feature sets only.
+constexpr bool end_before_scatter(u32 feat) { return (feat & ~(u32)(F_BOX | F_TRI | F_BVH | F_IDENT)) == 0u; }
 struct SuppliedRay {
     static constexpr bool supplied = true;
     V3 o, d;
@@ -1655,6 +1691,153 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
     // the same iteration, and the direction of the next ray -- scattered or fresh from the camera -- goes through ONE
     // shared normalisation at the bottom.  No lane ever waits for its neighbours' paths to end, and the divergent
     // regeneration block holds only two hashes and a few adds.
+    if constexpr (end_before_scatter(FEAT)) {
+    // Kernels without lights and maps (end_before_scatter): whether a path ends at a hit -- miss, emit coin, bounce cut -- does not
+    // depend on its scatter, so an iteration decides the end FIRST, lets the ended lanes do their bookkeeping, and then takes ONE
+    // pair of unit draws for every live lane: (pk, dbase + 1), (pk, dbase + 2) for a path that goes on, (new pk, DIM_LENS_X),
+    // (new pk, DIM_LENS_Z) for a regenerated one.  Same bits as the order below: a draw depends on (pk, dim) alone, the material
+    // is the hit renderer's whichever of hit.0 / hit.1 is recorded, and the T update and the cut read color, pwr and b only.
+    static_assert(!kTL && !kHit, "the 6-wave stash kernels carry lights and maps");
+    constexpr bool kId = (FEAT & F_IDENT) != 0;
+    // The scalars of the iteration's tail as values of their own: left in Params' 16-register kernel-argument tuple, a spilled
+    // tuple comes back whole -- 16 lane reads, vector instructions all -- for each of them
+    float q_pwr = P.q;
+    u32 bounce_max = P.bounce;
+    u32 k_split = P.k_split;
+    MRT_FORGET_SCALAR(q_pwr); MRT_FORGET_SCALAR(bounce_max); MRT_FORGET_SCALAR(k_split);
+    while (alive) {
+        MRT_PROBE(PH_ITER);
+        const RayPre ray = ray_pre<FEAT>(o, d);
+        Hit h;
+        ++seg;
+        V3 contrib = v3(0.0f, 0.0f, 0.0f);
+        bool ended = false;
+        MRT_TICK(3);                                                   // loop bottom -> here: ray set-up
+        const bool hit_any = trace<false, FEAT>(S, ray, h);
+        MRT_TICK(0);                                                   // the closest-hit query
+        // ---- 1. the path's end ----
+        const float *M = S.F + P.off_mat;
+        bool refr = false;
+        if (!hit_any) {
+            contrib = (b == 0) ? v3(P.sky[0], P.sky[1], P.sky[2]) : add(L_, hadam(T_, sky_init));    // src/rt.rs:957-959, :964
+            ended = true;
+        } else {
+            MRT_PROBE(PH_SHADE);
+            M += (u32)h.rend * MAT_WORDS;
+            refr = coin(fmin_(1.0f - M[MAT_OPACITY], 0.85f), pk, dim_of(b, SL_OPAC_COIN));
+            const V3 color = ld3(M, MAT_ALBEDO);
+            if (coin(M[MAT_EMIT], pk, dim_of(b, SL_EMIT_COIN))) {     // emit coin of the fold, src/rt.rs:966-970
+                MRT_PROBE(PH_EMIT_END);
+                contrib = add(L_, hadam(T_, color));
+                ended = true;
+            } else {
+                T_ = hadam(T_, muls(v3(0.5f + color.x, 0.5f + color.y, 0.5f + color.z), pwr));
+                pwr = pwr * q_pwr;                                        // Ray::cast, src/rt.rs:571
+                ++b;
+                if (b > bounce_max) {          // src/rt.rs:1018
+                    contrib = add(L_, hadam(T_, sky_init));
+                    ended = true;
+                }
+            }
+        }
+
+        MRT_TICK(1);                                                   // shading: the path's end
+        // ---- 2. ended lanes: the sample's sum, the chunk, the next sample's key ----
+        bool from_camera = false;
+        if (ended) {
+            csum = add(csum, contrib);
+            ++s;
+            if (s == f2u(st.get(ST_SEND))) {                        // chunk complete: flush its sum
+                u32 j = f2u(st.get(ST_CHUNK));
+                if (direct) {
+                    float *q = P.accum + f2u(st.get(ST_WORD));
+                    q[0] += csum.x; q[1] += csum.y; q[2] += csum.z;
+                } else {
+                    float *q = P.partial + ((size_t)j * P.partial_stride + f2u(st.get(ST_WORD)));
+                    q[0] = csum.x; q[1] = csum.y; q[2] = csum.z;
+                }
+                csum = v3(0.0f, 0.0f, 0.0f);
+                u32 e;
+                if (planes1) {                                      // (wave-uniform) the next sample, the next plane
+                    j += 1u;
+                    alive = s < s_stop;
+                    e = s + 1u;
+                } else {
+                    j += k_split;
+                    alive = j < n_chunks;
+                    s = (g0 + j) * kChunk;
+                    e = s_stop - s > kChunk ? s + kChunk : s_stop;   // (no wrap past 2^32, as above)
+                }
+                st.put(ST_CHUNK, u2f(j));
+                st.put(ST_SEND, u2f(e));
+            }
+            if (alive) {                                            // next sample: RayTracer::cast, src/rt.rs:916-922
+                MRT_PROBE(PH_REGEN);
+                pk = mix32(f2u(st.get(ST_PIXKEY)) + s * kGold);
+                T_ = v3(1.0f, 1.0f, 1.0f); L_ = v3(0.0f, 0.0f, 0.0f);
+                pwr = 1.0f; b = 0;
+                from_camera = true;
+            }
+        }
+        MRT_TICK(3);                                                   // regeneration: the ended lanes' bookkeeping
+        // ---- 3. one draw stage: the scatter's u1, u2 or the lens draws, slots that follow each other in both cases ----
+        // (a lane that scatters has passed ++b: its draws belong to bounce b - 1; the value is not read by the others)
+        u32 dbase = dim_of(b - 1u, refr ? SL_REFR_COIN : SL_REFL_COIN);      // coin, u1, u2 are consecutive slots
+        const u32 ddim = from_camera ? (u32)DIM_LENS_X : dbase + 1u;
+        float u1 = u32_to_unit(draw_u32(pk, ddim)), u2 = u32_to_unit(draw_u32(pk, ddim + 1u));
+        // ---- 4. the next ray's origin and un-normalised direction ----
+        V3 X = v3(0.0f, 1.0f, 0.0f);
+        V3 base = o;
+        if (from_camera) {
+            if constexpr (!Prim::supplied) {
+                base = lens_at(P, u1, u2);
+                X = sub(st_get3(st, ST_FOCUS), base);               // new_dir before .norm()
+            }
+        } else if (!ended) {
+            // Scatter.  The reference always builds the reflected ray at hit0 (src/rt.rs:1049) and replaces it by the
+            // refracted ray from the exit hit when the 15 % / opacity coin comes up and refraction is possible
+            // (src/rt.rs:1054-1058); a failed refraction (total internal reflection) takes a second pass as a reflection,
+            // with the SL_REFL_* draws of its own.
+            const Obj ob = obj_of_t<kId>(S, h);
+            const V3 p0 = add(o, muls(d, h.t0));                       // Vec3f::from(&hit.0.ray)
+            const V3 nh0 = to_object_t<kId>(S, ob, p0);
+            const float metal_c = M[MAT_METAL], opac = M[MAT_OPACITY];  // hit.obj.mat.metal (src/rt.rs:564)
+            V3 hp = p0, nhh = nh0;                                     // recorded hit point: hit.0, or hit.1 for a refracting lane
+            i32 ti = h.i0;
+            // the exit hit is formed only in a wavefront that holds a refracting lane (a quarter of the iterations on the
+            // Cornell box), and read only by those lanes
+            if (wave_any(refr)) {
+                const V3 p1 = add(o, muls(d, h.t1));
+                const V3 nh1 = to_object_t<kId>(S, ob, p1);
+                if (refr) { hp = p1; nhh = nh1; ti = h.i1; }
+            }
+            for (u32 pass = 0;; ++pass) {
+                if (pass == 0) { MRT_PROBE(PH_SCATTER1); } else { MRT_PROBE(PH_SCATTER2); }
+                if (refr) { MRT_PROBE(PH_REFRACT); }
+                if (ob.kind != KIND_PLANE) { MRT_PROBE(PH_NORMAL_NONPLANE); }
+                const V3 hn = hit_normal<FEAT, kId>(S, ob, nhh, ti);
+                float rough = M[MAT_ROUGH];                             // Ray::reflect / Ray::refract, src/rt.rs:559-589
+                if (metal_c == 0.0f && opac != 0.0f && draw_u32(pk, dbase) < kThr080) rough = 1.0f;
+                const V3 nn = rand_normal(hn, rough, u1, u2);
+                if (!refr) { X = reflect(d, nn); break; }              // .norm() of src/rt.rs:569 happens at the bottom
+                const float eta = 1.0f + 0.5f * M[MAT_GLASS];
+                if (refract(d, eta, nn, X)) break;                      // .norm() of src/rt.rs:586 happens at the bottom
+                refr = false;                                           // Vec3f::refract returned None: reflect at hit.0
+                hp = p0; nhh = nh0; ti = h.i0;
+                dbase = dim_of(b - 1u, SL_REFL_COIN);
+                u1 = u32_to_unit(draw_u32(pk, dbase + 1u)); u2 = u32_to_unit(draw_u32(pk, dbase + 2u));
+            }
+            base = hp;
+        }
+        MRT_TICK(1);                                                   // the draw stage and the scatter (lens position: a few adds)
+        // ---- 5. next ray: dir = X.norm(), orig = base + dir * E  (Ray::cast src/rt.rs:551-553; cast_default :555-557) ----
+        V3 nd = norm(X);
+        if (from_camera && !(P.cam_ident && nzfin3(nd))) nd = m3mul(S.F + P.off_cam + 9, m3mul(S.F + P.off_cam, nd));   // rot_y * (look * new_dir), src/rt.rs:930
+        o = add(base, muls(nd, kE));
+        d = nd;
+        if constexpr (Prim::supplied) { if (from_camera) { o = prim.o; d = prim.d; } }      // the supplied ray again, as given
+    }
+    } else
     while (alive) {
         MRT_PROBE(PH_ITER);
         // ---- RaytraceIterator::next ----
