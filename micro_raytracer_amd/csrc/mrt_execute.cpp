@@ -16,7 +16,12 @@ namespace {
 // Sample-split until the launch has ~25 rounds of 32 waves per CU: shorter wavefronts balance the tail of a launch (tiles
 // differ in path length).  Measured on the 1080p x 1024 spp Cornell box (tests/gpu_shard_probe.py): whole frame 328 -> 315 ms
 // with 4 lanes per pixel, one shard of 8 GPUs 47.1 -> 42.4 ms with 16; round 3, persistent 256-thread workgroups: 1 / 2 / 4 / 8
-// lanes per pixel 292.9 / 274.7 / 267.7 / 265.7 ms, hence 8 at 1080p (the target was 120 000 wavefronts: 4).
+// lanes per pixel 292.9 / 274.7 / 267.7 / 265.7 ms, hence a split of 8 at 1080p (the target was 120 000 wavefronts: 4).
+// The split says whether a launch goes through the chunk planes and is what mrt_stats reports.  The items of such a launch are
+// the split's interleaved chunk phases -- 8 chunks each at 1080p x 1024 samples -- only under MRT_K_SPLIT and in the kernels
+// that are no band kernels (mrt_inst.h); a band kernel's launch is cut into tapered bands of contiguous chunks instead
+// (plan_bands, mrt_plan.cpp: 31, 16, 8, 4, 2, 1, 1, 1 chunks there), which keeps the long items' fuller wavefronts and
+// drains the launch at single chunks: 190.8 -> 187.0 ms.
 constexpr unsigned long long kSplitTargetWaves = 200000ull;
 // A sample-split launch writes one f32x3 chunk sum per pixel per 16 samples; the buffer is bounded by cutting one
 // mrt_execute into several launches of at most this many sample chunks (1024 samples) and this many bytes.  Launch
@@ -133,6 +138,15 @@ int mrt::api::launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, floa
         while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { Event e; HIP_TRY(create(e)); c->evs.push_back(std::move(e)); }
         const Event *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
         c->P.persist_grid = (c->plan.small_plain_grid && stop - base < kChunk) ? 0u : c->persist_grid;
+        // Tapered items: a persistent launch through the chunk planes of a band kernel cuts its nc
+        // chunks into contiguous bands, longest first, instead of ks interleaved phases.  An explicit MRT_K_SPLIT keeps the phases.
+        c->P.band_items = 0u;
+        if (ks > 1u && !c->knobs.k_split && c->P.persist_grid && c->plan.block_threads > 64u
+            && band_kernel(c->plan.in_lds, (int)c->plan.block_threads, c->plan.inst)) {
+            const Bands b = plan_bands(nc, wave_tiles, (unsigned long long)c->persist_grid * (c->plan.block_threads / 64u), c->knobs);
+            c->P.band_items = b.items; c->P.n_bands = b.n; c->P.band_tail = b.tail;
+            for (u32 i = 0; i < kMaxBands; ++i) { c->P.band_first[i] = b.first[i]; c->P.band_len[i] = b.len[i]; }
+        }
         if ((rc = launch_trace(c, c->P, c->stream.get(), ev ? ev[0].get() : nullptr, ev ? ev[1].get() : nullptr, tl))) return rc;
         if (ks > 1u) {
             if (tl) HIP_TRY(launch_reduce_chunks_listed(c->d_accum, half, c->partial.p, tl->tiles, tl->n, c->pk.nw, c->pk.nh, plane, nc, c->stream.get()));
@@ -209,7 +223,7 @@ static int la_launch(mrt_ctx *c, int i, u32 base, u32 n)
     Lookahead &la = *c->la;
     if (plane * n > la.planes[i].n && !hip_tolerated(la.planes[i].alloc(plane * n))) return MRT_ERR_LIMIT;     // the caller falls back
     Params P = c->P;
-    P.n_samples = n; P.sample_base = base; P.k_split = 1u; P.to_planes = 1u;
+    P.n_samples = n; P.sample_base = base; P.k_split = 1u; P.to_planes = 1u; P.band_items = 0u;
     P.partial = la.planes[i].p; P.partial_stride = plane;
     P.count_segments = 0u;
     // small scenes: the plain grid (their persistent grid fills every wave slot of the chip and would keep the folds out until

@@ -51,6 +51,14 @@ constexpr bool lds_stash_for(bool scene_in_lds, int block_threads, u32 feat)
 #endif
 }
 
+// The kernels that understand tapered items (Params.band_items): the 256-thread
+// kernels with the scene and the lane stash in LDS whose paths end before their scatter (the Cornell box's family), with either
+// tile source.  Every other instantiation is launched with band_items == 0 and carries none of the code.
+constexpr bool band_kernel(bool scene_in_lds, int block_threads, u32 feat)
+{
+    return scene_in_lds && block_threads == 256 && end_before_scatter(feat) && lds_stash_for(scene_in_lds, block_threads, feat);
+}
+
 // LDS bytes per workgroup of a launch: staged scene + lane stash + the mesh kernels' walk areas
 inline size_t pt_lds_bytes(const Params &P, u32 block_threads, bool scene_in_lds, u32 features)
 {

@@ -168,11 +168,13 @@ hipError_t launch_pt(const Params &P, u32 block_threads, bool scene_in_lds, u32 
 {
     if (block_threads != P.tiles_x * P.tiles_y * 64u) return hipErrorInvalidConfiguration;
     const u32 tile_w = P.tiles_x * 8u, tile_h = P.tiles_y * 8u;
-    dim3 grid((P.nw + tile_w - 1) / tile_w, (P.local_rows + tile_h - 1) / tile_h, P.k_split);
+    const u32 items = P.band_items ? P.band_items : P.k_split;      // items per tile: bands (persistent band-kernel launches) or chunk phases
+    if (P.band_items && !(block_threads > 64u && P.persist_grid)) return hipErrorInvalidConfiguration;
+    dim3 grid((P.nw + tile_w - 1) / tile_w, (P.local_rows + tile_h - 1) / tile_h, items);
     if (TL) {                                // tile-list launch: one wavefront per listed tile, list entries packed along x
         if (!TL->n) return hipSuccess;
         const u32 per_wg = P.tiles_x * P.tiles_y;
-        grid = dim3((TL->n + per_wg - 1) / per_wg, 1, P.k_split);
+        grid = dim3((TL->n + per_wg - 1) / per_wg, 1, items);
     }
     if (block_threads > 64u && P.persist_grid) {
         const unsigned long long n_wg = (unsigned long long)grid.x * grid.y * grid.z;

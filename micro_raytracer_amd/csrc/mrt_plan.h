@@ -22,6 +22,8 @@ constexpr size_t kSmallScene = 6u * 1024u;          // <= this: launches of less
 //   MRT_AXIS_SCAN                                  set and atoi == 0 switches the axis scan of mrt_trace.h off
 //   MRT_K_SPLIT                                    atoi, values below 1 become 1: forced lanes per pixel
 //   MRT_MAX_CHUNKS                                 atoi > 0: chunks per launch
+//   MRT_BANDS                                      "48,8,4,2,1,1": forced band lengths of a tapered launch (plan_bands), non-increasing,
+//                                                  at most kMaxBands above 1; an invalid list is ignored
 //   MRT_PARTIAL_LIMIT_BYTES                        strtoull: budget of the chunk planes
 //   MRT_LOOKAHEAD                                  atoi <= 1 disables the look-ahead, else min(v, 64) samples per launch at most
 //   MRT_GPUS                                       atoi, used only when mrt_opts.n_devices == 0 (the Rust shim's knob)
@@ -35,8 +37,21 @@ struct Knobs {
     u32 walk_cap = kWalkCapDefault;
     bool axis_scan = true, lookahead_off = false;
     u32 lookahead_max = 0;                        // 0: the default
+    u32 n_bands = 0;                              // MRT_BANDS: entries of bands[] (0: unset) ...
+    u32 bands[64] = {};                           // ... and the lengths
     static Knobs from_env();
 };
+
+// The bands of one tapered launch of n_chunks sample chunks: the listed bands (longest first, each longer than one chunk), then
+// every remaining chunk as a band of its own.  items = n + (n_chunks - tail) bands in all, which cover chunks 0 .. n_chunks - 1
+// exactly once, in order, with non-increasing lengths.
+struct Bands {
+    u32 n = 0, first[kMaxBands] = {}, len[kMaxBands] = {};
+    u32 tail = 0;                                 // first chunk of the single-chunk bands
+    u32 items = 0;
+};
+// tiles: 8x8 wave tiles of the launch; slots: wavefronts resident on the device at once; the knobs' MRT_BANDS list overrides the rule
+Bands plan_bands(u32 n_chunks, unsigned long long tiles, unsigned long long slots, const Knobs &knobs);
 
 // What a context stages in LDS and the shape of its launches: the one record of plan_launch's outcome.
 struct Plan {

@@ -52,7 +52,10 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
 #ifdef MRT_PHASE_TIMING
     unsigned long long wave_ticks[4] = {0ull, 0ull, 0ull, 0ull};
 #endif
-    // one 8x8 tile of shard-local rows for this wavefront, lane k of the sample split
+    // The band kernels (mrt_inst.h): an item of a launch with Params.band_items is (band, tile) -- chunks [first, first + len) of
+    // the tile, from the band table or, behind the listed bands, one chunk -- and a lane traces its pixel's chunks of the band
+    constexpr bool kBands = band_kernel(SCENE_IN_LDS, BLOCK_THREADS, FEAT);
+    // one 8x8 tile of shard-local rows for this wavefront, lane k of the sample split (band kernels: item k of the tile)
     auto do_tile = [&](u32 tx, u32 ty, u32 k) {
         const u32 x = tx * 8u + (lane & 7u);
         const u32 ry = ty * 8u + (lane >> 3);
@@ -60,9 +63,37 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
         const u32 blk = ry / P.shard_rows;
         const u32 y = (blk * P.shard_count + P.shard_index) * P.shard_rows + (ry - blk * P.shard_rows);
         const bool active = x < P.nw && ry < P.local_rows && y < P.nh;
-        if (!active) return;
         u32 seg = 0;
         LaneJob job;
+        if constexpr (kBands) {
+            BandJobs jobs;
+            jobs.stride = P.k_split;
+            jobs.end = (P.sample_base + P.n_samples - 1u) / kChunk - P.sample_base / kChunk + 1u;      // the launch's chunks
+            if (P.band_items) {
+                const bool listed = k < P.n_bands;
+                const u32 len = listed ? P.band_len[k] : 1u;
+                k = listed ? P.band_first[k] : P.band_tail + (k - P.n_bands);
+                jobs.stride = 1u;
+                jobs.end = k + len;
+            }
+            if (!active) return;
+            job.k = k;
+            job.word = (ry * P.nw + x) * 3u;        // < 2^32: mrt_create limits a shard to 2^30 pixels
+            LdsStash<BLOCK_THREADS> st;
+            st.base = (lds_vfloat *)(reinterpret_cast<float *>(lds_blob + stash_base4) + threadIdx.x);
+#ifdef MRT_PHASE_TIMING
+            unsigned long long tk[4] = {0ull, 0ull, 0ull, 0ull};
+#else
+            unsigned long long *tk = nullptr;
+#endif
+            render_pixel<FEAT, LdsStash<BLOCK_THREADS>, CameraRays, BandJobs>(S, st, x, y, job, seg, tk, CameraRays(), jobs);
+#ifdef MRT_PHASE_TIMING
+            for (int i = 0; i < 4; ++i) wave_ticks[i] += tk[i];
+#endif
+            segments += seg;
+            return;
+        }
+        if (!active) return;
         job.k = k;
         job.word = (ry * P.nw + x) * 3u;        // < 2^32: mrt_create limits a shard to 2^30 pixels
         if constexpr (lds_stash_for(SCENE_IN_LDS, BLOCK_THREADS, FEAT)) {
@@ -90,7 +121,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS, waves_for(FEAT, BLOCK_THREADS))
     // A tile-list launch maps its tile index i -- counter-drawn or blockIdx-addressed -- to TL.tiles[i].
     const bool persist = BLOCK_THREADS > 64 && P.persist_grid != 0u;
     const u32 n_tx = (P.nw + 7u) >> 3, n_ty = (P.local_rows + 7u) >> 3;
-    const u32 per_k = tile_count(n_tx * n_ty, TL...), total = per_k * P.k_split;
+    const u32 per_k = tile_count(n_tx * n_ty, TL...), total = per_k * ((kBands && P.band_items) ? P.band_items : P.k_split);
     for (;;) {
         u32 tx = blockIdx.x * P.tiles_x + wave % P.tiles_x, ty = blockIdx.y * P.tiles_y + wave / P.tiles_x, k = blockIdx.z;
         if (persist) {

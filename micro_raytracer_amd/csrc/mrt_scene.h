@@ -151,6 +151,8 @@ enum : u32 { LK_POINT = 0, LK_DIR = 1 };
 
 // samples per chunk of the canonical accumulation order (mrt_trace.h render_pixel)
 constexpr u32 kChunk = 16;
+// listed bands of a tapered launch (Params.band_first / band_len); the chunks behind them are bands of one chunk each
+constexpr u32 kMaxBands = 8;
 
 struct Params {
     // frame / sampling
@@ -211,8 +213,16 @@ struct Params {
     u32 off_axis;            // the AXIS table (0: the scene has none)
     u32 axis_scan;           // 1: the plain F_IDENT kernel's closest-hit scan may take the axis body (pack_scene: the scene has an AXIS
                              // table; mrt_create clears it under MRT_AXIS_SCAN=0); wave-uniform, tested once per query
+    // Tapered items (mrt_plan.h plan_bands; kernels of mrt_inst.h band_kernel(), persistent sample-split launches only).  band_items == 0:
+    // the k_split interleaved items.  Otherwise the launch's chunks are cut into band_items contiguous bands -- the first n_bands
+    // as listed, every chunk behind them a band of its own -- and an item is (band, tile), drawn band by band.
+    u32 band_items;          // bands of this launch = items per tile
+    u32 n_bands;             // listed bands, <= kMaxBands
+    u32 band_first[kMaxBands], band_len[kMaxBands];      // local chunk index and length of a listed band
+    u32 band_pad_;           // (keeps the block a multiple of 8 bytes)
+    u32 band_tail;           // local chunk index behind the last listed band: band n_bands + i is chunk band_tail + i
 };
-static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, axis_scan) + 4 == sizeof(Params), "Params has no tail padding");
+static_assert(sizeof(Params) % 8 == 0 && offsetof(Params, band_tail) + 4 == sizeof(Params), "Params has no tail padding");
 
 // Scene features a kernel instantiation is compiled for; the host picks the smallest set that covers the
 // scene, so e.g. a Cornell box of planes and spheres carries no octree walker, texture fetch or shadow-ray code.

@@ -1630,13 +1630,25 @@ struct SuppliedRay {
     u32 key;
 };
 
+// Which chunks of a launch a lane owns (render_pixel's Jobs argument).  OwnedChunks: chunks job.k, job.k + k_split, ... of the
+// launch's n_chunks -- every caller but the band kernels (mrt_inst.h).  BandJobs: chunks job.k, job.k + stride, ... below end,
+// both wave-uniform: the interleaved items again (stride = k_split, end = n_chunks) or the contiguous chunks of one band of a
+// tapered launch (stride = 1, end = the band's end).  Same bookkeeping, same loop: only the two scalars of the
+// chunk-flush block differ.
+struct OwnedChunks { static constexpr bool banded = false; };
+struct BandJobs {
+    static constexpr bool banded = true;
+    u32 stride, end;
+};
+
 // All samples of one supersampled pixel: Sampler::execute's per-pixel body, n_samples times
 // (src/sampler.rs:45-70 calling RayTracer::iter / reduce_light, src/rt.rs:937-994, whose iterator
 // is RaytraceIterator::next, src/rt.rs:1014-1066).
-template <u32 FEAT, class Stash, class Prim = CameraRays>
+template <u32 FEAT, class Stash, class Prim = CameraRays, class Jobs = OwnedChunks>
 MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &job, u32 &segments, unsigned long long *ticks = nullptr,
-                         const Prim &prim = Prim())
+                         const Prim &prim = Prim(), const Jobs &jobs = Jobs())
 {
+    static_assert(!Jobs::banded || end_before_scatter(FEAT), "band kernels: mrt_inst.h band_kernel");
     MRT_TICK_DECL;
     const Params &P = *S.P;
     u32 pixel;
@@ -1666,6 +1678,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
         st.put(ST_SEND, u2f(e));
     }
     bool alive = planes1 ? job.k == 0u : job.k < n_chunks;
+    if constexpr (Jobs::banded) { if (!planes1) alive = job.k < jobs.end; }
     V3 csum = v3(0.0f, 0.0f, 0.0f);
     u32 pk = 0, b = 0;
     V3 o = v3(0, 0, 0), d = v3(0, 1, 0);
@@ -1703,7 +1716,8 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
     // tuple comes back whole -- 16 lane reads, vector instructions all -- for each of them
     float q_pwr = P.q;
     u32 bounce_max = P.bounce;
-    u32 k_split = P.k_split;
+    u32 k_split = P.k_split, chunks_end = n_chunks;
+    if constexpr (Jobs::banded) { k_split = jobs.stride; chunks_end = jobs.end; }
     MRT_FORGET_SCALAR(q_pwr); MRT_FORGET_SCALAR(bounce_max); MRT_FORGET_SCALAR(k_split);
     while (alive) {
         MRT_PROBE(PH_ITER);
@@ -1764,7 +1778,7 @@ MRT_HD void render_pixel(const Scn &S, Stash &st, u32 x, u32 y, const LaneJob &j
                     e = s + 1u;
                 } else {
                     j += k_split;
-                    alive = j < n_chunks;
+                    alive = j < chunks_end;
                     s = (g0 + j) * kChunk;
                     e = s_stop - s > kChunk ? s + kChunk : s_stop;   // (no wrap past 2^32, as above)
                 }
