@@ -335,6 +335,25 @@ int mrt_adapt_half(mrt_ctx *ctx, float *rgb);
  * Sharded and multi-device contexts return the whole frame too.  Not an observation: booked samples stay booked. */
 int mrt_aov(mrt_ctx *ctx, float *depth, float *normal, float *albedo, int32_t *renderer, int32_t *instance);
 
+/* The AOVs of a custom camera: one caller-supplied ray per supersampled pixel, orig and dir [nh][nw][3], in place
+ * of the camera's lens-centre ray -- the grid a caller renders through mrt_radiance and puts back with mrt_set_accum.  The call
+ * computes the planes at once and installs them as the context's AOVs: from then on mrt_aov and every filter guided by them
+ * (mrt_denoise, mrt_img_denoised, mrt_img_hdr with denoise) use them; mrt_reset and mrt_set_accum* keep them.  A ray is traced as
+ * given, by the rules of mrt_radiance: no shift of the origin, no normalisation (depth is the ray parameter t0, the world point
+ * orig + dir * t0), any float is legal.  A miss under an environment texture has the albedo E(dir) of the supplied direction.
+ *   MRT_AOV_RAYS_DEVICE   orig and dir are device pointers on the context's device
+ *   MRT_AOV_WRAP_X        the grid is periodic in x (a full 360-degree panorama); kept with the planes: while it is set every
+ *                         a-trous pass takes its horizontal taps at (x + s * dx) modulo nw, all 25 taps of a row inside the
+ *                         frame count, and the seam is filtered like any other column
+ * orig = dir = NULL with flags 0 drops the planes: the next use computes the camera's own again.  Pointers are borrowed for the
+ * duration of the call.  Not an observation: the accumulator, the counts, booked samples and the statistics stay as they are.
+ * MRT_ERR_ARG: a null context, exactly one of orig and dir NULL, an unknown flag, flags with NULL rays.  MRT_ERR_STATE: a
+ * multi-device context; and, while such planes are installed, MRT_DN_VARIANCE in the filters above -- the half buffer belongs to
+ * the camera's frame.  A row-sharded context takes the whole grid. */
+#define MRT_AOV_RAYS_DEVICE 1u
+#define MRT_AOV_WRAP_X 2u
+int mrt_aov_rays(mrt_ctx *ctx, const float *orig /*[nh][nw][3]*/, const float *dir /*[nh][nw][3]*/, uint32_t flags);
+
 /* Edge-avoiding a-trous filter (Dammertz et al. 2010) on the mean radiance, guided by the AOVs.  passes 0..8 (0: the means
  * unchanged); sigmas > 0 or +inf (+inf switches that term off); NaN or <= 0: MRT_ERR_ARG.  NULL options = the defaults.
  *

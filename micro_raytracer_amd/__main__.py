@@ -5,7 +5,7 @@
                                   [--denoise [--denoise-passes N] [--denoise-mode atrous|variance] [--denoise-sigma-var S]
                                    [--denoise-firefly F]] [--aov PREFIX]
                                   [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS] [--sky-filter nearest|bilinear]
-                                  [--tex-filter nearest|bilinear] [--camera pinhole|equirect [--pano-yaw TURNS]]
+                                  [--tex-filter nearest|bilinear] [--camera pinhole|equirect [--pano-yaw TURNS] [--pano-guides]]
                                   [--resize lanczos3|box]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
@@ -19,7 +19,9 @@ render, so --sample must be a multiple of 32.  --denoise-sigma-var and --denoise
 mapping and its rotation about +z; --sky-filter / --tex-filter choose the filter of the environment texture and of the material
 textures (nearest texel, or bilinear).
 --camera equirect renders the frame's supersampled grid as a full lat-long panorama from cam.pos through Sampler.radiance
-(cameras.render_equirect), turned by --pano-yaw; cam.dir, fov and aprt are ignored.
+(cameras.render_equirect), turned by --pano-yaw; cam.dir, fov and aprt are ignored.  --pano-guides also forms the first-hit AOVs
+on the panorama's own rays (Sampler.aov_rays, the filter wrapping across the seam); only with it do --denoise (mode atrous) and
+--aov go together with --camera equirect.
 -o out.hdr / out.pfm saves the linear float image (Sampler.img_hdr: the mean radiance at the output resolution, no tone map, no
 quantisation; with --denoise the filtered means) as a Radiance picture or a PFM; --resize chooses its filter, Lanczos3 with the
 taps of the 8-bit image or the box (area) average a light probe wants.  A panorama written with --camera equirect -o probe.hdr is
@@ -104,16 +106,25 @@ def main(argv=None):
                     help="equirect: the frame's supersampled grid as a 360 x 180 degree panorama from cam.pos; the description's "
                          "cam.dir, fov and aprt are ignored")
     ap.add_argument("--pano-yaw", type=float, metavar="TURNS", help="--camera equirect: the centre column looks along +y turned by TURNS")
+    ap.add_argument("--pano-guides", action="store_true",
+                    help="--camera equirect: first-hit AOVs on the panorama's rays, so that --denoise (atrous) and --aov apply to it")
     ap.add_argument("--resize", choices=sorted(_abi.RESIZE_FILTERS), help="filter of a .hdr / .pfm output's resize (default lanczos3)")
     a = ap.parse_args(argv)
     if a.resize is not None and not is_float_output(a.output):
         ap.error("--resize needs a .hdr or .pfm output: the 8-bit image is resized as the reference resizes it")
     if a.camera == "equirect":
-        for name, on in (("--adaptive", a.adaptive is not None), ("--denoise", a.denoise), ("--aov", a.aov is not None), ("--update", a.update)):
+        for name, on in (("--adaptive", a.adaptive is not None), ("--update", a.update)):
             if on:
                 ap.error(f"--camera equirect cannot be combined with {name}")
+        for name, on in (("--denoise", a.denoise), ("--aov", a.aov is not None)):
+            if on and not a.pano_guides:
+                ap.error(f"--camera equirect cannot be combined with {name} unless --pano-guides forms the AOVs on the panorama's rays")
+        if a.pano_guides and a.denoise and a.denoise_mode != "atrous":
+            ap.error("--pano-guides: --denoise-mode variance reads the half buffer of the camera's frame; use --denoise-mode atrous")
     elif a.pano_yaw is not None:
         ap.error("--pano-yaw needs --camera equirect")
+    elif a.pano_guides:
+        ap.error("--pano-guides needs --camera equirect")
     if not 0 <= a.denoise_passes <= 8:
         ap.error(f"--denoise-passes {a.denoise_passes} is not in 0..8")
     variance = a.denoise and a.denoise_mode == "variance"
@@ -155,7 +166,7 @@ def main(argv=None):
     s = Sampler(seed=a.seed)
     t0 = time.perf_counter()
     if a.camera == "equirect":
-        cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0)
+        cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0, guides=a.pano_guides)
     elif a.adaptive is not None:
         info = s.execute_adaptive(render, a.adaptive, min_samples=a.min_sample, max_samples=render.rt.sample, step=a.step)
         uniform = s.nw * s.nh * render.rt.sample

@@ -87,6 +87,8 @@ class Stats(C.Structure):
 
 
 RAYS_DEVICE = 1          # MRT_RAYS_DEVICE: the rays, keys and sums of mrt_radiance are device pointers
+AOV_RAYS_DEVICE = 1      # MRT_AOV_RAYS_DEVICE: the rays of mrt_aov_rays are device pointers
+AOV_WRAP_X = 2           # MRT_AOV_WRAP_X: their grid is periodic in x
 
 
 class Rays(C.Structure):

@@ -21,6 +21,7 @@ SYMBOLS = (
     "mrt_selftest_trace", "mrt_selftest_instantiations",
     "mrt_radiance", "mrt_camera_rays",
     "mrt_img_hdr", "mrt_save_image_f32",
+    "mrt_aov_rays",
 )
 
 
@@ -91,6 +92,7 @@ def lib():
     L.mrt_radiance.argtypes = [vp, C.POINTER(_abi.Rays), vp, C.POINTER(_abi.RaysInfo)]
     L.mrt_camera_rays.argtypes = [vp, f32p, f32p]
     L.mrt_selftest_instantiations.restype = u32
+    L.mrt_aov_rays.argtypes = [vp, vp, vp, u32]
     L.mrt_img_hdr.argtypes = [vp, C.POINTER(_abi.HdrOpts), f32p, C.POINTER(_abi.HdrInfo)]
     L.mrt_save_image_f32.argtypes = [C.c_char_p, f32p, u32, u32]
     _LIB = L

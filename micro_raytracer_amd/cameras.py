@@ -25,13 +25,17 @@ def equirect(pos, nw, nh, *, yaw=0.0, elevation=(-90.0, 90.0)):
     return o, d
 
 
-def render_equirect(sampler, render, n_samples=None, *, yaw=0.0, elevation=(-90.0, 90.0), info=None):
+def render_equirect(sampler, render, n_samples=None, *, yaw=0.0, elevation=(-90.0, 90.0), info=None, guides=False):
     """Render the supersampled grid of render's frame as a panorama from its camera position (cam.dir, fov and aprt play no
     part) and put the sums into the sampler's context as n_samples accumulated samples: img() / img_ss() / the writers follow.
+    guides: also install the first-hit AOVs of the same rays (Sampler.aov_rays), so that aov() and the denoisers belong to the
+    panorama and not to the pinhole camera; the grid spans the full azimuth, so the filter wraps its horizontal taps (wrap_x).
     Returns the sums, float32 [nh][nw][3]."""
     n = int(render.rt.sample if n_samples is None else n_samples)
     sampler.create(render)
     o, d = equirect(render.frame.cam.pos, sampler.nw, sampler.nh, yaw=yaw, elevation=elevation)
     rgb = sampler.radiance(render, o, d, n, info=info)
     sampler.set_accum(rgb, n)
+    if guides:
+        sampler.aov_rays(render, o, d, wrap_x=True)       # equirect() always spans the full turn
     return rgb

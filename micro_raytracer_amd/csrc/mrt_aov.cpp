@@ -1,4 +1,5 @@
-// mrt_aov.cpp — first-hit AOVs and the denoisers on them: mrt_aov, mrt_denoise, mrt_img_denoised.
+// mrt_aov.cpp — first-hit AOVs and the denoisers on them: mrt_aov, mrt_aov_rays, mrt_denoise,
+// mrt_img_denoised.
 #include <string.h>
 
 #include <utility>
@@ -94,6 +95,9 @@ int mrt::api::denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_inf
     if (d.mode == MRT_DN_VARIANCE && !c->adaptive)
         return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE needs the half buffer of an adaptive render on this context since its last reset or "
                     "mrt_set_accum; for a uniform budget of n samples call mrt_execute_adaptive with threshold 0 and min_samples = max_samples = n", fn);
+    if (d.mode == MRT_DN_VARIANCE && c->aov_ready && c->aov->from_rays)
+        return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE reads the adaptive half buffer, which belongs to the camera's frame, but the AOVs "
+                    "installed are those of caller-supplied rays; mrt_aov_rays(ctx, NULL, NULL, 0) returns to the camera's", fn);
     if ((rc = whole_frame(c, fn, "", S)) || (rc = aov_compute(c, cached, aov_ms))) return rc;
     Aov &a = *c->aov;
     const u32 nw = c->pk.nw, nh = c->pk.nh;
@@ -105,7 +109,7 @@ int mrt::api::denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_inf
     if (d.mode == MRT_DN_VARIANCE && d.passes != 0u)
         HIP_TRY(launch_denoise_var(S, c->ad->half.p, a.guide.p, a.albedo.p, nh, d.passes, d.sv, d.sn, d.sp, d.firefly, e0, e1, dst, c->stream.get(), env));
     else
-        HIP_TRY(launch_denoise(S, a.guide.p, a.albedo.p, nh, d.passes, d.sc, d.sn, d.sp, e0, e1, dst, c->stream.get(), env));
+        HIP_TRY(launch_denoise(S, a.guide.p, a.albedo.p, nh, d.passes, d.sc, d.sn, d.sp, e0, e1, dst, c->stream.get(), env, a.wrap_x));
     HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     float ms = 0.0f;
@@ -148,6 +152,54 @@ int mrt_aov(mrt_ctx *c, float *depth, float *normal, float *albedo, int32_t *ren
             if (instance) instance[p] = r < 0 ? -1 : ids[2 * p + 1] - (i32)a.inst_first[(u32)r];
         }
     }
+    ok();
+    return MRT_OK;
+}
+
+// The AOV pass on one caller-supplied ray per pixel; its planes stand where the camera's stood until (NULL, NULL, 0) drops them.
+// Not an observation: no enter(), nothing of the accumulator, of what was booked or traced ahead, or of the statistics is touched.
+int mrt_aov_rays(mrt_ctx *c, const float *orig, const float *dir, uint32_t flags)
+{
+    if (!c) return fail(MRT_ERR_ARG, "mrt_aov_rays: null context");
+    if (!orig != !dir) return fail(MRT_ERR_ARG, "mrt_aov_rays: orig and dir are both given, or both NULL");
+    if (flags & ~(uint32_t)(MRT_AOV_RAYS_DEVICE | MRT_AOV_WRAP_X)) return fail(MRT_ERR_ARG, "mrt_aov_rays: unknown flags 0x%x", flags);
+    if (!orig && flags) return fail(MRT_ERR_ARG, "mrt_aov_rays: flags 0x%x without rays", flags);
+    if (c->group) return fail(MRT_ERR_STATE, "mrt_aov_rays: multi-device context");
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    if (!orig) {                                  // back to the camera's own: the next use computes them
+        c->aov_ready = false;
+        if (c->aov) { c->aov->from_rays = false; c->aov->wrap_x = false; }
+        ok();
+        return MRT_OK;
+    }
+    const FlatScene fs = flat_scene(c);
+    if (!fs.blob) return g_status;
+    const Packed &ap = fs.pk;
+    if ((rc = aov_state(c))) return rc;
+    Aov &a = *c->aov;
+    const size_t words = (size_t)c->pk.nw * c->pk.nh * 3u;
+    DeviceMem<float> d_o, d_d;
+    const float *po = orig, *pd = dir;
+    if (!(flags & MRT_AOV_RAYS_DEVICE)) {
+        HIP_TRY(d_o.alloc(words));
+        HIP_TRY(d_d.alloc(words));
+        HIP_TRY(hipMemcpy(d_o.p, orig, words * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_d.p, dir, words * sizeof(float), hipMemcpyHostToDevice));
+        po = d_o.p; pd = d_d.p;
+    }
+    Params P = ap.P;
+    P.blob = fs.blob;
+    P.segments = a.seg.p;
+    // whatever fails from here on leaves no half-written planes behind as anybody's AOVs
+    c->aov_ready = false;
+    a.from_rays = false; a.wrap_x = false;
+    HIP_TRY(launch_aov_rays(P, ap.features, po, pd, a.guide.p, a.albedo.p, a.ids.p, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    a.inst_first = inst_first(ap);
+    a.from_rays = true;
+    a.wrap_x = (flags & MRT_AOV_WRAP_X) != 0u;
+    c->aov_ready = true;
     ok();
     return MRT_OK;
 }

@@ -119,7 +119,7 @@ struct Hdr {
     Event ev[2];
 };
 // first-hit AOVs and the denoiser (mrt_aov, mrt_denoise: DESIGN.md §13), on the context's device; the AOVs depend on scene and
-// camera only and survive mrt_reset
+// camera only (or on the rays mrt_aov_rays was given) and survive mrt_reset
 struct Aov {
     DeviceMem<float> guide;                       // [2][nh][nw] float4: (normal, depth), (world point, hit flag)
     DeviceMem<float> albedo;                      // [nh][nw][3]
@@ -127,6 +127,8 @@ struct Aov {
     DeviceMem<unsigned long long> seg;            // the AOV kernel's diagnostic counters (mrt_trace.h count_fallback)
     Event ev[2];                                  // around the AOV pass, then around the filter
     std::vector<u32> inst_first;                  // flat index of each renderer's first instance (ids -> mrt_scene order)
+    bool from_rays = false;                       // the planes are those of caller-supplied rays (mrt_aov_rays), not the camera's
+    bool wrap_x = false;                          // ... of a grid periodic in x (MRT_AOV_WRAP_X): the a-trous passes wrap their horizontal taps
     DeviceMem<float> dn;                          // two e planes ([nh][nw] float4) and the filtered means [nh][nw][3]: the first mrt_denoise
 };
 // in-process multi-device context (mrt_opts.n_devices > 1): one sharded sub-context per device, gathered on device 0

@@ -9,6 +9,7 @@
 //     w = 0 if hit_p != hit_q, else ((k5[dx] * k5[dy] * wc) * wn) * wp  (dn_tap_weight)
 //     num += w * e_q, den += w for taps with w > 0;  e'_p = den > 0 ? num / den : e_p
 //   c'_p = e'_p * D_p
+// On a frame periodic in x (MRT_AOV_WRAP_X) q.x = (p.x + s * dx) mod nw: all five columns of a row count.
 #pragma once
 #include "mrt_trace.h"
 
@@ -29,12 +30,12 @@ struct AovPixel {
     i32 inst;      // flat instance index of the packed scene, -1: miss
 };
 
+// ... of one ray (o, d), traced as given: the body both ray sources share -- the camera's lens-centre ray (aov_pixel) and a
+// caller-supplied one (mrt_aov_rays); t is the ray parameter, the world point o + d * t0 unfused
 template <u32 FEAT>
-MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
+MRT_HD AovPixel aov_ray(const Scn &S, const V3 &o, const V3 &d)
 {
     const Params &P = *S.P;
-    V3 o, d;
-    camera_ray_centre(P, S.F + P.off_cam, pixel_focus(P, (float)x, (float)y), o, d);
     Hit h;
     AovPixel a;
     if (!trace<false, FEAT>(S, ray_pre<FEAT>(o, d), h)) {
@@ -54,6 +55,15 @@ MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
     a.albedo = surf_color<FEAT>(S, surf_of<FEAT>(S, h, ob, nh0, h.i0));
     a.rend = h.rend; a.inst = (i32)h.inst;
     return a;
+}
+
+template <u32 FEAT>
+MRT_HD AovPixel aov_pixel(const Scn &S, u32 x, u32 y)
+{
+    const Params &P = *S.P;
+    V3 o, d;
+    camera_ray_centre(P, S.F + P.off_cam, pixel_focus(P, (float)x, (float)y), o, d);
+    return aov_ray<FEAT>(S, o, d);
 }
 
 // B3 spline taps, k5[dx + 2]
@@ -97,8 +107,12 @@ struct DnAcc {
 // The color term's 1/sigma^2 of pass i: sc * 4^i
 MRT_HD float dn_pass_sc(float sc, u32 i) { return sc * (float)(1u << (2u * i)); }
 
+// frame x of a horizontal tap on a frame periodic in x: x mod nw, a true modulo (a tap may wrap several times when 2 * step >= nw)
+MRT_HD long long dn_wrap(long long x, u32 nw) { const long long m = x % (long long)nw; return m < 0 ? m + (long long)nw : m; }
+
 // One whole pass over an nw x nh frame of e (3 floats per pixel) on the host (x86 build): out = e' of every pixel
-inline void dn_pass_host(const float *e, const DnGuide *g, u32 nw, u32 nh, u32 step, float sc, float sn, float sp, float *out)
+// wrap_x (MRT_AOV_WRAP_X): the frame is periodic in x, a horizontal tap is taken at (x + step * dx) mod nw
+inline void dn_pass_host(const float *e, const DnGuide *g, u32 nw, u32 nh, u32 step, float sc, float sn, float sp, float *out, bool wrap_x = false)
 {
     for (u32 y = 0; y < nh; ++y)
         for (u32 x = 0; x < nw; ++x) {
@@ -106,7 +120,9 @@ inline void dn_pass_host(const float *e, const DnGuide *g, u32 nw, u32 nh, u32 s
             DnAcc acc;
             for (int dy = -2; dy <= 2; ++dy)
                 for (int dx = -2; dx <= 2; ++dx) {
-                    const long long qx = (long long)x + (long long)step * dx, qy = (long long)y + (long long)step * dy;
+                    long long qx = (long long)x + (long long)step * dx;
+                    const long long qy = (long long)y + (long long)step * dy;
+                    if (wrap_x) qx = dn_wrap(qx, nw);
                     if (qx < 0 || qy < 0 || qx >= (long long)nw || qy >= (long long)nh) continue;
                     const size_t q = (size_t)qy * nw + (size_t)qx;
                     acc.add(dn_tap_weight(dn_k5(dx) * dn_k5(dy), e + 3 * p, e + 3 * q, g[p], g[q], sc, sn, sp), e + 3 * q);

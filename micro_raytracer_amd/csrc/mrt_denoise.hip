@@ -3,10 +3,12 @@
 //
 //   aov_first_hit   one lens-centre camera ray per supersampled pixel, scene read through L2 (the feature sets of the L2
 //                   path-tracing shape): guide (normal, depth, world point, hit flag), albedo, renderer and flat instance index
+//   aov_rays        the same pass on one caller-supplied ray per pixel (mrt_aov_rays)
 //   dn_mean         passes = 0: the mean c = A * rc, unchanged
 //   dn_pass         one a-trous pass at step s = 2^i over one residue class (x mod s, y mod s) of the frame -- a dense 5x5
 //                   stencil on that sub-image -- a 16x16 block per 256-thread workgroup with its 2-entry halo in LDS;
-//                   pass 0 demodulates the accumulator on load, the last pass remodulates into the output
+//                   pass 0 demodulates the accumulator on load, the last pass remodulates into the output; WRAP: the frame is
+//                   periodic in x, a halo entry left or right of the frame is loaded from its frame x modulo nw
 //
 // Build: as mrt_kernels.hip.
 #include <hip/hip_runtime.h>
@@ -28,6 +30,25 @@ __global__ void __launch_bounds__(256) aov_first_hit(const Params P, float4 *__r
     S.wk = nullptr; S.wk_stride = 256u;          // the L2 shape has no walk area (has_walk_area: F_COLD kernels only)
     const AovPixel a = aov_pixel<FEAT>(S, x, y);
     const size_t p = (size_t)y * P.nw + x, np = (size_t)P.nw * P.nh;
+    guide[p] = make_float4(a.g.nx, a.g.ny, a.g.nz, a.g.t);
+    guide[np + p] = make_float4(a.g.px, a.g.py, a.g.pz, a.g.hit);
+    albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
+    ids[2 * p] = a.rend; ids[2 * p + 1] = a.inst;
+}
+
+// aov_first_hit on the ray that orig / dir [nh][nw][3] hold for the pixel, traced as given: the same scene, the same planes
+template <u32 FEAT>
+__global__ void __launch_bounds__(256) aov_rays(const Params P, const float *__restrict__ orig, const float *__restrict__ dir,
+                                                float4 *__restrict__ guide, float *__restrict__ albedo, i32 *__restrict__ ids)
+{
+    const u32 x = blockIdx.x * 16u + (threadIdx.x & 15u), y = blockIdx.y * 16u + (threadIdx.x >> 4);
+    if (x >= P.nw || y >= P.nh) return;
+    Scn S;
+    S.F = reinterpret_cast<const float *>(P.blob);
+    S.U = S.F; S.G = S.F; S.P = &P;
+    S.wk = nullptr; S.wk_stride = 256u;          // no walk area, as above
+    const size_t p = (size_t)y * P.nw + x, np = (size_t)P.nw * P.nh;
+    const AovPixel a = aov_ray<FEAT>(S, v3(orig[3 * p], orig[3 * p + 1], orig[3 * p + 2]), v3(dir[3 * p], dir[3 * p + 1], dir[3 * p + 2]));
     guide[p] = make_float4(a.g.nx, a.g.ny, a.g.nz, a.g.t);
     guide[np + p] = make_float4(a.g.px, a.g.py, a.g.pz, a.g.hit);
     albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
@@ -62,7 +83,9 @@ constexpr u32 kDnB = 16, kDnT = kDnB + 4;   // output block, LDS tile with the 2
 
 // ENV: the kernel of contexts with an environment texture, whose miss pixels are demodulated by their backdrop
 // E(d) too (mrt_denoise.h dn_demod)
-template <bool ENV>
+// WRAP: the kernel of frames periodic in x (MRT_AOV_WRAP_X).  Only the tile load differs: it is the frame x of the
+// tap, rx + s * si, that is reduced modulo nw -- a wrapped tap generally lands in another residue class (nw % s != 0)
+template <bool ENV, bool WRAP>
 __global__ void __launch_bounds__(256) dn_pass(const DnPassArgs A)
 {
     __shared__ float4 s_e[kDnT * kDnT];
@@ -77,9 +100,15 @@ __global__ void __launch_bounds__(256) dn_pass(const DnPassArgs A)
     for (u32 t = threadIdx.x; t < kDnT * kDnT; t += 256u) {
         const u32 lj = t / kDnT, li = t - lj * kDnT;
         const long long si = (long long)(bx * kDnB + li) - 2, sj = (long long)(by * kDnB + lj) - 2;
-        const long long fx = (long long)rx + (long long)s * si, fy = (long long)ry + (long long)s * sj;
+        long long fx = (long long)rx + (long long)s * si;
+        const long long fy = (long long)ry + (long long)s * sj;
+        bool in_x = si >= 0 && fx < (long long)A.nw;
+        if constexpr (WRAP) {
+            if (!in_x) fx = dn_wrap(fx, A.nw);
+            in_x = true;
+        }
         float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g0 = e, g1 = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        if (si >= 0 && sj >= 0 && fx < (long long)A.nw && fy < (long long)A.nh) {
+        if (in_x && sj >= 0 && fy < (long long)A.nh) {
             const size_t p = (size_t)fy * A.nw + (size_t)fx;
             g0 = A.guide[p];
             g1 = A.guide[np + p];
@@ -134,8 +163,19 @@ hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo
     return hipGetLastError();
 }
 
+hipError_t launch_aov_rays(const Params &P, u32 features, const float *orig, const float *dir, float *guide, float *albedo, i32 *ids, hipStream_t stream)
+{
+    const u32 inst = pt_instantiation(256u, false, features);       // the L2 shape
+    const dim3 grid((P.nw + 15u) / 16u, (P.nh + 15u) / 16u);
+    float4 *g = reinterpret_cast<float4 *>(guide);
+#define MRT_CASE_L2(F) case (F): hipLaunchKernelGGL((aov_rays<(F)>), grid, dim3(256), 0, stream, P, orig, dir, g, albedo, ids); break;
+    switch (inst) { MRT_SHAPES_L2 default: return hipErrorInvalidConfiguration; }
+#undef MRT_CASE_L2
+    return hipGetLastError();
+}
+
 hipError_t launch_denoise(const MeanSrc &S, const float *guide, const float *albedo, u32 nh, u32 passes,
-                          float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env)
+                          float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env, bool wrap_x)
 {
     const u32 nw = S.nw;
     if (passes == 0u) {
@@ -157,8 +197,13 @@ hipError_t launch_denoise(const MeanSrc &S, const float *guide, const float *alb
         // sub-images of a class are at most ceil(n / s) wide / high
         const u32 sw = (nw + A.step - 1u) / A.step, sh = (nh + A.step - 1u) / A.step;
         const dim3 grid(A.cx * ((sw + kDnB - 1u) / kDnB), A.cy * ((sh + kDnB - 1u) / kDnB));
-        if (env) hipLaunchKernelGGL(dn_pass<true>, grid, dim3(256), 0, stream, A);
-        else hipLaunchKernelGGL(dn_pass<false>, grid, dim3(256), 0, stream, A);
+        if (wrap_x) {
+            if (env) hipLaunchKernelGGL((dn_pass<true, true>), grid, dim3(256), 0, stream, A);
+            else hipLaunchKernelGGL((dn_pass<false, true>), grid, dim3(256), 0, stream, A);
+        } else {
+            if (env) hipLaunchKernelGGL((dn_pass<true, false>), grid, dim3(256), 0, stream, A);
+            else hipLaunchKernelGGL((dn_pass<false, false>), grid, dim3(256), 0, stream, A);
+        }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

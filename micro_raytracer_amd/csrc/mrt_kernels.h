@@ -28,8 +28,11 @@ hipError_t launch_adapt_eval(const float *accum, const float *half, const u32 *l
                              u32 *keep, u32 *tile_count, u32 *tile_conv, u32 *list_out, u32 *n_out, hipStream_t stream);
 // mrt_denoise.hip: first-hit AOVs (guide [2][nh][nw] float4, albedo [nh][nw][3], ids [nh][nw][2]) and the a-trous passes
 hipError_t launch_aov(const Params &P, u32 features, float *guide, float *albedo, i32 *ids, hipStream_t stream);
+// ... the same planes of caller-supplied rays (orig, dir: [nh][nw][3] on the device; mrt_aov_rays)
+hipError_t launch_aov_rays(const Params &P, u32 features, const float *orig, const float *dir, float *guide, float *albedo, i32 *ids, hipStream_t stream);
 hipError_t launch_denoise(const MeanSrc &S, const float *guide, const float *albedo, u32 nh, u32 passes,
-                          float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env = false);   // env: the context has an environment texture
+                          float sc, float sn, float sp, float *e0, float *e1, float *out, hipStream_t stream, bool env = false,    // env: the context has an environment texture
+                          bool wrap_x = false);                                                                                    // wrap_x: the frame is periodic in x
 // mrt_denoise_var.hip: the variance-guided mode, passes >= 1; half: the adaptive half buffer, S.tile_count not null
 hipError_t launch_denoise_var(const MeanSrc &S, const float *half, const float *guide, const float *albedo, u32 nh, u32 passes,
                               float sv, float sn, float sp, float firefly, float *e0, float *e1, float *out, hipStream_t stream, bool env);

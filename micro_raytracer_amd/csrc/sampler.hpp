@@ -89,6 +89,9 @@ public:
         return out;
     }
 
+    // first-hit AOVs of a custom camera's rays, orig / dir [nh][nw][3] (mrt_aov_rays; flags MRT_AOV_*; nullptr, nullptr, 0: the camera's again)
+    void aov_rays(const float *orig, const float *dir, uint32_t flags = 0) { if (!ctx_ || mrt_aov_rays(ctx_, orig, dir, flags) != MRT_OK) throw std::runtime_error(ctx_ ? mrt_last_error() : "aov_rays before execute"); }
+
     mrt_stats stats() const
     {
         mrt_stats st{};

@@ -213,7 +213,7 @@ class Sampler:
     def aov(self) -> dict:
         """First-hit AOVs of the supersampled frame (mrt_aov): depth f32 [nh][nw] (inf: miss), normal and albedo f32
         [nh][nw][3], renderer and instance int32 [nh][nw] (indices into the scene's renderers and that renderer's instances,
-        -1: miss).  Computed once per context and kept."""
+        -1: miss).  Computed once per context and kept; after aov_rays() the planes of those rays."""
         self._need()
         out = {"depth": np.empty((self.nh, self.nw), np.float32), "normal": np.empty((self.nh, self.nw, 3), np.float32),
                "albedo": np.empty((self.nh, self.nw, 3), np.float32), "renderer": np.empty((self.nh, self.nw), np.int32),
@@ -223,6 +223,39 @@ class Sampler:
                                       out["albedo"].ctypes.data_as(fp), out["renderer"].ctypes.data_as(ip),
                                       out["instance"].ctypes.data_as(ip)))
         return out
+
+    def aov_rays(self, render: Render, orig, dir, *, wrap_x: bool = False):
+        """Install the first-hit AOVs of a custom camera (mrt_aov_rays): orig and dir of shape [nh][nw][3], one
+        ray per supersampled pixel, traced as given.  From then on aov(), denoise(), img_denoised() and img_hdr(denoise=...) use
+        these planes; reset() and set_accum() keep them.  wrap_x: the grid is periodic in x (a full 360-degree panorama), the
+        filter takes its horizontal taps modulo the width.  Numpy arrays go through the host, torch tensors on the context's
+        device are read in place.  aov_rays(render, None, None) returns to the camera's own AOVs.  Nothing else of the context
+        changes."""
+        self._ensure(render)
+        L = _lib.lib()
+        if orig is None and dir is None:
+            if wrap_x:
+                raise ValueError("aov_rays: wrap_x without rays")
+            _lib.check(L.mrt_aov_rays(self._ctx, None, None, 0))
+            return
+        if orig is None or dir is None:
+            raise ValueError("aov_rays: orig and dir are both given, or both None")
+        shape = (self.nh, self.nw, 3)
+        flags = _abi.AOV_WRAP_X if wrap_x else 0
+        if type(orig).__module__.split(".")[0] == "torch":
+            import torch
+            if not (orig.is_cuda and getattr(dir, "is_cuda", False)):
+                raise ValueError("aov_rays: orig and dir are both tensors on the context's device, or both host arrays")
+            if tuple(orig.shape) != shape or tuple(dir.shape) != shape:
+                raise ValueError(f"aov_rays: orig and dir are {shape}, got {tuple(orig.shape)} and {tuple(dir.shape)}")
+            o, d = orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous()
+            torch.cuda.synchronize(o.device)          # the library launches on a stream of its own
+            _lib.check(L.mrt_aov_rays(self._ctx, o.data_ptr(), d.data_ptr(), flags | _abi.AOV_RAYS_DEVICE))
+        else:
+            o, d = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
+            if o.shape != shape or d.shape != shape:
+                raise ValueError(f"aov_rays: orig and dir are {shape}, got {o.shape} and {d.shape}")
+            _lib.check(L.mrt_aov_rays(self._ctx, o.ctypes.data, d.ctypes.data, flags))
 
     def denoise(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None, mode="atrous",
                 sigma_var=None, firefly=None) -> np.ndarray:
