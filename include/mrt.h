@@ -348,8 +348,9 @@ int mrt_aov(mrt_ctx *ctx, float *depth, float *normal, float *albedo, int32_t *r
  * orig = dir = NULL with flags 0 drops the planes: the next use computes the camera's own again.  Pointers are borrowed for the
  * duration of the call.  Not an observation: the accumulator, the counts, booked samples and the statistics stay as they are.
  * MRT_ERR_ARG: a null context, exactly one of orig and dir NULL, an unknown flag, flags with NULL rays.  MRT_ERR_STATE: a
- * multi-device context; and, while such planes are installed, MRT_DN_VARIANCE in the filters above -- the half buffer belongs to
- * the camera's frame.  A row-sharded context takes the whole grid. */
+ * multi-device context; and, while such planes are installed, MRT_DN_VARIANCE in the filters above after mrt_execute_adaptive --
+ * that half buffer belongs to the camera's frame.  The half buffer of mrt_radiance_adaptive (below) belongs to its rays: after
+ * that call the mode serves with these planes, and only with them.  A row-sharded context takes the whole grid. */
 #define MRT_AOV_RAYS_DEVICE 1u
 #define MRT_AOV_WRAP_X 2u
 int mrt_aov_rays(mrt_ctx *ctx, const float *orig /*[nh][nw][3]*/, const float *dir /*[nh][nw][3]*/, uint32_t flags);
@@ -510,6 +511,32 @@ int mrt_radiance(mrt_ctx *ctx, const mrt_rays *r, float *rgb /*[n][3]*/, mrt_ray
 /* The lens-centre camera ray of every supersampled pixel, row-major: the ray of the depth AOV and, when aprt == 0, of every sample
  * of the pixel.  Either output may be NULL.  Host pointers.  MRT_ERR_STATE: a multi-device context. */
 int mrt_camera_rays(mrt_ctx *ctx, float *orig /*[nh][nw][3]*/, float *dir /*[nh][nw][3]*/);
+
+/* ---- adaptive sampling on caller-supplied rays: mrt_execute_adaptive for custom cameras ----
+ * One ray per supersampled pixel of the context's [nh][nw] grid, traced as given by the rules of mrt_radiance.  Pixel
+ * p = y * nw + x is ray p with hash key p; there is no key array.  Rounds, evaluation points, the stop rule, the rules of
+ * mrt_adapt with their MRT_ERR_ARGs, and mrt_adapt_info are those of mrt_execute_adaptive.  The accumulator of a tile that
+ * stopped at n holds the bytes mrt_radiance (sample_base 0, n_samples n, key NULL) gives for its rays; the half buffer holds the
+ * chunk sums of the even rounds, added in chunk order to 0.  With the rays of mrt_camera_rays on a scene with aprt == 0,
+ * accumulator, half buffer, counts and info (apart from times) equal those of mrt_execute_adaptive on a fresh context of the
+ * same seed, bit for bit.
+ * Preconditions as mrt_execute_adaptive: a context that holds no samples and has none booked; sharded and multi-device contexts:
+ * MRT_ERR_STATE.  MRT_ERR_ARG: a null ctx, r, orig or dir, a broken rule, a flag other than MRT_RAYS_DEVICE (orig and dir are
+ * device pointers on the context's device), a non-zero reserved word.  A refused call changes nothing; a call that fails half
+ * way leaves an empty uniform context.  Runs eagerly; pointers are borrowed for the call.
+ * Afterwards the context is in the adaptive state exactly as after mrt_execute_adaptive (mrt_img*, mrt_img_hdr, mrt_accum,
+ * mrt_sample_counts, mrt_adapt_half, mrt_denoise, mrt_get_stats serve it; mrt_execute refuses until mrt_reset or mrt_set_accum*),
+ * and it remembers that the half buffer belongs to a supplied grid: MRT_DN_VARIANCE then serves only while AOVs of mrt_aov_rays
+ * are installed (MRT_ERR_STATE with the camera's own or none).  The library cannot verify that mrt_aov_rays and this call were
+ * given the same rays: that is the caller's responsibility, as the frame handed to mrt_set_accum is. */
+typedef struct mrt_rays_adapt {
+    const float *orig;         /* [nh][nw][3] */
+    const float *dir;          /* [nh][nw][3] */
+    mrt_adapt    rule;
+    uint32_t     flags;        /* MRT_RAYS_DEVICE or 0 */
+    uint32_t     reserved[3];  /* 0 */
+} mrt_rays_adapt;
+int mrt_radiance_adaptive(mrt_ctx *ctx, const mrt_rays_adapt *r, mrt_adapt_info *info /*may be NULL*/, double *seconds /*may be NULL*/);
 
 /* ---- linear float image at the output resolution (not in the reference) ----
  * mrt_img tone-maps, truncates to u8 and only then resizes, as the reference does; mrt_img_hdr resamples the mean radiance itself,

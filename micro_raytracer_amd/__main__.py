@@ -5,7 +5,8 @@
                                   [--denoise [--denoise-passes N] [--denoise-mode atrous|variance] [--denoise-sigma-var S]
                                    [--denoise-firefly F]] [--aov PREFIX]
                                   [--sky-tex FILE] [--sky-map sphere|latlong] [--sky-rot TURNS] [--sky-filter nearest|bilinear]
-                                  [--tex-filter nearest|bilinear] [--camera pinhole|equirect [--pano-yaw TURNS] [--pano-guides]]
+                                  [--tex-filter nearest|bilinear]
+                                  [--camera pinhole|equirect [--pano-yaw TURNS] [--pano-guides] [--pano-adaptive THRESHOLD]]
                                   [--resize lanczos3|box]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
@@ -21,7 +22,10 @@ textures (nearest texel, or bilinear).
 --camera equirect renders the frame's supersampled grid as a full lat-long panorama from cam.pos through Sampler.radiance
 (cameras.render_equirect), turned by --pano-yaw; cam.dir, fov and aprt are ignored.  --pano-guides also forms the first-hit AOVs
 on the panorama's own rays (Sampler.aov_rays, the filter wrapping across the seam); only with it do --denoise (mode atrous) and
---aov go together with --camera equirect.
+--aov go together with --camera equirect.  --pano-adaptive THRESHOLD samples the panorama tile-adaptively on its own rays
+(Sampler.radiance_adaptive) with --min-sample, --step and --sample as the cap, and prints the adaptive: line; it leaves the half
+buffer of the panorama's grid behind, so with --pano-guides it makes --denoise --denoise-mode variance legal (--pano-adaptive 0 is
+the uniform budget with a half buffer).  Variance mode takes no horizontal taps across the seam.
 -o out.hdr / out.pfm saves the linear float image (Sampler.img_hdr: the mean radiance at the output resolution, no tone map, no
 quantisation; with --denoise the filtered means) as a Radiance picture or a PFM; --resize chooses its filter, Lanczos3 with the
 taps of the 8-bit image or the box (area) average a light probe wants.  A panorama written with --camera equirect -o probe.hdr is
@@ -75,6 +79,11 @@ def save_aov(s, prefix):
         _lib.save_image(f"{prefix}.{name}.png", np.ascontiguousarray(img))
 
 
+def adaptive_line(info, uniform):
+    return (f"adaptive: {info['samples']} samples traced of {uniform} uniform ({info['samples'] / uniform:.1%}), "
+            f"{info['tiles_converged']} of {info['tiles']} tiles converged, per-pixel counts {info['min_count']}..{info['max_count']}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m micro_raytracer_amd")
     ap.add_argument("full", help="full render description (JSON, the reference's schema)")
@@ -108,21 +117,33 @@ def main(argv=None):
     ap.add_argument("--pano-yaw", type=float, metavar="TURNS", help="--camera equirect: the centre column looks along +y turned by TURNS")
     ap.add_argument("--pano-guides", action="store_true",
                     help="--camera equirect: first-hit AOVs on the panorama's rays, so that --denoise (atrous) and --aov apply to it")
+    ap.add_argument("--pano-adaptive", type=float, metavar="THRESHOLD",
+                    help="--camera equirect: tile-adaptive sampling on the panorama's rays (--min-sample, --step, --sample as the cap); "
+                         "with --pano-guides it allows --denoise-mode variance")
     ap.add_argument("--resize", choices=sorted(_abi.RESIZE_FILTERS), help="filter of a .hdr / .pfm output's resize (default lanczos3)")
     a = ap.parse_args(argv)
     if a.resize is not None and not is_float_output(a.output):
         ap.error("--resize needs a .hdr or .pfm output: the 8-bit image is resized as the reference resizes it")
     if a.camera == "equirect":
-        for name, on in (("--adaptive", a.adaptive is not None), ("--update", a.update)):
-            if on:
-                ap.error(f"--camera equirect cannot be combined with {name}")
+        if a.adaptive is not None:
+            ap.error("--camera equirect cannot be combined with --adaptive, which samples the camera's own rays; use --pano-adaptive")
+        if a.update:
+            ap.error("--camera equirect cannot be combined with --update")
         for name, on in (("--denoise", a.denoise), ("--aov", a.aov is not None)):
             if on and not a.pano_guides:
                 ap.error(f"--camera equirect cannot be combined with {name} unless --pano-guides forms the AOVs on the panorama's rays")
-        if a.pano_guides and a.denoise and a.denoise_mode != "atrous":
-            ap.error("--pano-guides: --denoise-mode variance reads the half buffer of the camera's frame; use --denoise-mode atrous")
+        if a.pano_guides and a.denoise and a.denoise_mode != "atrous" and a.pano_adaptive is None:
+            ap.error("--pano-guides: --denoise-mode variance reads a half buffer of the panorama's grid, which only --pano-adaptive "
+                     "THRESHOLD leaves behind (0: the uniform budget); or use --denoise-mode atrous")
+        if a.pano_adaptive is not None:
+            if a.step <= 0 or a.step % 16:
+                ap.error(f"--step {a.step} is not a positive multiple of 16")
+            if not a.pano_adaptive >= 0.0:
+                ap.error("--pano-adaptive THRESHOLD must be >= 0")
     elif a.pano_yaw is not None:
         ap.error("--pano-yaw needs --camera equirect")
+    elif a.pano_adaptive is not None:
+        ap.error("--pano-adaptive needs --camera equirect")
     elif a.pano_guides:
         ap.error("--pano-guides needs --camera equirect")
     if not 0 <= a.denoise_passes <= 8:
@@ -133,7 +154,7 @@ def main(argv=None):
     for name, v in (("--denoise-sigma-var", a.denoise_sigma_var), ("--denoise-firefly", a.denoise_firefly)):
         if v is not None and not v > 0.0:
             ap.error(f"{name} {v} is not > 0")
-    if variance and a.adaptive is None:
+    if variance and a.adaptive is None and a.pano_adaptive is None:
         if a.update:
             ap.error("--update cannot be combined with --denoise-mode variance")
         if a.sample is not None and (a.sample <= 0 or a.sample % 32):
@@ -166,12 +187,16 @@ def main(argv=None):
     s = Sampler(seed=a.seed)
     t0 = time.perf_counter()
     if a.camera == "equirect":
-        cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0, guides=a.pano_guides)
+        if a.pano_adaptive is None:
+            cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0, guides=a.pano_guides)
+        else:
+            info = {}
+            cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0, guides=a.pano_guides, info=info,
+                                    adaptive=dict(threshold=a.pano_adaptive, min_samples=a.min_sample, step=a.step))
+            print(adaptive_line(info, s.nw * s.nh * render.rt.sample))
     elif a.adaptive is not None:
         info = s.execute_adaptive(render, a.adaptive, min_samples=a.min_sample, max_samples=render.rt.sample, step=a.step)
-        uniform = s.nw * s.nh * render.rt.sample
-        print(f"adaptive: {info['samples']} samples traced of {uniform} uniform ({info['samples'] / uniform:.1%}), "
-              f"{info['tiles_converged']} of {info['tiles']} tiles converged, per-pixel counts {info['min_count']}..{info['max_count']}")
+        print(adaptive_line(info, s.nw * s.nh * render.rt.sample))
     elif variance:
         if render.rt.sample <= 0 or render.rt.sample % 32:
             ap.error(f"the description's sample count {render.rt.sample} is not a positive multiple of 32, which --denoise-mode variance "

@@ -146,6 +146,11 @@ class AdaptInfo(C.Structure):
                 ("tiles_converged", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
+class RaysAdapt(C.Structure):
+    """mrt_rays_adapt: the rays of mrt_radiance_adaptive (one per supersampled pixel) and its rule"""
+    _fields_ = [("orig", C.c_void_p), ("dir", C.c_void_p), ("rule", Adapt), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class DenoiseOpts(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
                 ("mode", C.c_uint32), ("sigma_var", C.c_float), ("firefly", C.c_float), ("reserved", C.c_uint32 * 1)]

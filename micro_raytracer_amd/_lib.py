@@ -22,6 +22,7 @@ SYMBOLS = (
     "mrt_radiance", "mrt_camera_rays",
     "mrt_img_hdr", "mrt_save_image_f32",
     "mrt_aov_rays",
+    "mrt_radiance_adaptive",
 )
 
 
@@ -91,6 +92,7 @@ def lib():
     L.mrt_selftest_instantiations.argtypes = [u32p, u32p, u32p, u32]
     L.mrt_radiance.argtypes = [vp, C.POINTER(_abi.Rays), vp, C.POINTER(_abi.RaysInfo)]
     L.mrt_camera_rays.argtypes = [vp, f32p, f32p]
+    L.mrt_radiance_adaptive.argtypes = [vp, C.POINTER(_abi.RaysAdapt), C.POINTER(_abi.AdaptInfo), C.POINTER(C.c_double)]
     L.mrt_selftest_instantiations.restype = u32
     L.mrt_aov_rays.argtypes = [vp, vp, vp, u32]
     L.mrt_img_hdr.argtypes = [vp, C.POINTER(_abi.HdrOpts), f32p, C.POINTER(_abi.HdrInfo)]

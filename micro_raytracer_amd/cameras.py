@@ -25,17 +25,30 @@ def equirect(pos, nw, nh, *, yaw=0.0, elevation=(-90.0, 90.0)):
     return o, d
 
 
-def render_equirect(sampler, render, n_samples=None, *, yaw=0.0, elevation=(-90.0, 90.0), info=None, guides=False):
+def render_equirect(sampler, render, n_samples=None, *, yaw=0.0, elevation=(-90.0, 90.0), info=None, guides=False, adaptive=None):
     """Render the supersampled grid of render's frame as a panorama from its camera position (cam.dir, fov and aprt play no
     part) and put the sums into the sampler's context as n_samples accumulated samples: img() / img_ss() / the writers follow.
     guides: also install the first-hit AOVs of the same rays (Sampler.aov_rays), so that aov() and the denoisers belong to the
     panorama and not to the pinhole camera; the grid spans the full azimuth, so the filter wraps its horizontal taps (wrap_x).
+    adaptive: a dict with `threshold` and optionally `min_samples` (32) and `step` (16): the grid is sampled tile-adaptively on
+    these rays (Sampler.radiance_adaptive) with n_samples as the cap, which leaves the context in the adaptive state -- per-tile
+    counts, and a half buffer that denoise(mode="variance") reads once guides is set; info then receives mrt_adapt_info.
     Returns the sums, float32 [nh][nw][3]."""
     n = int(render.rt.sample if n_samples is None else n_samples)
     sampler.create(render)
     o, d = equirect(render.frame.cam.pos, sampler.nw, sampler.nh, yaw=yaw, elevation=elevation)
-    rgb = sampler.radiance(render, o, d, n, info=info)
-    sampler.set_accum(rgb, n)
+    if adaptive is not None:
+        unknown = set(adaptive) - {"threshold", "min_samples", "step"}
+        if unknown or "threshold" not in adaptive:
+            raise ValueError(f"render_equirect: adaptive is a dict of threshold, min_samples, step; got {sorted(adaptive)}")
+        res = sampler.radiance_adaptive(render, o, d, adaptive["threshold"], min_samples=adaptive.get("min_samples", 32), max_samples=n,
+                                        step=adaptive.get("step", 16))
+        if info is not None:
+            info.update(res)
+        rgb = sampler.accum()[0]
+    else:
+        rgb = sampler.radiance(render, o, d, n, info=info)
+        sampler.set_accum(rgb, n)
     if guides:
         sampler.aov_rays(render, o, d, wrap_x=True)       # equirect() always spans the full turn
     return rgb

@@ -1,4 +1,5 @@
-// mrt_adaptive.cpp — tile-adaptive sampling: mrt_execute_adaptive, mrt_sample_counts, mrt_adapt_half.
+// mrt_adaptive.cpp — tile-adaptive sampling: mrt_execute_adaptive, mrt_radiance_adaptive, mrt_sample_counts,
+// mrt_adapt_half.
 #include <chrono>
 #include <utility>
 #include <vector>
@@ -9,7 +10,8 @@ using namespace mrt;
 using namespace mrt::api;
 
 // ---- adaptive sampling ---------------------------------------------------------------------------------------------------------
-static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
+// rk: the rounds trace rk's caller-supplied rays (mrt_radiance_adaptive) in place of the camera's; everything else is shared
+static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, RaysKernel *rk = nullptr)
 {
     const u32 nw = c->pk.nw, nh = c->pk.nh, n_tx = (nw + 7u) / 8u, n_ty = (nh + 7u) / 8u, n_tiles = n_tx * n_ty;
     const size_t acc_floats = plane_floats(c);
@@ -39,7 +41,7 @@ static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
             const bool even = (rounds & 1u) == 0u;
             const TileList tl{lists[cur], n_active};
             u32 k_split = 1;
-            const int rc = launch_batch(c, n, a->step, &tl, even ? ad.half.p : nullptr, even, k_split, c->stats.k_split);
+            const int rc = launch_batch(c, n, a->step, &tl, even ? ad.half.p : nullptr, even, k_split, c->stats.k_split, rk);
             if (rc) return rc;
         }
         if (n < a->min_samples) continue;
@@ -67,6 +69,7 @@ static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
     }
     c->count = lo;
     c->adaptive = true;
+    c->adaptive_rays = rk != nullptr;
     c->stats.samples = samples;
     c->stats_pending = true;
     if (info) {
@@ -84,34 +87,94 @@ static int adapt_run(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info)
     return MRT_OK;
 }
 
+// The rules of mrt_adapt, shared by both adaptive calls (fn: the caller's name in the message)
+static int adapt_rule(const mrt_adapt *a, const char *fn)
+{
+    const unsigned long long two = 2ull * a->step;
+    if (a->step == 0u || a->step % kChunk) return fail(MRT_ERR_ARG, "%s: step %u is not a positive multiple of %u", fn, a->step, kChunk);
+    if (a->min_samples == 0u || a->min_samples % two || a->max_samples == 0u || a->max_samples % two)
+        return fail(MRT_ERR_ARG, "%s: min_samples %u and max_samples %u must be positive multiples of 2 * step = %llu", fn, a->min_samples, a->max_samples, two);
+    if (a->min_samples > a->max_samples) return fail(MRT_ERR_ARG, "%s: min_samples %u > max_samples %u", fn, a->min_samples, a->max_samples);
+    if (!(a->threshold >= 0.0f)) return fail(MRT_ERR_ARG, "%s: threshold %g is not >= 0", fn, (double)a->threshold);
+    return MRT_OK;
+}
+
+// ... and their precondition: one device, no samples held or booked
+static int adapt_state(const mrt_ctx *c, const char *fn)
+{
+    if (c->group || c->shard_count > 1u) return fail(MRT_ERR_STATE, "%s: sharded and multi-device contexts are not supported", fn);
+    if (c->adaptive || c->count || c->pending || c->full.p)
+        return fail(MRT_ERR_STATE, "%s: the context holds samples (an adaptive render starts from none): mrt_reset first", fn);
+    return MRT_OK;
+}
+
+static void adapt_begin(mrt_ctx *c)
+{
+    la_drop(c);
+    reset_exec_stats(c);
+    c->stats.k_split = 1; c->stats.deferred = 0;
+}
+
+// A failed adaptive run leaves nothing half done behind: the context is an empty uniform one again
+static int adapt_rollback(mrt_ctx *c, int rc)
+{
+    return keep_first_error(rc, [&] {
+        (void)hipStreamSynchronize(c->stream.get());
+        (void)hipMemsetAsync(c->d_accum, 0, plane_floats(c) * sizeof(float), c->stream.get());      // on the stream the next launch runs on
+        (void)hipStreamSynchronize(c->stream.get());
+        (void)hipGetLastError();
+        c->adaptive = false; c->adaptive_rays = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
+    });
+}
+
 extern "C" {
 
 int mrt_execute_adaptive(mrt_ctx *c, const mrt_adapt *a, mrt_adapt_info *info, double *seconds)
 {
     if (!c || !a) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: null argument");
-    const unsigned long long two = 2ull * a->step;
-    if (a->step == 0u || a->step % kChunk) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: step %u is not a positive multiple of %u", a->step, kChunk);
-    if (a->min_samples == 0u || a->min_samples % two || a->max_samples == 0u || a->max_samples % two)
-        return fail(MRT_ERR_ARG, "mrt_execute_adaptive: min_samples %u and max_samples %u must be positive multiples of 2 * step = %llu", a->min_samples, a->max_samples, two);
-    if (a->min_samples > a->max_samples) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: min_samples %u > max_samples %u", a->min_samples, a->max_samples);
-    if (!(a->threshold >= 0.0f)) return fail(MRT_ERR_ARG, "mrt_execute_adaptive: threshold %g is not >= 0", (double)a->threshold);
-    if (c->group || c->shard_count > 1u) return fail(MRT_ERR_STATE, "mrt_execute_adaptive: sharded and multi-device contexts are not supported");
-    if (c->adaptive || c->count || c->pending || c->full.p)
-        return fail(MRT_ERR_STATE, "mrt_execute_adaptive: the context holds samples (an adaptive render starts from none): mrt_reset first");
+    int rc;
+    if ((rc = adapt_rule(a, "mrt_execute_adaptive")) || (rc = adapt_state(c, "mrt_execute_adaptive"))) return rc;
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = set_device(c);
-    if (rc) return rc;
-    la_drop(c);
-    reset_exec_stats(c);
-    c->stats.k_split = 1; c->stats.deferred = 0;
-    if ((rc = adapt_run(c, a, info)))
-        return keep_first_error(rc, [&] {            // nothing half done stays behind: the context is an empty uniform one again
-            (void)hipStreamSynchronize(c->stream.get());
-            (void)hipMemsetAsync(c->d_accum, 0, plane_floats(c) * sizeof(float), c->stream.get());      // on the stream the next launch runs on
-            (void)hipStreamSynchronize(c->stream.get());
-            (void)hipGetLastError();
-            c->adaptive = false; c->count = 0; c->stats_pending = false; c->ev_used = 0;
-        });
+    if ((rc = set_device(c))) return rc;
+    adapt_begin(c);
+    if ((rc = adapt_run(c, a, info))) return adapt_rollback(c, rc);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ok();
+    return MRT_OK;
+}
+
+// mrt_execute_adaptive on one caller-supplied ray per supersampled pixel: the same rounds, rule and state, the
+// trace launches on the supplied rays (pt_rays_tiles)
+int mrt_radiance_adaptive(mrt_ctx *c, const mrt_rays_adapt *r, mrt_adapt_info *info, double *seconds)
+{
+    if (!c || !r || !r->orig || !r->dir) return fail(MRT_ERR_ARG, "mrt_radiance_adaptive: null argument");
+    int rc;
+    if ((rc = adapt_rule(&r->rule, "mrt_radiance_adaptive"))) return rc;
+    if (r->flags & ~(uint32_t)MRT_RAYS_DEVICE) return fail(MRT_ERR_ARG, "mrt_radiance_adaptive: unknown flags 0x%x", r->flags);
+    if (r->reserved[0] || r->reserved[1] || r->reserved[2]) return fail(MRT_ERR_ARG, "mrt_radiance_adaptive: reserved words must be 0");
+    if ((rc = adapt_state(c, "mrt_radiance_adaptive"))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = set_device(c))) return rc;
+    RaysKernel k;
+    if ((rc = rays_kernel(c, k))) return rc;
+    // the rays on the device: the caller's own, or one upload for the whole call
+    const size_t words = (size_t)c->pk.nw * c->pk.nh * 3u;
+    DeviceMem<float> d_o, d_d;
+    k.orig = r->orig; k.dir = r->dir;
+    if (!(r->flags & MRT_RAYS_DEVICE)) {
+        HIP_TRY(d_o.alloc(words));
+        HIP_TRY(d_d.alloc(words));
+        HIP_TRY(hipMemcpy(d_o.p, r->orig, words * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_d.p, r->dir, words * sizeof(float), hipMemcpyHostToDevice));
+        k.orig = d_o.p; k.dir = d_d.p;
+    }
+    // the kernel writes what the frame kernel of an adaptive render writes: the context's accumulator, chunk planes and counters
+    k.P.to_planes = 0u;
+    k.P.accum = c->d_accum;
+    k.P.count_segments = c->count_segments ? 1u : 0u; k.P.segments = c->segments.p;
+    k.P.tile_counter = nullptr; k.P.persist_grid = 0u; k.P.band_items = 0u;
+    adapt_begin(c);
+    if ((rc = adapt_run(c, &r->rule, info, &k))) return adapt_rollback(c, rc);
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     ok();
     return MRT_OK;

@@ -95,7 +95,12 @@ int mrt::api::denoise_run(mrt_ctx *c, const mrt_denoise_opts *o, mrt_denoise_inf
     if (d.mode == MRT_DN_VARIANCE && !c->adaptive)
         return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE needs the half buffer of an adaptive render on this context since its last reset or "
                     "mrt_set_accum; for a uniform budget of n samples call mrt_execute_adaptive with threshold 0 and min_samples = max_samples = n", fn);
-    if (d.mode == MRT_DN_VARIANCE && c->aov_ready && c->aov->from_rays)
+    const bool rays_aov = c->aov_ready && c->aov->from_rays;
+    // the half buffer and the guides must belong to the same grid: the camera's frame, or the rays of mrt_radiance_adaptive
+    if (d.mode == MRT_DN_VARIANCE && c->adaptive_rays && !rays_aov)
+        return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE reads the adaptive half buffer, which belongs to the rays of mrt_radiance_adaptive, but the "
+                    "AOVs are the camera's own; install those of the same rays with mrt_aov_rays first", fn);
+    if (d.mode == MRT_DN_VARIANCE && !c->adaptive_rays && rays_aov)
         return fail(MRT_ERR_STATE, "%s: MRT_DN_VARIANCE reads the adaptive half buffer, which belongs to the camera's frame, but the AOVs "
                     "installed are those of caller-supplied rays; mrt_aov_rays(ctx, NULL, NULL, 0) returns to the camera's", fn);
     if ((rc = whole_frame(c, fn, "", S)) || (rc = aov_compute(c, cached, aov_ms))) return rc;

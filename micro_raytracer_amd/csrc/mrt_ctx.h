@@ -188,6 +188,7 @@ struct mrt_ctx {
     mrt_stats stats;
     std::unique_ptr<mrt::api::Group> group;
     bool adaptive = false;                        // the accumulator holds an adaptive render: per-tile counts, count = the smallest
+    bool adaptive_rays = false;                   // ... of caller-supplied rays (mrt_radiance_adaptive): the half buffer belongs to their grid, not the camera's frame
     std::unique_ptr<mrt::api::Adaptive> ad;
     std::unique_ptr<mrt::api::Image> img;
     std::unique_ptr<mrt::api::Hdr> hdr;
@@ -256,6 +257,20 @@ FlatScene flat_scene(mrt_ctx *c);
 // A multi-device context's mrt_execute: every sub-context's launches, one ncclGather to device 0, the rows into the frame
 int exec_group(mrt_ctx *g, uint32_t n_samples);
 
+// mrt_radiance.cpp
+// What mrt_radiance and mrt_radiance_adaptive launch for this context: the arguments of a kernel without F_DEEP on the flat scene
+// (the context's seed; accumulator, planes, counters and sampling range are the caller's to set), its instantiation
+// pt_instantiation(256, false, features), whether it stages the scene in LDS, and its LDS bytes.  orig, dir: the rays of a
+// tile-list launch, on the device (launch_batch).  Sets the error and returns its code when the flat scene cannot be had.
+struct RaysKernel {
+    Params P;
+    u32 inst = 0;
+    bool in_lds = false;
+    size_t lds = 0;
+    const float *orig = nullptr, *dir = nullptr;
+};
+int rays_kernel(mrt_ctx *c, RaysKernel &k);
+
 // mrt_execute.cpp
 // asynchronous half of mrt_execute on one device: everything up to the closing event
 int exec_launch(mrt_ctx *c, uint32_t n_samples);
@@ -271,7 +286,9 @@ int resolve_stats(mrt_ctx *c);
 // (split_policy, sized from the tiles traced), cut into chunk-aligned launches, each followed by the fold of its chunk sums into
 // the accumulator -- and into `half` too when it is not null (listed tiles only).  planes: every launch goes through the chunk
 // planes.  k_split receives split_policy's lanes per pixel; ks_max is raised to the largest split of any launch.
-int launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *half, bool planes, u32 &k_split, u32 &ks_max);
+// rk (listed tiles only): the trace launches are pt_rays_tiles on rk's rays with rk->P -- whose sampling range, split and planes
+// this sets -- in place of the context's own kernel and c->P; split, cut and folds are the same.
+int launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *half, bool planes, u32 &k_split, u32 &ks_max, RaysKernel *rk = nullptr);
 // The look-ahead of the eager per-call path: any call other than a one-sample execute (n != 1, reset, set_accum) drops what was
 // traced ahead
 void la_drop(mrt_ctx *c);

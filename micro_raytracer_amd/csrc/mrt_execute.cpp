@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "mrt_ctx.h"
+#include "mrt_rays_adapt.h"
 
 using namespace mrt;
 using namespace mrt::api;
@@ -99,17 +100,20 @@ static int split_policy(mrt_ctx *c, unsigned long long wave_tiles, u32 n_chunks,
 
 // One trace launch of P on `stream`: the tile counter P draws from is reset first when the launch is persistent (before ev0, so
 // the kernel time leaves the reset out), then ev0, launch_pt, ev1 (null events are not recorded).  tl: a tile-list launch.
-static int launch_trace(mrt_ctx *c, const Params &P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const TileList *tl)
+// rk: the trace launch is pt_rays_tiles on rk's rays over tl (mrt_radiance_adaptive) instead of the context's own kernel.
+static int launch_trace(mrt_ctx *c, const Params &P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const TileList *tl, const RaysKernel *rk = nullptr)
 {
     if (c->plan.block_threads > 64u && P.persist_grid) HIP_TRY(hipMemsetAsync(P.tile_counter, 0, sizeof(u32), stream));
     if (ev0) HIP_TRY(hipEventRecord(ev0, stream));
-    HIP_TRY(launch_pt(P, c->plan.block_threads, c->plan.in_lds, c->pk.features, stream, tl));
+    if (rk) HIP_TRY(launch_rays_tiles(P, rk->in_lds, rk->inst, *tl, rk->orig, rk->dir, stream));
+    else HIP_TRY(launch_pt(P, c->plan.block_threads, c->plan.in_lds, c->pk.features, stream, tl));
     if (ev1) HIP_TRY(hipEventRecord(ev1, stream));
     return MRT_OK;
 }
 
-int mrt::api::launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *half, bool planes, u32 &k_split, u32 &ks_max)
+int mrt::api::launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, float *half, bool planes, u32 &k_split, u32 &ks_max, RaysKernel *rk)
 {
+    Params &P = rk ? rk->P : c->P;                   // the launch's arguments: the context's own, or those of the supplied-ray kernel
     const u32 n_chunks = (base + n - 1u) / kChunk - base / kChunk + 1u;
     // sample split: spread a small frame over more wavefronts, one lane per (pixel, every k-th sample chunk)
     const unsigned long long wave_tiles = tl ? tl->n : (unsigned long long)((c->pk.nw + 7) / 8) * ((c->local_rows + 7) / 8);
@@ -117,8 +121,8 @@ int mrt::api::launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, floa
     int rc = split_policy(c, wave_tiles, n_chunks, planes, k_split, cap);
     if (rc) return rc;
     const size_t plane = plane_floats(c);
-    c->P.partial = c->partial.p;
-    c->P.partial_stride = plane;
+    P.partial = c->partial.p;
+    P.partial_stride = plane;
     const u32 s_end = base + n;
     while (base < s_end) {
         // this launch: samples [base, stop), stop on a chunk boundary (or the end); k_split == 1 needs no buffer: one launch
@@ -131,23 +135,23 @@ int mrt::api::launch_batch(mrt_ctx *c, u32 base, u32 n, const TileList *tl, floa
         u32 ks = k_split;
         while (ks > nc) ks /= 2u;
         if (planes && ks < 2u) ks = 2u;                  // (a lane of chunk phase >= nc has nothing to do)
-        c->P.n_samples = stop - base;
-        c->P.sample_base = base;
-        c->P.k_split = ks;
+        P.n_samples = stop - base;
+        P.sample_base = base;
+        P.k_split = ks;
         if (ks > ks_max) ks_max = ks;
         while (c->event_timing && c->evs.size() < (size_t)c->ev_used + 3u) { Event e; HIP_TRY(create(e)); c->evs.push_back(std::move(e)); }
         const Event *ev = c->event_timing ? &c->evs[c->ev_used] : nullptr;
-        c->P.persist_grid = (c->plan.small_plain_grid && stop - base < kChunk) ? 0u : c->persist_grid;
+        P.persist_grid = (rk || (c->plan.small_plain_grid && stop - base < kChunk)) ? 0u : c->persist_grid;     // (pt_rays_tiles: a plain grid)
         // Tapered items: a persistent launch through the chunk planes of a band kernel cuts its nc
         // chunks into contiguous bands, longest first, instead of ks interleaved phases.  An explicit MRT_K_SPLIT keeps the phases.
-        c->P.band_items = 0u;
-        if (ks > 1u && !c->knobs.k_split && c->P.persist_grid && c->plan.block_threads > 64u
+        P.band_items = 0u;
+        if (ks > 1u && !c->knobs.k_split && P.persist_grid && c->plan.block_threads > 64u
             && band_kernel(c->plan.in_lds, (int)c->plan.block_threads, c->plan.inst)) {
             const Bands b = plan_bands(nc, wave_tiles, (unsigned long long)c->persist_grid * (c->plan.block_threads / 64u), c->knobs);
-            c->P.band_items = b.items; c->P.n_bands = b.n; c->P.band_tail = b.tail;
-            for (u32 i = 0; i < kMaxBands; ++i) { c->P.band_first[i] = b.first[i]; c->P.band_len[i] = b.len[i]; }
+            P.band_items = b.items; P.n_bands = b.n; P.band_tail = b.tail;
+            for (u32 i = 0; i < kMaxBands; ++i) { P.band_first[i] = b.first[i]; P.band_len[i] = b.len[i]; }
         }
-        if ((rc = launch_trace(c, c->P, c->stream.get(), ev ? ev[0].get() : nullptr, ev ? ev[1].get() : nullptr, tl))) return rc;
+        if ((rc = launch_trace(c, P, c->stream.get(), ev ? ev[0].get() : nullptr, ev ? ev[1].get() : nullptr, tl, rk))) return rc;
         if (ks > 1u) {
             if (tl) HIP_TRY(launch_reduce_chunks_listed(c->d_accum, half, c->partial.p, tl->tiles, tl->n, c->pk.nw, c->pk.nh, plane, nc, c->stream.get()));
             else HIP_TRY(launch_reduce_chunks(c->d_accum, c->partial.p, (size_t)c->local_rows * c->pk.nw * 3, plane, nc, c->stream.get()));

@@ -6,6 +6,26 @@
 using namespace mrt;
 using namespace mrt::api;
 
+int mrt::api::rays_kernel(mrt_ctx *c, RaysKernel &k)
+{
+    // The scene as a kernel without F_DEEP reads it: the context's own blob, or (deep staging) the binary-BVH packing
+    const FlatScene fs = flat_scene(c);
+    if (!fs.blob) return g_status;
+    const Packed &rp = fs.pk;
+    k.P = c->P;
+    if (c->aov_pk) {
+        k.P = rp.P;
+        k.P.seed_lo = c->P.seed_lo; k.P.seed_hi = c->P.seed_hi;
+    }
+    k.P.blob = fs.blob;
+    k.inst = pt_instantiation(256u, false, rp.features);
+    // Staged in LDS when the context stages the whole scene and four 256-thread workgroups of it -- the 4 waves per SIMD these
+    // feature sets are bound to -- still fit a CU; through L2 otherwise (warm, deep and L2 contexts, MRT_SCENE_IN_L2)
+    k.in_lds = c->plan.in_lds && c->plan.staging == 0u && rays_lds_bytes(k.P, true, k.inst) <= kLdsLimit / 4u;
+    k.lds = rays_lds_bytes(k.P, k.in_lds, k.inst);
+    return MRT_OK;
+}
+
 extern "C" {
 
 int mrt_radiance(mrt_ctx *c, const mrt_rays *r, float *rgb, mrt_rays_info *info)
@@ -20,21 +40,12 @@ int mrt_radiance(mrt_ctx *c, const mrt_rays *r, float *rgb, mrt_rays_info *info)
     if (c->group) return fail(MRT_ERR_STATE, "mrt_radiance: multi-device context");
     int rc;
     if ((rc = set_device(c))) return rc;
-    // The scene as a kernel without F_DEEP reads it: the context's own blob, or (deep staging) the binary-BVH packing
-    const FlatScene fs = flat_scene(c);
-    if (!fs.blob) return g_status;
-    const Packed &rp = fs.pk;
-    Params P = c->P;
-    if (c->aov_pk) {
-        P = rp.P;
-        P.seed_lo = c->P.seed_lo; P.seed_hi = c->P.seed_hi;
-    }
-    P.blob = fs.blob;
-    const u32 inst = pt_instantiation(256u, false, rp.features);
-    // Staged in LDS when the context stages the whole scene and four 256-thread workgroups of it -- the 4 waves per SIMD these
-    // feature sets are bound to -- still fit a CU; through L2 otherwise (warm, deep and L2 contexts, MRT_SCENE_IN_L2)
-    const bool in_lds = c->plan.in_lds && c->plan.staging == 0u && rays_lds_bytes(P, true, inst) <= kLdsLimit / 4u;
-    const size_t lds = rays_lds_bytes(P, in_lds, inst);
+    RaysKernel k;
+    if ((rc = rays_kernel(c, k))) return rc;
+    Params &P = k.P;
+    const u32 inst = k.inst;
+    const bool in_lds = k.in_lds;
+    const size_t lds = k.lds;
     const size_t n = r->n;
     const bool dev = (r->flags & MRT_RAYS_DEVICE) != 0u;
     DeviceMem<float> d_o, d_d, d_rgb;

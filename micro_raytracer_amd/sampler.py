@@ -262,7 +262,7 @@ class Sampler:
         """The accumulated means filtered by the AOV-guided a-trous filter (mrt_denoise), f32 [nh][nw][3].  info: a dict that
         receives mrt_denoise_info (and "mode").  mode "variance": the colour term follows a per-pixel variance estimate from the
         half buffer, so it needs an execute_adaptive() on this context (threshold=0, min_samples=max_samples=n for a uniform
-        budget); sigma_var / firefly of None take the library's defaults, firefly=float("inf") switches the clamp off."""
+        budget) -- or, with the guides of aov_rays(), a radiance_adaptive() on the same rays; sigma_var / firefly of None take the library's defaults, firefly=float("inf") switches the clamp off."""
         self._need()
         o = _abi.denoise_opts(passes, sigma_color, sigma_normal, sigma_plane, mode, sigma_var, firefly)
         out = np.empty((self.nh, self.nw, 3), np.float32)
@@ -368,6 +368,42 @@ class Sampler:
         del keep
         if info is not None:
             info.update({k: getattr(ri, k) for k, _ in ri._fields_ if k != "reserved"})
+        return out
+
+    def radiance_adaptive(self, render: Render, orig, dir, threshold: float, min_samples: int = 32, max_samples=None, step: int = 16) -> dict:
+        """execute_adaptive() on a custom camera (mrt_radiance_adaptive): orig and dir of shape [nh][nw][3], one ray
+        per supersampled pixel, traced as given with the pixel index as the hash key; rounds, rule and the returned dict are
+        those of execute_adaptive().  Needs a context without samples.  Afterwards the context holds the adaptive render of these
+        rays: accum(), sample_counts(), adapt_half(), img*() and denoise() serve it, and denoise(mode="variance") works once
+        aov_rays() has installed the guides of the same rays.  Numpy arrays go through the host (one upload per call), torch
+        tensors on the context's device are read in place."""
+        self._ensure(render)
+        r = _abi.RaysAdapt()
+        r.rule.min_samples = int(min_samples)
+        r.rule.max_samples = int(render.rt.sample if max_samples is None else max_samples)
+        r.rule.step = int(step)
+        r.rule.threshold = float(threshold)
+        shape = (self.nh, self.nw, 3)
+        if type(orig).__module__.split(".")[0] == "torch":
+            import torch
+            if not (orig.is_cuda and getattr(dir, "is_cuda", False)):
+                raise ValueError("radiance_adaptive: orig and dir are both tensors on the context's device, or both host arrays")
+            if tuple(orig.shape) != shape or tuple(dir.shape) != shape:
+                raise ValueError(f"radiance_adaptive: orig and dir are {shape}, got {tuple(orig.shape)} and {tuple(dir.shape)}")
+            o, d = orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous()
+            torch.cuda.synchronize(o.device)          # the library launches on a stream of its own
+            r.orig, r.dir, r.flags = o.data_ptr(), d.data_ptr(), _abi.RAYS_DEVICE
+        else:
+            o, d = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
+            if o.shape != shape or d.shape != shape:
+                raise ValueError(f"radiance_adaptive: orig and dir are {shape}, got {o.shape} and {d.shape}")
+            r.orig, r.dir = o.ctypes.data, d.ctypes.data
+        info = _abi.AdaptInfo()
+        secs = C.c_double()
+        _lib.check(_lib.lib().mrt_radiance_adaptive(self._ctx, C.byref(r), C.byref(info), C.byref(secs)))
+        del o, d
+        out = {k: getattr(info, k) for k, _ in info._fields_}
+        out["seconds"] = secs.value
         return out
 
     # -- extras of the C ABI -----------------------------------------------------------------
