@@ -11,8 +11,10 @@
 
 #include "../../micro_raytracer_amd/csrc/mrt_rays_adapt.h"
 
-// what this probe runs: the two feature sets of pt_rays_tiles that scenes without instance BVH, vertex attributes and environment take
-#define LANE_FEAT_LIST LANE_F(F_ALL & ~F_TRI) LANE_F(F_ALL)
+// what this probe runs: the eight feature sets of pt_rays_tiles (MRT_RAYS_LIST of csrc/mrt_rays.h)
+#define LANE_FEAT_LIST \
+    LANE_F(F_ALL & ~F_TRI) LANE_F(F_ALL) LANE_F((F_ALL & ~F_TRI) | F_BVH) LANE_F(F_ALL | F_BVH) \
+    LANE_F(F_ALL | F_VATTR) LANE_F(F_ALL | F_BVH | F_VATTR) LANE_F(F_ALL | F_VATTR | F_ENV) LANE_F(F_ALL | F_BVH | F_VATTR | F_ENV)
 #include "lane_host.h"
 
 using namespace mrt;

@@ -1,6 +1,8 @@
 """mrt_radiance_adaptive without a GPU: the per-lane body of csrc/mrt_rays_adapt.h, built for x86 (tests/emu/rays_adapt_probe.cpp),
 holds one round over a tile list to the x86 ray body of mrt_radiance at every launch shape; the ABI struct, the header, the CLI
-rules and cameras.render_equirect(adaptive=...)."""
+rules and cameras.render_equirect(adaptive=...).  The same round on one 44 x 36 grid per feature set of pt_rays_tiles
+(tests/radiance_adapt_cases.py: wild rays beside tame ones in every odd tile), and the preconditions of
+tests/test_gpu_radiance_adaptive_oracle.py, from the x86 ray body's sums alone."""
 import ctypes as C
 import os
 import shutil
@@ -9,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import radiance_adapt_cases as AC
 import rays_ref as Y
 from conftest import make_holder
 from emu.build import probe_or_skip
@@ -17,6 +20,9 @@ f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRID = (12, 10)                       # 2 x 2 tiles: the right column 4 pixels wide, the lower row 2 pixels high
 LISTED = [3, 0, 2]                    # tile 1 is left out; the list is in no particular order
+# ... of the 30 tiles of the 44 x 36 grids: 17 entries (with four wavefronts to a workgroup, a launch has wavefronts past the list
+# at k_split 1 and 2), odd (wild) and even tiles, the corner and both sliver edges listed and left out
+LISTED_GRID = [29, 3, 14, 0, 23, 8, 27, 11, 5, 16, 21, 24, 1, 18, 7, 26, 13]
 
 
 @pytest.fixture(scope="module")
@@ -32,10 +38,10 @@ def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-def _round(L, holder, feat, base, n, k_split, tiles, o, d, accum, half):
+def _round(L, holder, feat, base, n, k_split, tiles, o, d, accum, half, seed=Y.SEED):
     t = np.ascontiguousarray(tiles, np.uint32)
     seg = C.c_uint64(0)
-    rc = L.ra_round(*Y._ptrs(holder), feat, Y.SEED, base, n, k_split, t.size, _p(t, C.c_uint32), _p(o), _p(d), _p(accum),
+    rc = L.ra_round(*Y._ptrs(holder), feat, seed, base, n, k_split, t.size, _p(t, C.c_uint32), _p(o), _p(d), _p(accum),
                     None if half is None else _p(half), C.byref(seg))
     assert rc == 0, L.ra_error()
     return int(seg.value)
@@ -88,6 +94,68 @@ def test_one_round_over_a_tile_list_equals_the_ray_body(adapt_probe):
     _round(adapt_probe, holder, feat, 16, 16, 2, LISTED, o, d, acc, half)
     assert Y.same(acc, np.where(listed[..., None], chunk[0] + chunk[1], chunk[0]))
     assert Y.same(half, np.where(listed[..., None], h0 + chunk[1], h0))
+
+
+@pytest.mark.parametrize("name", AC.FEAT_NAMES)
+def test_one_round_over_a_tile_list_on_a_grid_of_every_feature_set(adapt_probe, oracle_mod, name):
+    """The round of the test above -- samples [16, 48) on top of chunk 0, k_split 1, 2 and 4 -- on the 44 x 36 grid of one case per
+    feature set of MRT_RAYS_LIST, over 17 of its 30 tiles in no particular order.  Expected, from the x86 mrt_radiance body: the
+    accumulator is chunk 0 + chunk 1 + chunk 2 in float32 in that order, word for word, NaN words included; the half buffer
+    holds the same fold; unlisted pixels keep their bytes; the segment total is that of the listed rays."""
+    case = AC.case(name, oracle_mod)
+    _, holder = case.holder()
+    o, d = case.o, case.d
+    assert len(set(LISTED_GRID)) == len(LISTED_GRID) < AC.N_TILES and LISTED_GRID != sorted(LISTED_GRID) and AC.CORNER in LISTED_GRID
+    chunk = [case.x86(16 * j, 16) for j in range(3)]
+    listed = AC.tiles_mask(LISTED_GRID)
+    assert (listed & case.wild).any() and (~listed & case.wild).any()
+    nan_words = int(np.isnan(chunk[1][listed]).sum())
+    assert (nan_words > 0) == case.has_nan
+    with np.errstate(invalid="ignore"):
+        want = np.where(listed[..., None], (chunk[0] + chunk[1]) + chunk[2], chunk[0])
+        h0 = np.full_like(chunk[0], f32(0.375))
+        want_h = np.where(listed[..., None], (h0 + chunk[1]) + chunk[2], h0)
+    m = listed.reshape(-1)
+    rays = Y.shared_probe()
+    seg_listed = sum(Y.x86_radiance(rays, holder, case.feat, o.reshape(-1, 3)[m], d.reshape(-1, 3)[m], 16, seed=AC.SEED, sample_base=16 * j,
+                                    key=np.flatnonzero(m), segments=True)[1] for j in (1, 2))
+    for k_split in (1, 2, 4):
+        acc = chunk[0].copy()
+        half = None if k_split == 1 else h0.copy()
+        seg = _round(adapt_probe, holder, case.feat, 16, 32, k_split, LISTED_GRID, o, d, acc, half, seed=AC.SEED)
+        diff = int((Y.bits(acc) != Y.bits(want)).any(-1).sum())
+        print(f"one round, x86: {name:52s} FEAT {case.feat:4d} k_split {k_split}: {diff} of {m.size} pixels differ ({int(m.sum())} listed, "
+              f"{int(case.wild.sum())} wild, {nan_words} NaN words in chunk 1 of the listed), {seg} segments against {seg_listed}")
+        assert diff == 0
+        assert seg == seg_listed
+        if half is not None:
+            assert Y.same(half, want_h)
+
+
+def test_preconditions_of_the_gpu_oracle_tests(oracle_mod):
+    """What tests/test_gpu_radiance_adaptive_oracle.py needs in order to say anything, from the x86 mrt_radiance body's sums at 32, 64
+    and 96 samples and the numpy rule alone: at the threshold those tests take (the median of the non-NaN tile errors at 32) every
+    case has at least two distinct stop counts (but the two of the scene without noise, AC.NOISE_FREE), all three counts occur
+    across the table, and a tile with a NaN sum never stops before the cap."""
+    seen = {}
+    for name in AC.NAMES:
+        case = AC.case(name, oracle_mod)
+        whole = {n: case.x86(0, n) for n in AC.STOPS}
+        chunk = {j: case.x86(16 * j, 16) for j in (0, 2)}
+        thr = AC.median_threshold(whole[32], chunk[0])
+        counts = AC.rule_counts(whole, chunk, thr)
+        hist = {n: int((counts == n).sum()) for n in AC.STOPS}
+        nan = AC.nan_tiles(whole[32])
+        print(f"stop counts from the x86 sums: {name:52s} threshold {thr:.4f} tiles per count {hist} tiles with a NaN sum {int(nan.sum())}")
+        assert sum(hist.values()) == AC.N_TILES, (name, hist)
+        if case.noise_free:           # (the one scene of FN | F_BVH: every tile error is exactly 0, nothing runs on)
+            assert hist[AC.MIN_SAMPLES] == AC.N_TILES and thr == 0.0, (name, hist, thr)
+        else:
+            assert sum(v > 0 for v in hist.values()) >= 2, (name, hist)
+        assert nan.any() == case.has_nan and np.array_equal(nan, AC.nan_tiles(whole[96])) and (counts[nan] == AC.MAX_SAMPLES).all(), name
+        for n, v in hist.items():
+            seen[n] = seen.get(n, 0) + v
+    assert all(seen[n] > 0 for n in AC.STOPS), seen
 
 
 def test_header_declares_the_call_and_abi_matches():
