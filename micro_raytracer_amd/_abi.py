@@ -201,6 +201,11 @@ class HdrInfo(C.Structure):
     _fields_ = [("resize_ms", C.c_double), ("dn", DenoiseInfo), ("reserved", C.c_uint32 * 2)]
 
 
+def as_dict(s) -> dict:
+    """A ctypes struct's fields by name, without its `reserved` words"""
+    return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
+
 STAGING = ("all", "warm", "deep", "none")
 MAP_SLOTS = ("tex", "rmap", "mmap", "gmap", "omap", "emap")
 

@@ -150,24 +150,16 @@ int mrt_radiance_adaptive(mrt_ctx *c, const mrt_rays_adapt *r, mrt_adapt_info *i
     if (!c || !r || !r->orig || !r->dir) return fail(MRT_ERR_ARG, "mrt_radiance_adaptive: null argument");
     int rc;
     if ((rc = adapt_rule(&r->rule, "mrt_radiance_adaptive"))) return rc;
-    if (r->flags & ~(uint32_t)MRT_RAYS_DEVICE) return fail(MRT_ERR_ARG, "mrt_radiance_adaptive: unknown flags 0x%x", r->flags);
-    if (r->reserved[0] || r->reserved[1] || r->reserved[2]) return fail(MRT_ERR_ARG, "mrt_radiance_adaptive: reserved words must be 0");
+    if ((rc = rays_words(r->flags, r->reserved, "mrt_radiance_adaptive"))) return rc;
     if ((rc = adapt_state(c, "mrt_radiance_adaptive"))) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if ((rc = set_device(c))) return rc;
     RaysKernel k;
     if ((rc = rays_kernel(c, k))) return rc;
     // the rays on the device: the caller's own, or one upload for the whole call
-    const size_t words = (size_t)c->pk.nw * c->pk.nh * 3u;
-    DeviceMem<float> d_o, d_d;
-    k.orig = r->orig; k.dir = r->dir;
-    if (!(r->flags & MRT_RAYS_DEVICE)) {
-        HIP_TRY(d_o.alloc(words));
-        HIP_TRY(d_d.alloc(words));
-        HIP_TRY(hipMemcpy(d_o.p, r->orig, words * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_d.p, r->dir, words * sizeof(float), hipMemcpyHostToDevice));
-        k.orig = d_o.p; k.dir = d_d.p;
-    }
+    DeviceRays rays;
+    HIP_TRY(rays.take(r->orig, r->dir, (size_t)c->pk.nw * c->pk.nh, (r->flags & MRT_RAYS_DEVICE) != 0u));
+    k.orig = rays.orig; k.dir = rays.dir;
     // the kernel writes what the frame kernel of an adaptive render writes: the context's accumulator, chunk planes and counters
     k.P.to_planes = 0u;
     k.P.accum = c->d_accum;

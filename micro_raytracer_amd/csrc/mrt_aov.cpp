@@ -27,28 +27,42 @@ static int aov_state(mrt_ctx *c)
     return MRT_OK;
 }
 
+// What aov_compute and mrt_aov_rays share around their launch: the flat scene, the context's Aov state, and the Params of that
+// scene with its blob and the AOV counter block ...
+struct AovPass { const Packed *pk; Params P; };
+static int aov_pass(mrt_ctx *c, AovPass &ap)
+{
+    const FlatScene fs = flat_scene(c);
+    if (!fs.blob) return g_status;
+    if (const int rc = aov_state(c)) return rc;
+    ap.pk = &fs.pk;
+    ap.P = fs.pk.P;
+    ap.P.blob = fs.blob;
+    ap.P.segments = c->aov->seg.p;
+    return MRT_OK;
+}
+// ... and the bookkeeping after a successful pass
+static void aov_done(mrt_ctx *c, const AovPass &ap)
+{
+    c->aov->inst_first = inst_first(*ap.pk);
+    c->aov_ready = true;
+}
+
 // The AOV buffers of this context, computed on first use: *ms = HIP-event time of the pass (0 when they were there already)
 static int aov_compute(mrt_ctx *c, bool &cached, double &ms)
 {
     cached = c->aov_ready;
     ms = 0.0;
     if (c->aov_ready) return MRT_OK;
-    const FlatScene fs = flat_scene(c);
-    if (!fs.blob) return g_status;
-    const Packed &ap = fs.pk;
-    int rc;
-    if ((rc = aov_state(c))) return rc;
+    AovPass ap;
+    if (const int rc = aov_pass(c, ap)) return rc;
     Aov &a = *c->aov;
-    Params P = ap.P;
-    P.blob = fs.blob;
-    P.segments = a.seg.p;
     HIP_TRY(hipEventRecord(a.ev[0].get(), c->stream.get()));
-    HIP_TRY(launch_aov(P, ap.features, a.guide.p, a.albedo.p, a.ids.p, c->stream.get()));
+    HIP_TRY(launch_aov(ap.P, ap.pk->features, a.guide.p, a.albedo.p, a.ids.p, c->stream.get()));
     HIP_TRY(hipEventRecord(a.ev[1].get(), c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
     { float t = 0.0f; HIP_TRY(hipEventElapsedTime(&t, a.ev[0].get(), a.ev[1].get())); ms = t; }
-    a.inst_first = inst_first(ap);
-    c->aov_ready = true;
+    aov_done(c, ap);
     return MRT_OK;
 }
 
@@ -178,33 +192,19 @@ int mrt_aov_rays(mrt_ctx *c, const float *orig, const float *dir, uint32_t flags
         ok();
         return MRT_OK;
     }
-    const FlatScene fs = flat_scene(c);
-    if (!fs.blob) return g_status;
-    const Packed &ap = fs.pk;
-    if ((rc = aov_state(c))) return rc;
+    AovPass ap;
+    if ((rc = aov_pass(c, ap))) return rc;
     Aov &a = *c->aov;
-    const size_t words = (size_t)c->pk.nw * c->pk.nh * 3u;
-    DeviceMem<float> d_o, d_d;
-    const float *po = orig, *pd = dir;
-    if (!(flags & MRT_AOV_RAYS_DEVICE)) {
-        HIP_TRY(d_o.alloc(words));
-        HIP_TRY(d_d.alloc(words));
-        HIP_TRY(hipMemcpy(d_o.p, orig, words * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_d.p, dir, words * sizeof(float), hipMemcpyHostToDevice));
-        po = d_o.p; pd = d_d.p;
-    }
-    Params P = ap.P;
-    P.blob = fs.blob;
-    P.segments = a.seg.p;
+    DeviceRays rays;
+    HIP_TRY(rays.take(orig, dir, (size_t)c->pk.nw * c->pk.nh, (flags & MRT_AOV_RAYS_DEVICE) != 0u));
     // whatever fails from here on leaves no half-written planes behind as anybody's AOVs
     c->aov_ready = false;
     a.from_rays = false; a.wrap_x = false;
-    HIP_TRY(launch_aov_rays(P, ap.features, po, pd, a.guide.p, a.albedo.p, a.ids.p, c->stream.get()));
+    HIP_TRY(launch_aov_rays(ap.P, ap.pk->features, rays.orig, rays.dir, a.guide.p, a.albedo.p, a.ids.p, c->stream.get()));
     HIP_TRY(hipStreamSynchronize(c->stream.get()));
-    a.inst_first = inst_first(ap);
     a.from_rays = true;
     a.wrap_x = (flags & MRT_AOV_WRAP_X) != 0u;
-    c->aov_ready = true;
+    aov_done(c, ap);
     ok();
     return MRT_OK;
 }

@@ -59,6 +59,23 @@ inline hipError_t alloc_counters(DeviceMem<unsigned long long> &m)
     const hipError_t e = m.alloc(8);
     return e != hipSuccess ? e : hipMemset(m.p, 0, 8 * sizeof(unsigned long long));
 }
+// Caller-supplied rays on the device for the length of one call (mrt_radiance, mrt_radiance_adaptive, mrt_aov_rays): orig and dir
+// are what a launch reads -- the caller's own device pointers (on_device), or one upload of its n_rays x 3 host floats each
+struct DeviceRays {
+    DeviceMem<float> up_o, up_d;
+    const float *orig = nullptr, *dir = nullptr;
+    hipError_t take(const float *o, const float *d, size_t n_rays, bool on_device)
+    {
+        orig = o; dir = d;
+        if (on_device) return hipSuccess;
+        const size_t words = n_rays * 3u;
+        hipError_t e;
+        if ((e = up_o.alloc(words)) || (e = up_d.alloc(words)) || (e = hipMemcpy(up_o.p, o, words * sizeof(float), hipMemcpyHostToDevice)) ||
+            (e = hipMemcpy(up_d.p, d, words * sizeof(float), hipMemcpyHostToDevice))) return e;
+        orig = up_o.p; dir = up_d.p;
+        return hipSuccess;
+    }
+};
 struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
 struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
 using Event = std::unique_ptr<ihipEvent_t, EventDestroy>;
@@ -270,6 +287,13 @@ struct RaysKernel {
     const float *orig = nullptr, *dir = nullptr;
 };
 int rays_kernel(mrt_ctx *c, RaysKernel &k);
+// The flags and reserved words of mrt_rays and mrt_rays_adapt (fn: the caller's name in the message)
+inline int rays_words(uint32_t flags, const uint32_t (&reserved)[3], const char *fn)
+{
+    if (flags & ~(uint32_t)MRT_RAYS_DEVICE) return fail(MRT_ERR_ARG, "%s: unknown flags 0x%x", fn, flags);
+    if (reserved[0] || reserved[1] || reserved[2]) return fail(MRT_ERR_ARG, "%s: reserved words must be 0", fn);
+    return MRT_OK;
+}
 
 // mrt_execute.cpp
 // asynchronous half of mrt_execute on one device: everything up to the closing event

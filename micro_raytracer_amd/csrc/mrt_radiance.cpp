@@ -35,36 +35,28 @@ int mrt_radiance(mrt_ctx *c, const mrt_rays *r, float *rgb, mrt_rays_info *info)
     if (r->n_samples == 0) return fail(MRT_ERR_ARG, "mrt_radiance: n_samples = 0");
     if ((unsigned long long)r->sample_base + r->n_samples > 0xffffffffull)
         return fail(MRT_ERR_ARG, "mrt_radiance: samples [%u, + %u) reach past 2^32 - 1", r->sample_base, r->n_samples);
-    if (r->flags & ~(uint32_t)MRT_RAYS_DEVICE) return fail(MRT_ERR_ARG, "mrt_radiance: unknown flags 0x%x", r->flags);
-    if (r->reserved[0] || r->reserved[1] || r->reserved[2]) return fail(MRT_ERR_ARG, "mrt_radiance: reserved words must be 0");
-    if (c->group) return fail(MRT_ERR_STATE, "mrt_radiance: multi-device context");
     int rc;
+    if ((rc = rays_words(r->flags, r->reserved, "mrt_radiance"))) return rc;
+    if (c->group) return fail(MRT_ERR_STATE, "mrt_radiance: multi-device context");
     if ((rc = set_device(c))) return rc;
     RaysKernel k;
     if ((rc = rays_kernel(c, k))) return rc;
-    Params &P = k.P;
-    const u32 inst = k.inst;
-    const bool in_lds = k.in_lds;
-    const size_t lds = k.lds;
     const size_t n = r->n;
     const bool dev = (r->flags & MRT_RAYS_DEVICE) != 0u;
-    DeviceMem<float> d_o, d_d, d_rgb;
+    DeviceRays rays;
+    DeviceMem<float> d_rgb;
     DeviceMem<u32> d_key;
-    const float *po = r->orig, *pd = r->dir;
     const u32 *pkey = r->key;
     float *pout = rgb;
+    HIP_TRY(rays.take(r->orig, r->dir, n, dev));
     if (!dev) {
-        HIP_TRY(d_o.alloc(n * 3u));
-        HIP_TRY(d_d.alloc(n * 3u));
         HIP_TRY(d_rgb.alloc(n * 3u));
-        HIP_TRY(hipMemcpy(d_o.p, r->orig, n * 3u * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_d.p, r->dir, n * 3u * sizeof(float), hipMemcpyHostToDevice));
+        pout = d_rgb.p;
         if (r->key) {
             HIP_TRY(d_key.alloc(n));
             HIP_TRY(hipMemcpy(d_key.p, r->key, n * sizeof(u32), hipMemcpyHostToDevice));
             pkey = d_key.p;
         }
-        po = d_o.p; pd = d_d.p; pout = d_rgb.p;
     }
     // everything the kernel writes belongs to the call: the sums, and a segment counter of its own
     DeviceMem<unsigned long long> d_seg;
@@ -74,13 +66,13 @@ int mrt_radiance(mrt_ctx *c, const mrt_rays *r, float *rgb, mrt_rays_info *info)
     HIP_TRY(create(e1));
     hipStream_t st = c->stream.get();
     HIP_TRY(hipMemsetAsync(pout, 0, n * 3u * sizeof(float), st));
-    P.n_samples = r->n_samples; P.sample_base = r->sample_base;
-    P.k_split = 1u; P.to_planes = 0u;
-    P.accum = pout; P.partial = nullptr; P.partial_stride = 0ull;
-    P.count_segments = 1u; P.segments = d_seg.p;
-    P.tile_counter = nullptr; P.persist_grid = 0u;
+    k.P.n_samples = r->n_samples; k.P.sample_base = r->sample_base;
+    k.P.k_split = 1u; k.P.to_planes = 0u;
+    k.P.accum = pout; k.P.partial = nullptr; k.P.partial_stride = 0ull;
+    k.P.count_segments = 1u; k.P.segments = d_seg.p;
+    k.P.tile_counter = nullptr; k.P.persist_grid = 0u;
     HIP_TRY(hipEventRecord(e0.get(), st));
-    HIP_TRY(launch_rays(P, in_lds, inst, (u32)n, po, pd, pkey, st));
+    HIP_TRY(launch_rays(k.P, k.in_lds, k.inst, (u32)n, rays.orig, rays.dir, pkey, st));
     HIP_TRY(hipEventRecord(e1.get(), st));
     HIP_TRY(hipStreamSynchronize(st));
     if (!dev) HIP_TRY(hipMemcpy(rgb, d_rgb.p, n * 3u * sizeof(float), hipMemcpyDeviceToHost));
@@ -93,9 +85,9 @@ int mrt_radiance(mrt_ctx *c, const mrt_rays *r, float *rgb, mrt_rays_info *info)
         info->kernel_ms = t;
         info->samples = (uint64_t)n * r->n_samples;
         info->segments = seg;
-        info->kernel_features = inst;
-        info->scene_in_lds = in_lds ? 1u : 0u;
-        info->lds_bytes = (uint32_t)lds;
+        info->kernel_features = k.inst;
+        info->scene_in_lds = k.in_lds ? 1u : 0u;
+        info->lds_bytes = (uint32_t)k.lds;
     }
     ok();
     return MRT_OK;

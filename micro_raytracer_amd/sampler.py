@@ -12,6 +12,7 @@ Rust shim in INTEGRATION.md does.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import zlib
 
 import numpy as np
@@ -64,6 +65,60 @@ def _fingerprint(render: Render):
         out.append((o.kind, o.r, arr(o.n), arr(o.sizes), arr(o.vtx), arr(o.mesh), arr(o.uv), arr(o.vn), arr(m.albedo), m.rough, m.metal, m.glass,
                     m.opacity, m.emit, tuple(tex(getattr(m, k)) for k in _abi.MAP_SLOTS), insts(o.inst)))
     return tuple(out)
+
+
+def _ray_args(fn, orig, dir, shape, key=None, mixed=None):
+    """A pair of ray arrays as the C ABI takes them, for the caller named fn.  shape: what both must be ((nh, nw, 3)), or None for
+    any [..., 3] with equal shapes.  key: optional 32-bit words, one per ray.  mixed: the caller's text for inputs that are not all
+    on one side.  Numpy arrays go through the host; torch tensors on a device are read in place, after a synchronize of that
+    device (the library launches on a stream of its own).  Returns (keep, (orig_ptr, dir_ptr, key_ptr), on_device): keep holds the
+    contiguous f32 orig and dir, then the key words if any, and must outlive the call the pointers go to."""
+    def check(so, sd):
+        if shape is None:
+            if so != sd or so[-1] != 3:
+                raise ValueError(f"{fn}: orig and dir are [..., 3]")
+        elif so != shape or sd != shape:
+            raise ValueError(f"{fn}: orig and dir are {shape}, got {so} and {sd}")
+
+    dev = type(orig).__module__.split(".")[0] == "torch"
+    if dev:
+        import torch
+        if not (orig.is_cuda and getattr(dir, "is_cuda", False)) or (key is not None and not getattr(key, "is_cuda", False)):
+            raise ValueError(mixed or f"{fn}: orig and dir are both tensors on the context's device, or both host arrays")
+        check(tuple(orig.shape), tuple(dir.shape))
+        keep = (orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous())
+        if key is not None:
+            words = (torch.int32, getattr(torch, "uint32", torch.int32))          # the same 32 bits either way
+            keep += ((key if key.dtype in words else key.to(torch.int64).to(torch.int32)).contiguous(),)
+    else:
+        keep = (np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32))
+        check(keep[0].shape, keep[1].shape)
+        if key is not None:
+            keep += (np.ascontiguousarray(key, np.uint32),)
+    if key is not None and math.prod(keep[2].shape) != math.prod(keep[0].shape[:-1]):
+        raise ValueError(f"{fn}: one key per ray")
+    if dev:
+        torch.cuda.synchronize(keep[0].device)
+    return keep, [a.data_ptr() if dev else a.ctypes.data for a in keep] + [None] * (key is None), dev
+
+
+def _fill_rule(a, render, threshold, min_samples, max_samples, step):
+    """The stop rule of both adaptive calls into an _abi.Adapt (max_samples of None: render.rt.sample)"""
+    a.min_samples = int(min_samples)
+    a.max_samples = int(render.rt.sample if max_samples is None else max_samples)
+    a.step = int(step)
+    a.threshold = float(threshold)
+
+
+def _adapt_out(info, secs) -> dict:
+    """mrt_adapt_info as a dict plus the wall time ("seconds")"""
+    return {**_abi.as_dict(info), "seconds": secs.value}
+
+
+def _dn_info(info, di):
+    """mrt_denoise_info (and "mode", its reserved[0]) into the caller's dict, if there is one"""
+    if info is not None:
+        info.update(_abi.as_dict(di), mode=int(di.reserved[0]))
 
 
 class Sampler:
@@ -179,16 +234,11 @@ class Sampler:
         plus the wall time ("seconds")."""
         self._ensure(render)
         a = _abi.Adapt()
-        a.min_samples = int(min_samples)
-        a.max_samples = int(render.rt.sample if max_samples is None else max_samples)
-        a.step = int(step)
-        a.threshold = float(threshold)
+        _fill_rule(a, render, threshold, min_samples, max_samples, step)
         info = _abi.AdaptInfo()
         secs = C.c_double()
         _lib.check(_lib.lib().mrt_execute_adaptive(self._ctx, C.byref(a), C.byref(info), C.byref(secs)))
-        out = {k: getattr(info, k) for k, _ in info._fields_}
-        out["seconds"] = secs.value
-        return out
+        return _adapt_out(info, secs)
 
     def sample_counts(self) -> np.ndarray:
         """Samples accumulated per supersampled pixel, uint32 [nh][nw]."""
@@ -240,22 +290,9 @@ class Sampler:
             return
         if orig is None or dir is None:
             raise ValueError("aov_rays: orig and dir are both given, or both None")
-        shape = (self.nh, self.nw, 3)
-        flags = _abi.AOV_WRAP_X if wrap_x else 0
-        if type(orig).__module__.split(".")[0] == "torch":
-            import torch
-            if not (orig.is_cuda and getattr(dir, "is_cuda", False)):
-                raise ValueError("aov_rays: orig and dir are both tensors on the context's device, or both host arrays")
-            if tuple(orig.shape) != shape or tuple(dir.shape) != shape:
-                raise ValueError(f"aov_rays: orig and dir are {shape}, got {tuple(orig.shape)} and {tuple(dir.shape)}")
-            o, d = orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous()
-            torch.cuda.synchronize(o.device)          # the library launches on a stream of its own
-            _lib.check(L.mrt_aov_rays(self._ctx, o.data_ptr(), d.data_ptr(), flags | _abi.AOV_RAYS_DEVICE))
-        else:
-            o, d = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
-            if o.shape != shape or d.shape != shape:
-                raise ValueError(f"aov_rays: orig and dir are {shape}, got {o.shape} and {d.shape}")
-            _lib.check(L.mrt_aov_rays(self._ctx, o.ctypes.data, d.ctypes.data, flags))
+        keep, (po, pd, _), dev = _ray_args("aov_rays", orig, dir, (self.nh, self.nw, 3))
+        _lib.check(L.mrt_aov_rays(self._ctx, po, pd, (_abi.AOV_WRAP_X if wrap_x else 0) | (_abi.AOV_RAYS_DEVICE if dev else 0)))
+        del keep
 
     def denoise(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None, mode="atrous",
                 sigma_var=None, firefly=None) -> np.ndarray:
@@ -268,9 +305,7 @@ class Sampler:
         out = np.empty((self.nh, self.nw, 3), np.float32)
         di = _abi.DenoiseInfo()
         _lib.check(_lib.lib().mrt_denoise(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(di)))
-        if info is not None:
-            info.update({k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"})
-            info["mode"] = int(di.reserved[0])
+        _dn_info(info, di)
         return out
 
     def img_denoised(self, passes=_abi.DENOISE_PASSES, sigma_color=None, sigma_normal=None, sigma_plane=None, info=None, mode="atrous",
@@ -281,9 +316,7 @@ class Sampler:
         out = np.empty((self.res[1], self.res[0], 3), np.uint8)
         di = _abi.DenoiseInfo()
         _lib.check(_lib.lib().mrt_img_denoised(self._ctx, C.byref(o), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(di)))
-        if info is not None:
-            info.update({k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"})
-            info["mode"] = int(di.reserved[0])
+        _dn_info(info, di)
         return out
 
     def img_hdr(self, filter="lanczos3", denoise=None, info=None) -> np.ndarray:
@@ -306,8 +339,7 @@ class Sampler:
         if info is not None:
             info["resize_ms"] = hi.resize_ms
             if dn is not None:
-                info.update({k: getattr(hi.dn, k) for k, _ in hi.dn._fields_ if k != "reserved"})
-                info["mode"] = int(hi.dn.reserved[0])
+                _dn_info(info, hi.dn)
         return out
 
     # -- radiance along caller-supplied rays (mrt_radiance) --------------------
@@ -330,44 +362,15 @@ class Sampler:
         self._ensure(render)
         r = _abi.Rays()
         r.sample_base, r.n_samples = int(sample_base), int(n_samples)
-        if type(orig).__module__.split(".")[0] == "torch":
-            import torch
-            if not (orig.is_cuda and getattr(dir, "is_cuda", False)) or (key is not None and not getattr(key, "is_cuda", False)):
-                raise ValueError("radiance: orig, dir and key are all tensors on the context's device, or all host arrays")
-            if orig.shape != dir.shape or orig.shape[-1] != 3:
-                raise ValueError("radiance: orig and dir are [..., 3]")
-            o, d = orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous()
-            out = torch.empty_like(o)
-            keep = (o, d, out)
-            r.n, r.orig, r.dir, r.flags = o.numel() // 3, o.data_ptr(), d.data_ptr(), _abi.RAYS_DEVICE
-            if key is not None:
-                words = (torch.int32, getattr(torch, "uint32", torch.int32))          # the same 32 bits either way
-                k = (key if key.dtype in words else key.to(torch.int64).to(torch.int32)).contiguous()
-                if k.numel() != r.n:
-                    raise ValueError("radiance: one key per ray")
-                keep += (k,)
-                r.key = k.data_ptr()
-            torch.cuda.synchronize(o.device)          # the library launches on a stream of its own
-            out_ptr = out.data_ptr()
-        else:
-            o, d = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
-            if o.shape != d.shape or o.shape[-1] != 3:
-                raise ValueError("radiance: orig and dir are [..., 3]")
-            out = np.empty_like(o)
-            keep = (o, d, out)
-            r.n, r.orig, r.dir = o.size // 3, o.ctypes.data, d.ctypes.data
-            if key is not None:
-                k = np.ascontiguousarray(key, np.uint32)
-                if k.size != r.n:
-                    raise ValueError("radiance: one key per ray")
-                keep += (k,)
-                r.key = k.ctypes.data
-            out_ptr = out.ctypes.data
+        keep, (r.orig, r.dir, r.key), dev = _ray_args("radiance", orig, dir, None, key,
+                                                      "radiance: orig, dir and key are all tensors on the context's device, or all host arrays")
+        r.n, r.flags = math.prod(keep[0].shape[:-1]), _abi.RAYS_DEVICE if dev else 0
+        out = keep[0].new_empty(keep[0].shape) if dev else np.empty_like(keep[0])
         ri = _abi.RaysInfo()
-        _lib.check(_lib.lib().mrt_radiance(self._ctx, C.byref(r), C.c_void_p(out_ptr), C.byref(ri)))
+        _lib.check(_lib.lib().mrt_radiance(self._ctx, C.byref(r), C.c_void_p(out.data_ptr() if dev else out.ctypes.data), C.byref(ri)))
         del keep
         if info is not None:
-            info.update({k: getattr(ri, k) for k, _ in ri._fields_ if k != "reserved"})
+            info.update(_abi.as_dict(ri))
         return out
 
     def radiance_adaptive(self, render: Render, orig, dir, threshold: float, min_samples: int = 32, max_samples=None, step: int = 16) -> dict:
@@ -379,32 +382,14 @@ class Sampler:
         tensors on the context's device are read in place."""
         self._ensure(render)
         r = _abi.RaysAdapt()
-        r.rule.min_samples = int(min_samples)
-        r.rule.max_samples = int(render.rt.sample if max_samples is None else max_samples)
-        r.rule.step = int(step)
-        r.rule.threshold = float(threshold)
-        shape = (self.nh, self.nw, 3)
-        if type(orig).__module__.split(".")[0] == "torch":
-            import torch
-            if not (orig.is_cuda and getattr(dir, "is_cuda", False)):
-                raise ValueError("radiance_adaptive: orig and dir are both tensors on the context's device, or both host arrays")
-            if tuple(orig.shape) != shape or tuple(dir.shape) != shape:
-                raise ValueError(f"radiance_adaptive: orig and dir are {shape}, got {tuple(orig.shape)} and {tuple(dir.shape)}")
-            o, d = orig.to(torch.float32).contiguous(), dir.to(torch.float32).contiguous()
-            torch.cuda.synchronize(o.device)          # the library launches on a stream of its own
-            r.orig, r.dir, r.flags = o.data_ptr(), d.data_ptr(), _abi.RAYS_DEVICE
-        else:
-            o, d = np.ascontiguousarray(orig, np.float32), np.ascontiguousarray(dir, np.float32)
-            if o.shape != shape or d.shape != shape:
-                raise ValueError(f"radiance_adaptive: orig and dir are {shape}, got {o.shape} and {d.shape}")
-            r.orig, r.dir = o.ctypes.data, d.ctypes.data
+        _fill_rule(r.rule, render, threshold, min_samples, max_samples, step)
+        keep, (r.orig, r.dir, _), dev = _ray_args("radiance_adaptive", orig, dir, (self.nh, self.nw, 3))
+        r.flags = _abi.RAYS_DEVICE if dev else 0
         info = _abi.AdaptInfo()
         secs = C.c_double()
         _lib.check(_lib.lib().mrt_radiance_adaptive(self._ctx, C.byref(r), C.byref(info), C.byref(secs)))
-        del o, d
-        out = {k: getattr(info, k) for k, _ in info._fields_}
-        out["seconds"] = secs.value
-        return out
+        del keep
+        return _adapt_out(info, secs)
 
     # -- extras of the C ABI -----------------------------------------------------------------
     def _need(self):
@@ -475,7 +460,7 @@ class Sampler:
         self._need()
         st = _abi.Stats()
         _lib.check(_lib.lib().mrt_get_stats(self._ctx, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in st._fields_}
+        return _abi.as_dict(st)
 
 
 def raytrace(render: Render, *, seed=1, update=None, batch=None, **kw):

@@ -36,14 +36,9 @@ int ar_camera_rays(const mrt_render_desc *d, const mrt_desc_ext *ext, float *ori
     lane::Packing k;
     const int rc = lane::pack(d, ext, PackOpts(), lane::Level(), k, g_err);
     if (rc) return rc;
-    for (u32 y = 0; y < k.pk.nh; ++y)
-        for (u32 x = 0; x < k.pk.nw; ++x) {
-            V3 o, dd;
-            camera_ray_centre(k.P, k.S.F + k.P.off_cam, pixel_focus(k.P, (float)x, (float)y), o, dd);
-            const size_t p = (size_t)y * k.pk.nw + x;
-            orig[3 * p] = o.x; orig[3 * p + 1] = o.y; orig[3 * p + 2] = o.z;
-            dir[3 * p] = dd.x; dir[3 * p + 1] = dd.y; dir[3 * p + 2] = dd.z;
-        }
+    lane::camera_rays(k, orig, dir, [&](u32 x, u32 y, V3 &o, V3 &dd) {
+        camera_ray_centre(k.P, k.S.F + k.P.off_cam, pixel_focus(k.P, (float)x, (float)y), o, dd);
+    });
     return 0;
 }
 
@@ -69,13 +64,8 @@ int ar_aov_rays(const mrt_render_desc *d, const mrt_desc_ext *ext, uint64_t n, c
     const std::vector<u32> first = inst_first(k.pk);
     const u32 inst = lane::lane_inst(k.pk, 0u, false);
     const bool known = lane::with_feat(inst, [&](auto feat) {
-        for (size_t p = 0; p < n; ++p) {
-            const AovPixel a = aov_ray<decltype(feat)::value>(k.S, v3(orig[3 * p], orig[3 * p + 1], orig[3 * p + 2]), v3(dir[3 * p], dir[3 * p + 1], dir[3 * p + 2]));
-            memcpy(guide + 8 * p, &a.g, sizeof(DnGuide));
-            albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
-            renderer[p] = a.rend;
-            instance[p] = a.rend < 0 ? -1 : a.inst - (i32)first[(u32)a.rend];
-        }
+        for (size_t p = 0; p < n; ++p)
+            lane::aov_store(aov_ray<decltype(feat)::value>(k.S, lane::ray_at(orig, p), lane::ray_at(dir, p)), first, p, guide, albedo, renderer, instance);
     });
     k.P.segments = nullptr;
     return known ? 0 : lane::no_inst(inst, g_err);
@@ -87,29 +77,12 @@ void ar_pass(const float *e, const float *guide, uint32_t nw, uint32_t nh, uint3
     dn_pass_host(e, reinterpret_cast<const DnGuide *>(guide), nw, nh, step, sc, sn, sp, out, wrap_x != 0u);
 }
 
-// mrt_denoise on installed planes: the chain of lane::atrous_host with the wrap flag -- the filtered means out[nh][nw][3] of the sums
+// mrt_denoise on installed planes: lane::atrous_host with the wrap flag -- the filtered means out[nh][nw][3] of the sums
 // A[nh][nw][3] at per-pixel counts[nh][nw]; env: the context has an environment texture
 void ar_filter(const float *A, const uint32_t *counts, const float *guide, const float *albedo, uint32_t nw, uint32_t nh, uint32_t passes,
                float sc, float sn, float sp, uint32_t env, uint32_t wrap_x, float *out)
 {
-    const size_t np = (size_t)nw * nh;
-    const DnGuide *g = reinterpret_cast<const DnGuide *>(guide);
-    std::vector<float> e(np * 3), t(np * 3);
-    for (size_t p = 0; p < np; ++p) {
-        const float rc = 1.0f / (float)counts[p];
-        for (int c3 = 0; c3 < 3; ++c3) {
-            const float c = A[3 * p + c3] * rc;
-            if (passes == 0u) out[3 * p + c3] = c;
-            else e[3 * p + c3] = c / dn_demod(albedo[3 * p + c3], g[p].hit, env != 0u);
-        }
-    }
-    if (passes == 0u) return;
-    for (u32 i = 0; i < passes; ++i) {
-        dn_pass_host(e.data(), g, nw, nh, 1u << i, dn_pass_sc(sc, i), sn, sp, t.data(), wrap_x != 0u);
-        e.swap(t);
-    }
-    for (size_t p = 0; p < np; ++p)
-        for (int c3 = 0; c3 < 3; ++c3) out[3 * p + c3] = e[3 * p + c3] * dn_demod(albedo[3 * p + c3], g[p].hit, env != 0u);
+    lane::atrous_host(A, counts, guide, albedo, nw, nh, passes, sc, sn, sp, env != 0u, out, wrap_x != 0u);
 }
 
 }

@@ -2,7 +2,9 @@
 // does and wires up the Scn the lane code reads (pack), names the kernel instantiation a probe runs (lane_inst: the full feature
 // set at a staging level, or the F_IDENT build pt_instantiation of csrc/mrt_inst.h picks), dispatches a run-time FEAT to its
 // compiled instantiation (with_feat over LANE_FEAT_LIST) and runs whole frames: the path tracer's render_pixel over a pool of
-// row-stealing threads (render_frame), the first-hit AOV pass (aov_frame) and the a-trous filter (atrous_host).
+// row-stealing threads (render_frame), the first-hit AOV pass (aov_frame; aov_store for a probe's own loop over supplied rays), the
+// a-trous filter (atrous_host, wrap_x for a grid periodic in x) and the camera-ray loop over a frame (camera_rays); ray_at reads ray
+// i of a packed [n][3] array.
 // Header-only, and included AFTER a probe's MRT_COUNT / MRT_PROBE* hooks: it is what pulls in mrt_trace.h.
 #pragma once
 #include <stdint.h>
@@ -156,8 +158,35 @@ inline int render_frame(Packing &k, u32 inst, uint64_t seed, u32 sample_base, u3
     return 0;
 }
 
+// ray i of a packed [n][3] array, and back
+inline V3 ray_at(const float *a, size_t i) { return v3(a[3 * i], a[3 * i + 1], a[3 * i + 2]); }
+inline void put3(float *a, size_t i, V3 v) { a[3 * i] = v.x; a[3 * i + 1] = v.y; a[3 * i + 2] = v.z; }
+
+// ray(x, y, o, d) -- how the caller's kernel forms the lens-centre ray of a pixel -- over the frame: orig, dir [nh][nw][3]
+template <class Ray>
+inline void camera_rays(const Packing &k, float *orig, float *dir, Ray &&ray)
+{
+    for (u32 y = 0; y < k.pk.nh; ++y)
+        for (u32 x = 0; x < k.pk.nw; ++x) {
+            V3 o, d;
+            ray(x, y, o, d);
+            put3(orig, (size_t)y * k.pk.nw + x, o);
+            put3(dir, (size_t)y * k.pk.nw + x, d);
+        }
+}
+
+// One AovPixel into plane entry p: guide[p][8], albedo[p][3], renderer[p] and, where instance is not NULL, instance[p]: the index
+// within the renderer's inst list (the flat index less the renderer's first of `first` = inst_first(pk), as mrt_aov maps it)
+inline void aov_store(const AovPixel &a, const std::vector<u32> &first, size_t p, float *guide, float *albedo, int32_t *renderer, int32_t *instance)
+{
+    memcpy(guide + 8 * p, &a.g, sizeof(DnGuide));
+    put3(albedo, p, a.albedo);
+    renderer[p] = a.rend;
+    if (instance) instance[p] = a.rend < 0 ? -1 : a.inst - (i32)first[(u32)a.rend];
+}
+
 // mrt_aov: guide[nh][nw][8] (normal, depth, world point, hit flag), albedo[nh][nw][3], renderer[nh][nw] and, where instance is not
-// NULL, instance[nh][nw]: the index within the renderer's inst list (the flat index less the renderer's first, as mrt_aov maps it)
+// NULL, instance[nh][nw]
 inline int aov_frame(Packing &k, u32 inst, float *guide, float *albedo, int32_t *renderer, int32_t *instance, std::string &err)
 {
     unsigned long long seg[8] = {0};
@@ -165,23 +194,17 @@ inline int aov_frame(Packing &k, u32 inst, float *guide, float *albedo, int32_t 
     const std::vector<u32> first = inst_first(k.pk);
     const bool known = with_feat(inst, [&](auto feat) {
         for (u32 y = 0; y < k.pk.nh; ++y)
-            for (u32 x = 0; x < k.pk.nw; ++x) {
-                const AovPixel a = aov_pixel<decltype(feat)::value>(k.S, x, y);
-                const size_t p = (size_t)y * k.pk.nw + x;
-                memcpy(guide + 8 * p, &a.g, sizeof(DnGuide));
-                albedo[3 * p] = a.albedo.x; albedo[3 * p + 1] = a.albedo.y; albedo[3 * p + 2] = a.albedo.z;
-                renderer[p] = a.rend;
-                if (instance) instance[p] = a.rend < 0 ? -1 : a.inst - (i32)first[(u32)a.rend];
-            }
+            for (u32 x = 0; x < k.pk.nw; ++x)
+                aov_store(aov_pixel<decltype(feat)::value>(k.S, x, y), first, (size_t)y * k.pk.nw + x, guide, albedo, renderer, instance);
     });
     k.P.segments = nullptr;
     return known ? 0 : no_inst(inst, err);
 }
 
 // mrt_denoise: the filtered means out[nh][nw][3] of the sums A[nh][nw][3] at per-pixel counts[nh][nw], guided by guide / albedo;
-// env: the context has an environment texture (miss pixels demodulated by their albedo too)
+// env: the context has an environment texture (miss pixels demodulated by their albedo too); wrap_x: the frame is periodic in x
 inline void atrous_host(const float *A, const uint32_t *counts, const float *guide, const float *albedo, uint32_t nw, uint32_t nh, uint32_t passes,
-                        float sc, float sn, float sp, bool env, float *out)
+                        float sc, float sn, float sp, bool env, float *out, bool wrap_x = false)
 {
     const size_t np = (size_t)nw * nh;
     const DnGuide *g = reinterpret_cast<const DnGuide *>(guide);
@@ -196,7 +219,7 @@ inline void atrous_host(const float *A, const uint32_t *counts, const float *gui
     }
     if (passes == 0u) return;
     for (u32 i = 0; i < passes; ++i) {
-        dn_pass_host(e.data(), g, nw, nh, 1u << i, dn_pass_sc(sc, i), sn, sp, t.data());
+        dn_pass_host(e.data(), g, nw, nh, 1u << i, dn_pass_sc(sc, i), sn, sp, t.data(), wrap_x);
         e.swap(t);
     }
     for (size_t p = 0; p < np; ++p)

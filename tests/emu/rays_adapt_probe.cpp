@@ -11,10 +11,9 @@
 
 #include "../../micro_raytracer_amd/csrc/mrt_rays_adapt.h"
 
-// what this probe runs: the eight feature sets of pt_rays_tiles (MRT_RAYS_LIST of csrc/mrt_rays.h)
-#define LANE_FEAT_LIST \
-    LANE_F(F_ALL & ~F_TRI) LANE_F(F_ALL) LANE_F((F_ALL & ~F_TRI) | F_BVH) LANE_F(F_ALL | F_BVH) \
-    LANE_F(F_ALL | F_VATTR) LANE_F(F_ALL | F_BVH | F_VATTR) LANE_F(F_ALL | F_VATTR | F_ENV) LANE_F(F_ALL | F_BVH | F_VATTR | F_ENV)
+// what this probe runs: the feature sets of pt_rays_tiles (MRT_RAYS_LIST of csrc/mrt_rays.h itself)
+#define MRT_RAYS(F) LANE_F(F)
+#define LANE_FEAT_LIST MRT_RAYS_LIST
 #include "lane_host.h"
 
 using namespace mrt;
@@ -62,7 +61,7 @@ int ra_round(const mrt_render_desc *d, const mrt_desc_ext *ext, uint32_t feat, u
             if (!rays_tile_pixel(list[entry], l, nw, nh, p)) continue;
             lane::with_feat(feat, [&](auto f) {
                 u32 sg = 0;
-                rays_tile_body<decltype(f)::value>(k.S, p, phase, v3(orig[3 * p], orig[3 * p + 1], orig[3 * p + 2]), v3(dir[3 * p], dir[3 * p + 1], dir[3 * p + 2]), sg);
+                rays_tile_body<decltype(f)::value>(k.S, p, phase, lane::ray_at(orig, p), lane::ray_at(dir, p), sg);
                 segs += sg;
             });
         }

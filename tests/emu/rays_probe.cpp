@@ -11,10 +11,9 @@
 
 #include "../../micro_raytracer_amd/csrc/mrt_rays.h"
 
-// what this probe runs: the eight feature sets of pt_rays and the F_IDENT builds a scene's own frame kernel may be
-#define LANE_FEAT_LIST \
-    LANE_F(F_ALL & ~F_TRI) LANE_F(F_ALL) LANE_F((F_ALL & ~F_TRI) | F_BVH) LANE_F(F_ALL | F_BVH) \
-    LANE_F(F_ALL | F_VATTR) LANE_F(F_ALL | F_BVH | F_VATTR) LANE_F(F_ALL | F_VATTR | F_ENV) LANE_F(F_ALL | F_BVH | F_VATTR | F_ENV) \
+// what this probe runs: the feature sets of pt_rays (MRT_RAYS_LIST itself) and the F_IDENT builds a scene's own frame kernel may be
+#define MRT_RAYS(F) LANE_F(F)
+#define LANE_FEAT_LIST MRT_RAYS_LIST \
     LANE_F(F_IDENT) LANE_F(F_IDENT | F_BOX) LANE_F(F_IDENT | F_LIGHTS) LANE_F(F_IDENT | F_BOX | F_LIGHTS) LANE_F(F_IDENT | F_BVH) LANE_F(F_IDENT | F_LIGHTS | F_BVH)
 #include "lane_host.h"
 
@@ -45,14 +44,7 @@ int ry_camera_rays(const mrt_render_desc *d, const mrt_desc_ext *ext, float *ori
     lane::Packing k;
     const int rc = lane::pack(d, ext, PackOpts(), lane::Level(), k, g_err);
     if (rc) return rc;
-    for (u32 y = 0; y < k.pk.nh; ++y)
-        for (u32 x = 0; x < k.pk.nw; ++x) {
-            V3 o, dr;
-            camera_ray_of(k.P, k.S.F, x, y, o, dr);
-            const size_t p = ((size_t)y * k.pk.nw + x) * 3;
-            orig[p] = o.x; orig[p + 1] = o.y; orig[p + 2] = o.z;
-            dir[p] = dr.x; dir[p + 1] = dr.y; dir[p + 2] = dr.z;
-        }
+    lane::camera_rays(k, orig, dir, [&](u32 x, u32 y, V3 &o, V3 &dr) { camera_ray_of(k.P, k.S.F, x, y, o, dr); });
     return 0;
 }
 
@@ -80,8 +72,7 @@ int ry_radiance(const mrt_render_desc *d, const mrt_desc_ext *ext, uint32_t feat
             for (uint32_t i = i0; i < n && i < i0 + 64u; ++i)
                 lane::with_feat(feat, [&](auto f) {
                     u32 sg = 0;
-                    rays_body<decltype(f)::value>(k.S, i, v3(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]), v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]),
-                                                  key ? key[i] : i, sg);
+                    rays_body<decltype(f)::value>(k.S, i, lane::ray_at(orig, i), lane::ray_at(dir, i), key ? key[i] : i, sg);
                     local += sg;
                 });
         }

@@ -3,12 +3,11 @@
 kernels (the mapping, the texture's mean, the closed-form render of a mirror sphere under an environment), scene builders and
 a Radiance RGBE encoder."""
 import ctypes as C
-import shutil
 
 import numpy as np
 
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import desc_ptrs as _ptrs, ptr as _p, shared
 from vattr_ref import camera_rays, same_bits
 
 f32 = np.float32
@@ -17,8 +16,7 @@ MAPPINGS = ("sphere", "latlong")
 
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
-def build_probe(out_dir):
-    L = probe_or_skip("env_probe", out_dir)
+def _bind(L):
     fp, u32p, i32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32
     L.ev_error.restype = C.c_char_p
     L.ev_uv.argtypes = [u32, u32, C.c_float, u32, u32, fp, fp, u32p]
@@ -34,29 +32,11 @@ def build_probe(out_dir):
     L.ev_filter.argtypes = [fp, u32p, fp, fp, u32, u32, u32, C.c_float, C.c_float, C.c_float, u32, fp]
     L.ev_filter.restype = None
     L.ev_render.argtypes = [vp, vp, C.c_uint64, u32, u32, u32, u32, fp]
-    return L
-
-
-_SHARED = []
 
 
 def shared_probe():
-    """One build of the probe per process, for the modules that only call it (the build takes about a minute)."""
-    if not _SHARED:
-        import atexit
-        import tempfile
-        d = tempfile.mkdtemp(prefix="env_probe_")
-        atexit.register(shutil.rmtree, d, True)
-        _SHARED.append(build_probe(d))
-    return _SHARED[0]
-
-
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-def _ptrs(holder, with_ext=True):
-    return C.cast(holder.ptr(), C.c_void_p), (holder.ext_ptr() if with_ext else None)
+    """The probe, built once per process (about a minute) for every module that uses it."""
+    return shared("env_probe", _bind)
 
 
 def x86_uv(L, mapping, rot, d, w, h):

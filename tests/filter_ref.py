@@ -10,7 +10,7 @@ import numpy as np
 
 import env_ref as E
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import ptr as _p, shared
 from vattr_ref import camera_rays
 
 f32 = np.float32
@@ -20,8 +20,7 @@ BILINEAR_MAX = f32(2.0 ** 30)
 
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
-def build_probe(out_dir):
-    L = probe_or_skip("filter_probe", out_dir, with_pack=False)
+def _bind(L):
     fp, vp, u32 = C.POINTER(C.c_float), C.c_void_p, C.c_uint32
     L.fl_core.argtypes = [u32, u32, u32, vp, u32, u32, fp, fp]
     L.fl_core.restype = None
@@ -31,17 +30,16 @@ def build_probe(out_dir):
     L.fl_env.restype = None
     L.fl_params_offsets.argtypes = [C.POINTER(u32)]
     L.fl_params_offsets.restype = None
-    return L
+
+
+def shared_probe():
+    return shared("filter_probe", _bind, with_pack=False)
 
 
 def params_offsets(L):
     out = (C.c_uint32 * 4)()
     L.fl_params_offsets(out)
     return dict(zip(("off_mat", "n_rend", "off_env", "off_rend"), (int(v) for v in out)))
-
-
-def _p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 class Tex:

@@ -363,19 +363,18 @@ def attributes(oracle_mod=None):
 
 
 # ---- running a case: the x86 probe, the oracle, the comparison rules ---------------------------------------------------------------
-def build_probe(out_dir):
-    """tests/emu/rayq_probe.cpp, loaded with ctypes; None where there is no g++."""
+def _bind(L):
     import ctypes as C
-
-    from emu.build import build_probe as build
-    L = build("rayq_probe", out_dir)
-    if L is None:
-        return None
     fp, u32p, vp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p
     L.rq_error.restype = C.c_char_p
     L.rq_pack.argtypes = [vp, vp, C.c_uint32, u32p]
     L.rq_trace.argtypes = [vp, vp, u32p, C.c_uint32, fp, fp, u32p, u32p]
-    return L
+
+
+def shared_probe():
+    """tests/emu/rayq_probe.cpp, built once per process and loaded with ctypes; skips the test where there is no g++."""
+    from emu.build import shared
+    return shared("rayq_probe", _bind)
 
 
 def probe_trace(L, holder, cfg, o, d):

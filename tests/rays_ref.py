@@ -3,14 +3,13 @@
 core_ref.render_image with its only source of rays, core_ref.camera_rays, replaced by the window's."""
 import ctypes as C
 import functools
-import shutil
 
 import numpy as np
 
 import core_cases as K
 import core_ref as R
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import desc_ptrs as _ptrs, ptr as _p, shared
 
 f32 = np.float32
 RES, SPP, SEED = (50, 37), 40, 5          # 1850 rays: a partial last wavefront and workgroup; chunks of 16, 16, 8
@@ -19,36 +18,17 @@ F_TRI, F_ALL, F_BVH, F_IDENT, F_VATTR, F_ENV = 2, 15, 16, 256, 512, 1024
 
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
-def build_probe(out_dir):
-    L = probe_or_skip("rays_probe", out_dir)
+def _bind(L):
     fp, u32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32
     L.ry_error.restype = C.c_char_p
     L.ry_info.argtypes = [vp, vp, u32p]
     L.ry_camera_rays.argtypes = [vp, vp, fp, fp]
     L.ry_radiance.argtypes = [vp, vp, u32, C.c_uint64, u32, u32, u32, fp, fp, u32p, u32, fp, C.POINTER(C.c_uint64)]
-    return L
-
-
-_SHARED = []
 
 
 def shared_probe():
-    """One build of the probe per process (half a minute), for both modules."""
-    if not _SHARED:
-        import atexit
-        import tempfile
-        d = tempfile.mkdtemp(prefix="rays_probe_")
-        atexit.register(shutil.rmtree, d, True)
-        _SHARED.append(build_probe(d))
-    return _SHARED[0]
-
-
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-def _ptrs(holder):
-    return C.cast(holder.ptr(), C.c_void_p), (holder.ext_ptr() if hasattr(holder, "ext_ptr") else None)
+    """The probe, built once per process (half a minute) for every module that uses it."""
+    return shared("rays_probe", _bind)
 
 
 INFO_KEYS = ("nw", "nh", "features", "own_inst", "rays_inst", "axis_scan", "lds_words")

@@ -8,18 +8,20 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from emu.build import probe_or_skip
+from emu.build import shared
 
 f32 = np.float32
 
 
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = probe_or_skip("adapt_probe", tmp_path_factory.mktemp("adapt"), with_pack=False)
+def _bind(L):
     fp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
     L.adapt_pixel_errors.argtypes = [fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, fp]
     L.adapt_tile_errors.argtypes = [fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, fp, u32p, u32p]
-    return L
+
+
+@pytest.fixture(scope="module")
+def probe():
+    return shared("adapt_probe", _bind, with_pack=False)
 
 
 def np_pixel_errors(A, H, n):

@@ -12,14 +12,13 @@ GPU: csrc/mrt_denoise.h compiled for x86 (tests/emu/aov_rays_probe.cpp).
 The helpers serve tests/test_gpu_aov_rays.py as well."""
 import ctypes as C
 import os
-import shutil
 
 import numpy as np
 import pytest
 
 import test_denoise_host as D
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import desc_ptrs as _ptrs, ptr as _p, shared
 
 f32 = np.float32
 SIGMAS = ((0.5, 0.25, 0.05), (2.0, np.inf, 0.3))
@@ -27,8 +26,7 @@ WRAP_SHAPES = ((37, 9), (80, 24), (24, 8), (5, 7))          # nw x nh: 37: nw % 
 
 
 # ---- the probe -----------------------------------------------------------------------------------------------------------------
-def build_probe(out_dir):
-    L = probe_or_skip("aov_rays_probe", out_dir)
+def _bind(L):
     fp, u32p, i32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32
     L.ar_error.restype = C.c_char_p
     L.ar_dims.argtypes = [vp, vp, u32p]
@@ -37,34 +35,16 @@ def build_probe(out_dir):
     L.ar_aov_rays.argtypes = [vp, vp, C.c_uint64, fp, fp, fp, fp, i32p, i32p]
     L.ar_pass.argtypes = [fp, fp, u32, u32, u32, C.c_float, C.c_float, C.c_float, u32, fp]
     L.ar_filter.argtypes = [fp, u32p, fp, fp, u32, u32, u32, C.c_float, C.c_float, C.c_float, u32, u32, fp]
-    return L
-
-
-_SHARED = []
 
 
 def shared_probe():
-    """One build of the probe per process, for both modules."""
-    if not _SHARED:
-        import atexit
-        import tempfile
-        d = tempfile.mkdtemp(prefix="aov_rays_probe_")
-        atexit.register(shutil.rmtree, d, True)
-        _SHARED.append(build_probe(d))
-    return _SHARED[0]
+    """The probe, built once per process for both modules."""
+    return shared("aov_rays_probe", _bind)
 
 
 @pytest.fixture(scope="module")
 def probe():
     return shared_probe()
-
-
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-def _ptrs(holder):
-    return C.cast(holder.ptr(), C.c_void_p), holder.ext_ptr()
 
 
 def x86_dims(L, holder):

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import ptr as _p, shared
 
 f32 = np.float32
 TOL = 1e-4          # tests/test_gpu_parity.py: mean radiance against the oracle, per channel, L-inf
@@ -20,19 +20,17 @@ WIN_LO, WIN_HI, AXIS_MAX = f32(2.0 ** -40), f32(2.0 ** 40), f32(2.0 ** 38)
 
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = probe_or_skip("axis_probe", tmp_path_factory.mktemp("axis_probe"))
+def _bind(L):
     fp, u32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32
     L.ax_error.restype = C.c_char_p
     L.ax_pack.argtypes = [vp, u32p, u32p, C.c_uint64]
     L.ax_trace.argtypes = [vp, C.c_int, u32, fp, fp, u32p]
     L.ax_render.argtypes = [vp, C.c_int, C.c_uint64, u32, u32, fp, C.POINTER(C.c_uint64)]
-    return L
 
 
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
+@pytest.fixture(scope="module")
+def probe():
+    return shared("axis_probe", _bind)
 
 
 PACK_KEYS = ("features", "all_ident", "axis_scan", "params_axis_scan", "off_axis", "n_inst", "off_inst", "blob_words")

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import ptr as _p, shared
 from test_axis_scan import _gpu, _tame, probe, x86_trace  # noqa: F401  (probe: the fixture)
 
 f32 = np.float32
@@ -23,18 +23,16 @@ WIN_LO = f32(2.0 ** -40)
 AXIS_WORDS = 2
 
 
-@pytest.fixture(scope="module")
-def redo_probe(tmp_path_factory):
-    L = probe_or_skip("axis_redo_probe", tmp_path_factory.mktemp("axis_redo_probe"))
+def _bind(L):
     fp, u32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32
     L.ar_error.restype = C.c_char_p
     L.ar_trace.argtypes = [vp, C.c_int, u32, fp, fp, u32p]
     L.ar_census.argtypes = [vp, C.c_uint64, u32, fp, C.POINTER(C.c_uint64), u32p]
-    return L
 
 
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
+@pytest.fixture(scope="module")
+def redo_probe():
+    return shared("axis_redo_probe", _bind)
 
 
 def redo_trace(L, holder, axis, orig, dirs):

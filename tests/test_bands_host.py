@@ -9,7 +9,7 @@ import itertools
 
 import pytest
 
-from emu.build import probe_or_skip
+from emu.build import shared
 
 CHUNKS = [1, 2, 3, 4, 5, 63, 64]
 # (tiles, slots): the headline frame, the 512 x 512 frame, a 44 x 20 frame, one tile of a tile list, a frame just below the
@@ -17,13 +17,15 @@ CHUNKS = [1, 2, 3, 4, 5, 63, 64]
 SHAPES = [(32400, 8192), (4096, 8192), (18, 8192), (1, 8192), (99999, 8192), (32400, 0), (300, 96)]
 
 
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = probe_or_skip("bands_probe", tmp_path_factory.mktemp("bands_probe"))
+def _bind(L):
     L.bp_plan.restype = C.c_uint32
     L.bp_plan.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint32)]
     L.bp_max_bands.restype = C.c_uint32
-    return L
+
+
+@pytest.fixture(scope="module")
+def probe():
+    return shared("bands_probe", _bind)
 
 
 def plan(L, n_chunks, tiles, slots, bands=None):

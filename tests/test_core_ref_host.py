@@ -45,11 +45,8 @@ def two_samples_are_twice_one(one, two, ref):
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = Q.build_probe(tmp_path_factory.mktemp("core_ref_probe"))
-    if L is None:
-        pytest.skip("no g++")
-    return L
+def probe():
+    return Q.shared_probe()
 
 
 def oracle_image(oracle_mod, holder, ref):

@@ -8,28 +8,26 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from emu.build import probe_or_skip
+from emu.build import ptr as _p, shared
 
 f32 = np.float32
 K5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], f32)
 
 
-def build_probe(out_dir):
-    L = probe_or_skip("denoise_probe", out_dir)
+def _bind(L):
     fp, u32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
     L.dn_error.restype = C.c_char_p
     L.dn_aov.argtypes = [C.c_void_p, fp, fp, i32p, i32p]
     L.dn_filter.argtypes = [fp, u32p, fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, fp]
-    return L
+
+
+def shared_probe():
+    return shared("denoise_probe", _bind)
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return build_probe(tmp_path_factory.mktemp("denoise"))
-
-
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
+def probe():
+    return shared_probe()
 
 
 def x86_aov(L, holder, nw, nh):

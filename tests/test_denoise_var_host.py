@@ -10,7 +10,7 @@ import pytest
 
 import var_ref as V
 from conftest import ROOT
-from test_denoise_host import build_probe as build_dn_probe
+from test_denoise_host import shared_probe as shared_dn_probe
 from test_denoise_host import random_case, tonemapped, x86_aov
 from test_denoise_host import x86_filter as x86_atrous
 
@@ -20,13 +20,13 @@ SN, SP = V.inv_sq(0.25), V.inv_sq(0.05)
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return V.build_probe(tmp_path_factory.mktemp("denoise_var"))
+def probe():
+    return V.shared_probe()
 
 
 @pytest.fixture(scope="module")
-def dn_probe(tmp_path_factory):
-    return build_dn_probe(tmp_path_factory.mktemp("denoise_var_aov"))
+def dn_probe():
+    return shared_dn_probe()
 
 
 def var_case(rng, nh, nw):

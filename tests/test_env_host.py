@@ -16,8 +16,8 @@ f32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return E.build_probe(tmp_path_factory.mktemp("env_host"))
+def probe():
+    return E.shared_probe()
 
 
 def _same(a, b):

@@ -18,13 +18,13 @@ SIZES = [(1, 1), (1, 7), (7, 1), (61, 31), (1024, 512)]
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return F.build_probe(tmp_path_factory.mktemp("filter_host"))
+def probe():
+    return F.shared_probe()
 
 
 @pytest.fixture(scope="module")
-def env_probe(tmp_path_factory):
-    return E.build_probe(tmp_path_factory.mktemp("filter_host_env"))
+def env_probe():
+    return E.shared_probe()
 
 
 def _same(a, b):

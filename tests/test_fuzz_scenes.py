@@ -265,10 +265,10 @@ def test_fuzz_kernel_headers_on_x86(seed, oracle_mod, emu_mod):
 
 # ---- the extension fuzz -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def aov_probes(tmp_path_factory):
+def aov_probes():
     import env_ref as E
     import test_denoise_host as D
-    return D.build_probe(tmp_path_factory.mktemp("fuzz_ext")), E.shared_probe()
+    return D.shared_probe(), E.shared_probe()
 
 
 def _frame_only(desc):

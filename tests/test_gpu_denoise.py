@@ -5,15 +5,15 @@ import numpy as np
 import pytest
 
 from micro_raytracer_amd import Sampler, _abi, _lib, load_render, scenes
-from test_denoise_host import build_probe, id_edges, inv_sq, same_bits, tonemapped, x86_aov, x86_filter
+from test_denoise_host import id_edges, inv_sq, same_bits, shared_probe, tonemapped, x86_aov, x86_filter
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return build_probe(tmp_path_factory.mktemp("denoise_gpu"))
+def probe():
+    return shared_probe()
 
 
 def sigmas(sc=None, sn=None, sp=None):

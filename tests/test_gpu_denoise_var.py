@@ -8,7 +8,7 @@ import pytest
 
 import var_ref as V
 from micro_raytracer_amd import Sampler, _abi, _lib, load_render, scenes
-from test_denoise_host import build_probe as build_dn_probe
+from test_denoise_host import shared_probe as shared_dn_probe
 from test_denoise_host import tonemapped, x86_aov
 
 pytestmark = pytest.mark.gpu
@@ -17,13 +17,13 @@ INF = float("inf")
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return V.build_probe(tmp_path_factory.mktemp("denoise_var_gpu"))
+def probe():
+    return V.shared_probe()
 
 
 @pytest.fixture(scope="module")
-def dn_probe(tmp_path_factory):
-    return build_dn_probe(tmp_path_factory.mktemp("denoise_var_gpu_aov"))
+def dn_probe():
+    return shared_dn_probe()
 
 
 def uniform_with_half(render, seed, spp=32):
@@ -87,11 +87,11 @@ def test_gpu_var_denoise_textured_albedo(probe, dn_probe):
     s.close()
 
 
-def test_gpu_var_denoise_env_backdrop(probe, tmp_path_factory):
+def test_gpu_var_denoise_env_backdrop(probe):
     """A context with an environment texture: miss pixels are demodulated by the backdrop the centre ray sees."""
     import env_ref as E
     from conftest import make_holder
-    ep = E.build_probe(tmp_path_factory.mktemp("denoise_var_env"))
+    ep = E.shared_probe()
     render, holder = make_holder(scenes.env_scene(res=(43, 31), sample=32, bounce=8, tex_res=(64, 32)))
     s = uniform_with_half(render, 7)
     g, alb, _ = E.x86_aov(ep, holder)

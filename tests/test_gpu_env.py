@@ -15,8 +15,8 @@ TOL = 1e-4      # the project's bar: per-channel L-inf on the mean radiance
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return E.build_probe(tmp_path_factory.mktemp("env_gpu"))
+def probe():
+    return E.shared_probe()
 
 
 def _env(mapping, res=(96, 54), sample=16, crowd=False, tex_res=(64, 32)):

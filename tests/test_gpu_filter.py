@@ -17,8 +17,8 @@ f32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return E.build_probe(tmp_path_factory.mktemp("filter_gpu"))
+def probe():
+    return E.shared_probe()
 
 
 def _env(sky="bilinear", tex="bilinear", mapping="latlong", res=(96, 54), sample=16, crowd=False, tex_res=(64, 32)):

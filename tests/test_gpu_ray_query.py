@@ -21,11 +21,8 @@ SEEN = {}          # (scene in LDS, FEAT) -> cases run: the table of instantiati
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = R.build_probe(tmp_path_factory.mktemp("rayq_probe"))
-    if L is None:
-        pytest.skip("no g++")
-    return L
+def probe():
+    return R.shared_probe()
 
 
 class Ctx:

@@ -14,8 +14,8 @@ TOL = 1e-4      # the project's bar: per-channel L-inf on the mean radiance
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return V.build_probe(tmp_path_factory.mktemp("vattr_gpu"))
+def probe():
+    return V.shared_probe()
 
 
 def _smooth(res=(96, 54), sample=16, n_tris=600, crowd=False):

@@ -11,20 +11,22 @@ import pytest
 
 import hdr_ref as H
 from conftest import ROOT
-from emu.build import probe_or_skip
+from emu.build import shared
 
 f32 = np.float32
 BOX_PAIRS = ((6, 3), (9, 6), (7, 5), (520, 260), (3, 6), (1, 1))
 
 
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = probe_or_skip("hdr_probe", tmp_path_factory.mktemp("hdr"))
+def _bind(L):
     fp, u32p, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32
     L.hd_taps.restype = u32
     L.hd_taps.argtypes = [u32, u32, u32, u32p, u32p, fp, u32]
     L.hd_img.argtypes = [fp, C.c_float, u32p, u32, u32, u32, u32, u32, u32, fp]
-    return L
+
+
+@pytest.fixture(scope="module")
+def probe():
+    return shared("hdr_probe", _bind)
 
 
 def x86_taps(probe, filter, src, dst):

@@ -107,17 +107,19 @@ def _linf(got, ref, spp):
 
 
 # ---- x86: the reduced feature sets ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="session")
-def census_probe(tmp_path_factory):
-    from emu.build import probe_or_skip
-    L = probe_or_skip("census_probe", tmp_path_factory.mktemp("census"))
+def _bind(L):
     u32p, vp, u32 = C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32
     L.cs_error.restype = C.c_char_p
     L.cs_list.argtypes = [u32p, u32]
     L.cs_list.restype = u32
     L.cs_features.argtypes = [vp, vp, u32p]
     L.cs_render.argtypes = [vp, vp, u32, C.c_uint64, u32, u32, C.POINTER(C.c_float)]
-    return L
+
+
+@pytest.fixture(scope="session")
+def census_probe():
+    from emu.build import shared
+    return shared("census_probe", _bind)
 
 
 def _x86(L, holder, inst, spp):

@@ -29,8 +29,8 @@ FUZZ = [("random", k) for k in range(40)] + [("crowd", k) for k in range(8)] + [
 
 
 @pytest.fixture(scope="module")
-def probes(tmp_path_factory):
-    return D.build_probe(tmp_path_factory.mktemp("oracle_aov")), E.shared_probe()
+def probes():
+    return D.shared_probe(), E.shared_probe()
 
 
 def fuzz_desc(family, seed):

@@ -27,8 +27,8 @@ RES = (96, 54)
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return E.build_probe(tmp_path_factory.mktemp("oracle_ext"))
+def probe():
+    return E.shared_probe()
 
 
 def _same(a, b):

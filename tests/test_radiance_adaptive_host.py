@@ -14,7 +14,7 @@ import pytest
 import radiance_adapt_cases as AC
 import rays_ref as Y
 from conftest import make_holder
-from emu.build import probe_or_skip
+from emu.build import ptr as _p, shared
 
 f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,17 +25,15 @@ LISTED = [3, 0, 2]                    # tile 1 is left out; the list is in no pa
 LISTED_GRID = [29, 3, 14, 0, 23, 8, 27, 11, 5, 16, 21, 24, 1, 18, 7, 26, 13]
 
 
-@pytest.fixture(scope="module")
-def adapt_probe(tmp_path_factory):
-    L = probe_or_skip("rays_adapt_probe", tmp_path_factory.mktemp("rays_adapt_probe"))
+def _bind(L):
     fp, u32p, vp, u32 = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32
     L.ra_error.restype = C.c_char_p
     L.ra_round.argtypes = [vp, vp, u32, C.c_uint64, u32, u32, u32, u32, u32p, fp, fp, fp, fp, C.POINTER(C.c_uint64)]
-    return L
 
 
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
+@pytest.fixture(scope="module")
+def adapt_probe():
+    return shared("rays_adapt_probe", _bind)
 
 
 def _round(L, holder, feat, base, n, k_split, tiles, o, d, accum, half, seed=Y.SEED):

@@ -18,11 +18,8 @@ MAX_EXCLUDED_SHARE = 0.01          # the issue's ceiling; the rule below exclude
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    L = R.build_probe(tmp_path_factory.mktemp("rayq_probe"))
-    if L is None:
-        pytest.skip("no g++")
-    return L
+def probe():
+    return R.shared_probe()
 
 
 def excluded(case):

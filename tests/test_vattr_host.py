@@ -17,8 +17,8 @@ f32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    return V.build_probe(tmp_path_factory.mktemp("vattr"))
+def probe():
+    return V.shared_probe()
 
 
 # ---- 1. interpolation: x86 build of mrt_trace.h against numpy float32 ----------------------------------------------------------------

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from emu.build import probe_or_skip
+from emu.build import ptr as _p, shared
 
 f32 = np.float32
 K5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16], f32)
@@ -13,16 +13,14 @@ EPS = f32(1e-6)
 INF = float("inf")
 
 
-def build_probe(out_dir):
-    L = probe_or_skip("var_probe", out_dir, with_pack=False)
+def _bind(L):
     fp, u32p, u32, f = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32, C.c_float
     L.dv_prep.argtypes = [fp, fp, u32p, fp, fp, u32, u32, u32, f, fp]
     L.dv_filter.argtypes = [fp, fp, u32p, fp, fp, u32, u32, u32, f, f, f, f, u32, fp, fp]
-    return L
 
 
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
+def shared_probe():
+    return shared("var_probe", _bind, with_pack=False)
 
 
 def inv_sq(sigma):

@@ -5,15 +5,14 @@ import ctypes as C
 
 import numpy as np
 
-from emu.build import probe_or_skip
+from emu.build import desc_ptrs as _ptrs, ptr as _p, shared
 
 f32 = np.float32
 WARM = 0xFFFFFFFF      # deep_nodes value of the probe: the warm (F_COLD) lane code on the binary triangle BVHs
 
 
 # ---- the probe ---------------------------------------------------------------------------------------------------------------
-def build_probe(out_dir):
-    L = probe_or_skip("vattr_probe", out_dir)
+def _bind(L):
     fp, u32p, i32p, vp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p
     L.va_error.restype = C.c_char_p
     L.va_interp.argtypes = [C.c_uint32] + [fp] * 9
@@ -23,15 +22,10 @@ def build_probe(out_dir):
     L.va_pack.argtypes = [vp, vp, u32p, C.c_uint32, u32p]
     L.va_aov.argtypes = [vp, vp, C.c_uint32, fp, fp, i32p]
     L.va_render.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, fp]
-    return L
 
 
-def _p(a, t=C.c_float):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-def _ptrs(holder, with_ext=True):
-    return C.cast(holder.ptr(), C.c_void_p), (holder.ext_ptr() if with_ext else None)
+def shared_probe():
+    return shared("vattr_probe", _bind)
 
 
 PACK_KEYS = ("features", "off_vattr", "n_vattr_rows", "blob_words", "lds_words", "lds_words_warm", "lds_words_hot", "off_rend")
