@@ -538,6 +538,57 @@ typedef struct mrt_rays_adapt {
 } mrt_rays_adapt;
 int mrt_radiance_adaptive(mrt_ctx *ctx, const mrt_rays_adapt *r, mrt_adapt_info *info /*may be NULL*/, double *seconds /*may be NULL*/);
 
+/* ---- point gathers: irradiance and SH9 light probes, lightmap baking ----
+ * mrt_gather forms n_dirs rays at each of n points on the device, path-traces them by the rules of mrt_radiance and reduces the
+ * radiance of each point's rays to one answer; neither the rays nor their sums leave the device.
+ * Directions (csrc/mrt_gather.h, f32, unfused): a spherical Fibonacci set turned per point by a hashed angle.  Point i has the
+ * point key key_base + i; rot_i = mix32(pix_key(key_base + i) + 0x85EBCA6B) with the pix_key of mrt_radiance; direction j has the
+ * azimuth phi = 6.28318548f * u32_to_unit(rot_i + j * 0x9E3779B9), (s, c) = sincos(phi), and
+ *   MRT_GATHER_SPHERE     z = 1 - (2j + 1) / n_dirs, q = sqrt(max(0, 1 - z z)), d = (q c, q s, z)
+ *   MRT_GATHER_HEMI_COS   u = (2j + 1) / (2 n_dirs), local (sqrt(u) c, sqrt(u) s, sqrt(1 - u)), taken to the world by the branchless
+ *                         frame of Duff et al. 2017 about n = normal[i] / |normal[i]|: d = (t lx + bt ly) + n lz
+ * stored as formed (no renormalisation).  Ray (i, j) starts at pos[i] + d * offset (SPHERE) or pos[i] + n * offset (HEMI_COS), has
+ * the hash key key_base + i * n_dirs + j (mod 2^32) and is sampled n_samples times from sample_base as mrt_radiance samples it: its
+ * canonical sum S_ij gives L_ij = S_ij * (1.0f / n_samples).
+ * Reduction: one wavefront per point.  Lane l adds its terms j = l, l + 64, ... in rising j from +0 -- L_ij (MEAN) or
+ * L_ij.c * Y_k(d_ij) (SH9) --, the 64 partials are combined pairwise (p[l] += p[l + 32], then 16, 8, 4, 2, 1), and p[0] is scaled
+ * by 1.0f / n_dirs (MEAN) or 12.566370614f / n_dirs (SH9).  Y_0..Y_8: 0.282094792, 0.488602512 (y, z, x), 1.092548431 xy,
+ * 1.092548431 yz, 0.315391565 (3 zz - 1), 1.092548431 xz, 0.546274215 (xx - yy), evaluated at the stored direction.
+ * A zero or non-finite normal gives NaN directions for that point and whatever their reduction gives; other points are not
+ * disturbed.  The points are traced in batches of whole points (default max(1, 2^22 / n_dirs) of them, ~170 MB of workspace
+ * allocated once per call); the answer does not depend on the batch size.
+ * Like mrt_radiance the call observes and changes nothing of the context; a row-sharded context serves it.
+ * MRT_ERR_ARG: a null ctx, g, pos or out; n outside 1 .. 2^30 - 1; n_dirs outside 1 .. 65536; n_samples == 0 or
+ * sample_base + n_samples > 2^32 - 1; an unknown dist, out or flag; SH9 with HEMI_COS; HEMI_COS without normal, SPHERE with one; an
+ * offset that is non-finite or negative; a non-zero reserved word; mrt_gather_rays: first + count > n.
+ * MRT_ERR_STATE: a multi-device context. */
+#define MRT_GATHER_SPHERE   0u   /* n_dirs directions over the whole sphere, uniform in solid angle           */
+#define MRT_GATHER_HEMI_COS 1u   /* n_dirs directions over the hemisphere about normal[i], cosine-distributed */
+#define MRT_GATHER_MEAN 0u       /* out[n][3]: mean radiance over the set (HEMI_COS: irradiance / pi)          */
+#define MRT_GATHER_SH9  1u       /* out[n][9][3]: radiance projected on the 9 real SH of bands 0..2; SPHERE only */
+typedef struct mrt_gather_desc {
+    size_t n;                   /* points, 1 .. 2^30 - 1 */
+    const float *pos;           /* [n][3] */
+    const float *normal;        /* [n][3], any length; required for HEMI_COS, must be NULL for SPHERE */
+    uint32_t n_dirs;            /* 1 .. 65536 */
+    uint32_t sample_base, n_samples;   /* per ray, rules of mrt_rays */
+    uint32_t dist, out;         /* MRT_GATHER_* */
+    uint32_t key_base;          /* point i has point key key_base + i; ray (i, j) has hash key key_base + i * n_dirs + j (mod 2^32) */
+    float    offset;            /* finite, >= 0: origin = pos + dir * offset (SPHERE), pos + unit normal * offset (HEMI_COS) */
+    uint32_t batch_points;      /* 0: default; else points per internal batch (results do not depend on it) */
+    uint32_t flags;             /* MRT_RAYS_DEVICE: pos, normal and the outputs are device pointers */
+    uint32_t reserved[3];       /* 0 */
+} mrt_gather_desc;
+typedef struct mrt_gather_info {
+    double gen_ms, kernel_ms, reduce_ms;     /* HIP-event times summed over batches */
+    uint64_t rays, samples, segments;
+    uint32_t batches, kernel_features, scene_in_lds, lds_bytes;
+} mrt_gather_info;
+int mrt_gather(mrt_ctx *ctx, const mrt_gather_desc *g, float *out, mrt_gather_info *info /*may be NULL*/);
+/* The rays of points [first, first + count) as mrt_gather forms them: orig, dir [count][n_dirs][3], key [count][n_dirs]; any may be
+ * NULL.  g->out is validated and not used. */
+int mrt_gather_rays(mrt_ctx *ctx, const mrt_gather_desc *g, size_t first, size_t count, float *orig, float *dir, uint32_t *key);
+
 /* ---- linear float image at the output resolution (not in the reference) ----
  * mrt_img tone-maps, truncates to u8 and only then resizes, as the reference does; mrt_img_hdr resamples the mean radiance itself,
  * in f32 on the device, with no tone map and no quantisation: rgb[res_h][res_w][3], linear, >= 0.

@@ -8,6 +8,7 @@
                                   [--tex-filter nearest|bilinear]
                                   [--camera pinhole|equirect [--pano-yaw TURNS] [--pano-guides] [--pano-adaptive THRESHOLD]]
                                   [--resize lanczos3|box]
+                                  [--gather POINTS.npy --gather-out OUT.npy [--gather-dirs D] [--gather-sh]]
 
 Mirrors CLI::raytrace (src/cli.rs:155-177): per-sample loop with optional --update saves, then the final image.
 --adaptive renders with a per-tile noise threshold instead (Sampler.execute_adaptive), --sample being the cap.
@@ -30,6 +31,10 @@ the uniform budget with a half buffer).  Variance mode takes no horizontal taps 
 quantisation; with --denoise the filtered means) as a Radiance picture or a PFM; --resize chooses its filter, Lanczos3 with the
 taps of the 8-bit image or the box (area) average a light probe wants.  A panorama written with --camera equirect -o probe.hdr is
 what --sky-tex probe.hdr --sky-map latlong loads.
+--gather POINTS.npy gathers radiance at points instead of rendering a frame (Sampler.gather): the file holds [n][3] positions (rays
+over the whole sphere) or [n][6], position plus normal (cosine-distributed rays over the hemisphere, the mean is irradiance / pi);
+--gather-dirs rays per point (default 64), --sample path samples per ray; --gather-out receives float32 [n][3], or with
+--gather-sh (positions only) the SH9 probes [n][9][3].  No image is written.
 """
 import argparse
 import sys
@@ -84,6 +89,24 @@ def adaptive_line(info, uniform):
             f"{info['tiles_converged']} of {info['tiles']} tiles converged, per-pixel counts {info['min_count']}..{info['max_count']}")
 
 
+def gather(ap, a, s, render, t0):
+    """--gather: the points of a.gather through Sampler.gather into a.gather_out"""
+    pts = np.load(a.gather)
+    if pts.ndim != 2 or pts.shape[1] not in (3, 6) or pts.shape[0] == 0:
+        ap.error(f"--gather {a.gather}: expected [n][3] or [n][6], got {pts.shape}")
+    if a.gather_sh and pts.shape[1] == 6:
+        ap.error("--gather-sh projects the whole sphere: the points file must hold positions only ([n][3])")
+    pts = pts.astype(np.float32)
+    info = {}
+    out = s.gather(render, pts[:, :3], pts[:, 3:] if pts.shape[1] == 6 else None, n_dirs=64 if a.gather_dirs is None else a.gather_dirs,
+                   n_samples=render.rt.sample, out="sh9" if a.gather_sh else "mean", info=info)
+    np.save(a.gather_out, out)
+    print(f"done: {pts.shape[0]} points x {info['rays'] // pts.shape[0]} rays x {render.rt.sample} spp in {time.perf_counter() - t0:.3f} s -> "
+          f"{a.gather_out} (gen {info['gen_ms']:.3f} ms, trace {info['kernel_ms']:.3f} ms, reduce {info['reduce_ms']:.3f} ms, "
+          f"{info['batches']} batches)", file=sys.stderr)
+    s.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m micro_raytracer_amd")
     ap.add_argument("full", help="full render description (JSON, the reference's schema)")
@@ -121,7 +144,17 @@ def main(argv=None):
                     help="--camera equirect: tile-adaptive sampling on the panorama's rays (--min-sample, --step, --sample as the cap); "
                          "with --pano-guides it allows --denoise-mode variance")
     ap.add_argument("--resize", choices=sorted(_abi.RESIZE_FILTERS), help="filter of a .hdr / .pfm output's resize (default lanczos3)")
+    ap.add_argument("--gather", metavar="POINTS.npy", help="gather radiance at the points of this file ([n][3], or [n][6] with normals) "
+                                                           "instead of rendering; needs --gather-out")
+    ap.add_argument("--gather-out", metavar="OUT.npy", help="--gather: where the float32 answers go")
+    ap.add_argument("--gather-dirs", type=int, metavar="D", help="--gather: rays per point (default 64)")
+    ap.add_argument("--gather-sh", action="store_true", help="--gather: SH9 probes [n][9][3] instead of the mean radiance (positions only)")
     a = ap.parse_args(argv)
+    if a.gather is None:
+        if a.gather_out is not None or a.gather_dirs is not None or a.gather_sh:
+            ap.error("--gather-out / --gather-dirs / --gather-sh need --gather")
+    elif a.gather_out is None:
+        ap.error("--gather needs --gather-out")
     if a.resize is not None and not is_float_output(a.output):
         ap.error("--resize needs a .hdr or .pfm output: the 8-bit image is resized as the reference resizes it")
     if a.camera == "equirect":
@@ -186,6 +219,8 @@ def main(argv=None):
         render.scene.tex_filter = a.tex_filter
     s = Sampler(seed=a.seed)
     t0 = time.perf_counter()
+    if a.gather is not None:
+        return gather(ap, a, s, render, t0)
     if a.camera == "equirect":
         if a.pano_adaptive is None:
             cameras.render_equirect(s, render, yaw=a.pano_yaw or 0.0, guides=a.pano_guides)

@@ -101,6 +101,24 @@ class RaysInfo(C.Structure):
                 ("scene_in_lds", C.c_uint32), ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+GATHER_SPHERE, GATHER_HEMI_COS = 0, 1        # MRT_GATHER_*: mrt_gather_desc.dist
+GATHER_MEAN, GATHER_SH9 = 0, 1               # ... and .out
+GATHER_OUTS = {"mean": GATHER_MEAN, "sh9": GATHER_SH9}
+
+
+class Gather(C.Structure):
+    """mrt_gather_desc: the points of mrt_gather / mrt_gather_rays, their direction set and the reduction"""
+    _fields_ = [("n", C.c_size_t), ("pos", C.c_void_p), ("normal", C.c_void_p), ("n_dirs", C.c_uint32), ("sample_base", C.c_uint32),
+                ("n_samples", C.c_uint32), ("dist", C.c_uint32), ("out", C.c_uint32), ("key_base", C.c_uint32), ("offset", C.c_float),
+                ("batch_points", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class GatherInfo(C.Structure):
+    _fields_ = [("gen_ms", C.c_double), ("kernel_ms", C.c_double), ("reduce_ms", C.c_double), ("rays", C.c_uint64), ("samples", C.c_uint64),
+                ("segments", C.c_uint64), ("batches", C.c_uint32), ("kernel_features", C.c_uint32), ("scene_in_lds", C.c_uint32),
+                ("lds_bytes", C.c_uint32)]
+
+
 class Plan(C.Structure):
     _fields_ = [("staging", C.c_uint32), ("block_threads", C.c_uint32), ("lds_bytes", C.c_uint32), ("staged_bytes", C.c_uint32),
                 ("scene_bytes", C.c_uint32), ("kernel_features", C.c_uint32), ("tbvh_nodes", C.c_uint32), ("tbvh_hot_nodes", C.c_uint32),

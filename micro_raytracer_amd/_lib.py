@@ -23,6 +23,7 @@ SYMBOLS = (
     "mrt_img_hdr", "mrt_save_image_f32",
     "mrt_aov_rays",
     "mrt_radiance_adaptive",
+    "mrt_gather", "mrt_gather_rays",
 )
 
 
@@ -93,6 +94,8 @@ def lib():
     L.mrt_radiance.argtypes = [vp, C.POINTER(_abi.Rays), vp, C.POINTER(_abi.RaysInfo)]
     L.mrt_camera_rays.argtypes = [vp, f32p, f32p]
     L.mrt_radiance_adaptive.argtypes = [vp, C.POINTER(_abi.RaysAdapt), C.POINTER(_abi.AdaptInfo), C.POINTER(C.c_double)]
+    L.mrt_gather.argtypes = [vp, C.POINTER(_abi.Gather), vp, C.POINTER(_abi.GatherInfo)]
+    L.mrt_gather_rays.argtypes = [vp, C.POINTER(_abi.Gather), C.c_size_t, C.c_size_t, vp, vp, vp]
     L.mrt_selftest_instantiations.restype = u32
     L.mrt_aov_rays.argtypes = [vp, vp, vp, u32]
     L.mrt_img_hdr.argtypes = [vp, C.POINTER(_abi.HdrOpts), f32p, C.POINTER(_abi.HdrInfo)]

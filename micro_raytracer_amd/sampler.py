@@ -391,6 +391,65 @@ class Sampler:
         del keep
         return _adapt_out(info, secs)
 
+    # -- point gathers (mrt_gather) --------------------------------------------
+    def _gather_desc(self, fn, pos, normal, n_dirs, n_samples, out, key_base, offset, sample_base, batch_points):
+        """(keep, desc, on_device) of both gather calls: pos (and normal) by the rules of _ray_args, flattened to [n][3]"""
+        if out not in _abi.GATHER_OUTS:
+            raise ValueError(f"{fn}: out `{out}`: expected one of {sorted(_abi.GATHER_OUTS)}")
+        keep, (pp, pn, _), dev = _ray_args(fn, pos, pos if normal is None else normal, None,
+                                           mixed=f"{fn}: pos and normal are both tensors on the context's device, or both host arrays")
+        g = _abi.Gather()
+        g.n, g.pos, g.normal = math.prod(keep[0].shape[:-1]), pp, None if normal is None else pn
+        g.n_dirs, g.n_samples, g.sample_base = int(n_dirs), int(n_samples), int(sample_base)
+        g.dist = _abi.GATHER_SPHERE if normal is None else _abi.GATHER_HEMI_COS
+        g.out, g.key_base, g.offset, g.batch_points = _abi.GATHER_OUTS[out], int(key_base) & 0xffffffff, float(offset), int(batch_points)
+        g.flags = _abi.RAYS_DEVICE if dev else 0
+        return keep, g, dev
+
+    def gather(self, render: Render, pos, normal=None, n_dirs: int = 64, n_samples: int = 16, out: str = "mean", key_base: int = 0,
+               offset: float = 1e-4, sample_base: int = 0, batch_points: int = 0, info=None):
+        """Gather radiance at points (mrt_gather): pos of shape [..., 3]; n_dirs rays per point over the whole sphere (normal None)
+        or cosine-distributed over the hemisphere about normal [..., 3] (any length), each path-traced n_samples times, formed,
+        traced and reduced on the device.  out "mean": f32 [..., 3], the mean radiance over the set (with a normal: irradiance /
+        pi); "sh9" (sphere only): f32 [..., 9, 3], the radiance projected on the 9 real spherical harmonics of bands 0..2
+        (probes.sh9_eval, probes.sh9_irradiance read them).  Point i has the key key_base + i; rays start offset along their
+        direction (sphere) or along the unit normal (hemisphere).  Numpy arrays go through the host; torch tensors on the
+        context's device are read and written in place on the device and a tensor comes back.  info: a dict that receives
+        mrt_gather_info.  Nothing of the context changes."""
+        self._ensure(render)
+        keep, g, dev = self._gather_desc("gather", pos, normal, n_dirs, n_samples, out, key_base, offset, sample_base, batch_points)
+        shape = tuple(keep[0].shape[:-1]) + ((9, 3) if out == "sh9" else (3,))
+        res = keep[0].new_empty(shape) if dev else np.empty(shape, np.float32)
+        gi = _abi.GatherInfo()
+        _lib.check(_lib.lib().mrt_gather(self._ctx, C.byref(g), C.c_void_p(res.data_ptr() if dev else res.ctypes.data), C.byref(gi)))
+        del keep
+        if info is not None:
+            info.update(_abi.as_dict(gi))
+        return res
+
+    def gather_rays(self, render: Render, pos, normal=None, n_dirs: int = 64, key_base: int = 0, offset: float = 1e-4, first: int = 0,
+                    count=None):
+        """(orig, dir, key) of the rays gather() forms for points [first, first + count) of the flattened pos (mrt_gather_rays):
+        f32 [count][n_dirs][3] twice and the hash keys uint32 [count][n_dirs] -- what radiance(orig, dir, n, key=key) takes.  count
+        None: every point from first on.  Numpy in, numpy out; torch tensors on the context's device in, tensors out."""
+        self._ensure(render)
+        keep, g, dev = self._gather_desc("gather_rays", pos, normal, n_dirs, 1, "mean", key_base, offset, 0, 0)
+        count = g.n - int(first) if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("gather_rays: first and count are >= 0")
+        shape = (count, int(n_dirs))
+        if dev:
+            import torch
+            o, d = keep[0].new_empty(shape + (3,)), keep[0].new_empty(shape + (3,))
+            k = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=keep[0].device)
+            ptrs = [C.c_void_p(a.data_ptr()) for a in (o, d, k)]
+        else:
+            o, d, k = np.empty(shape + (3,), np.float32), np.empty(shape + (3,), np.float32), np.empty(shape, np.uint32)
+            ptrs = [C.c_void_p(a.ctypes.data) for a in (o, d, k)]
+        _lib.check(_lib.lib().mrt_gather_rays(self._ctx, C.byref(g), int(first), count, *ptrs))
+        del keep
+        return o, d, k
+
     # -- extras of the C ABI -----------------------------------------------------------------
     def _need(self):
         if self._ctx is None:
